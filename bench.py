@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- the headline metric of BASELINE.json on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 With N > 1 and no WORLD_SIZE in the environment the script re-executes itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free>`
@@ -13,7 +13,10 @@ embedding lookups (with their backward) -> 24 RWKV-7 layers (HIP WKV7 fwd/bwd + 
 fused linear+CE -> backward -> bucketed RCCL gradient all-reduce (N>1) -> AdamW on fp32 master weights.
 Nothing is skipped and nothing in the step waits for the device (the NaN flag stays on the device, trainer.py).
 
-Prints ONE JSON line (rank 0): metric/value/unit per BASELINE.json, plus
+Prints ONE JSON line (rank 0): metric/value/unit per BASELINE.json, ms_per_step (one timed step), the workload, the
+loss of the last step and the device's name.  A plain run does nothing else: set-up, W warm-up steps, K timed steps, the
+line.  --full adds the secondary measurements below, all after the timed region:
+  kernel_ms    : per-launch durations of the WKV7 kernels, HIP events recorded in the timed steps.
   roofline     : the dominant kernel group (WKV7 backward): algorithmic bytes per launch (13*64*2 B per token-head,
                  SURVEY.md section 8d) / its average launch duration measured live with HIP events on the launch
                  stream, against the 8 TB/s HBM peak (MI355X_MICROARCH.md).  `traffic` = HBM bytes per launch,
@@ -25,10 +28,16 @@ Prints ONE JSON line (rank 0): metric/value/unit per BASELINE.json, plus
                  BASELINE.json configs[0] -- RWKV7-0.1B, Cosy layout, B=2, L=512, fwd+bwd, per-token torch scan,
                  all host cores -- plus the WKV scan alone at (B,T,H,N) = (2,512,12,64) through the C oracle
                  (SURVEY.md section 8d); bounded to ~25 s.
+  device       : a box fingerprint: shader clock, copy and GEMM probes, the isolated WKV7 group (wkv7_probe).
+  packed       : (N = 1, spark layout) the same model on the packed variable-length row of --packed, 1 + 3 steps.
   decode       : (N = 1 only, after the timed region, not part of `value`) greedy decode of the same model at
                  BASELINE.json configs[4] -- B=32, prompt 128, 2048 new tokens -- tokens/s, ms per step and the
                  fraction of the weight+state streaming bound (decode.GraphDecoder).
-  comm         : (N > 1) bytes all-reduced per step, bucket count, exposed (non-overlapped) wait per step.
+With N > 1 every line also carries
+  comm         : bytes all-reduced per step, bucket count, exposed (non-overlapped) wait per step.
+
+--dump-outputs DIR writes what the last timed step computed (dump_outputs) before anything else runs on the model.
+The inputs depend on the arguments alone (seeded model init, batches and dropout masks), so two builds can be compared file by file.
 """
 import argparse
 import json
@@ -53,17 +62,19 @@ def _free_port():
     return p
 
 
-def _device_info(torch, dev):
-    """Name / CU count of the GPU the line was measured on, plus a FINGERPRINT of the box (boxes of one pool differ by several per
-    cent in kernel time; lines from different boxes can be normalised by these): the shader clock torch reports right after the
-    timed steps, a ~40 ms device-to-device copy probe (1 GiB read + 1 GiB written, GB/s) and a ~40 ms bf16 GEMM probe
-    (8192 x 8192 x 8192 through the library, TFLOP/s).  Run AFTER the timed region (called when the JSON line is assembled)."""
+def _device_info(torch, dev, probes=True):
+    """Name / CU count of the GPU the line was measured on, plus (probes=True, --full) a FINGERPRINT of the box (boxes of one pool
+    differ by several per cent in kernel time; lines from different boxes can be normalised by these): the shader clock torch
+    reports right after the timed steps, a ~40 ms device-to-device copy probe (1 GiB read + 1 GiB written, GB/s) and a ~40 ms bf16
+    GEMM probe (8192 x 8192 x 8192 through the library, TFLOP/s).  Run AFTER the timed region (called when the JSON line is assembled)."""
     try:
         p = torch.cuda.get_device_properties(dev)
         out = {"name": p.name, "arch": getattr(p, "gcnArchName", ""), "compute_units": p.multi_processor_count,
                "hbm_gib": round(p.total_memory / 2**30)}
     except Exception as e:
         return {"error": repr(e)}
+    if not probes:
+        return out
     try:
         out["sclk_mhz_after_steps"] = int(torch.cuda.clock_rate())
     except Exception:   # amdsmi / rocm-smi bindings absent: the probes below still fingerprint the box
@@ -415,6 +426,39 @@ def decode_rate(model, dev, B=32, P=128, n1=256, n2=2048):
             "sampled": sampled, "multi_group": multi}
 
 
+DUMP_PER_TENSOR = 4096     # sampled elements per parameter in --dump-outputs
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, loss, tr):
+    """--dump-outputs: what the last timed step hands its caller, as float32 .npy files under `path` -- the loss (`loss.npy`) and
+    the model that step left behind: for every trainable parameter, in registration order, the gradient the step computed
+    (`grad_sample.npy`), the updated bf16 weights (`param_sample.npy`) and, when the trainer keeps them on this rank, the fp32
+    master weights (`master_sample.npy`).  A parameter of more than DUMP_PER_TENSOR elements contributes a fixed sample of its
+    elements, drawn from one generator seeded with 0, so the positions depend on the parameter shapes alone.  With the same
+    arguments two runs of one build write the same bits (main() seeds the dropout masks)."""
+    import numpy as np
+    import torch
+    flat = tr.flat
+    g = torch.Generator().manual_seed(0)
+    idx = []
+    for p, o in zip(flat.params, flat.offsets):
+        n = p.numel()
+        sel = torch.arange(n) if n <= DUMP_PER_TENSOR else torch.randint(0, n, (DUMP_PER_TENSOR,), generator=g).sort().values
+        idx.append(sel + o)
+    idx = torch.cat(idx).to(flat.flat_grad.device)
+    arrays = {"loss": loss.detach().float().reshape(1), "grad_sample": flat.flat_grad[idx], "param_sample": flat.flat_param[idx]}
+    if tr.master is not flat.flat_param and not tr.shard_optimizer:
+        arrays["master_sample"] = tr.master[idx]
+    arrays = {k: v.float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes > {DUMP_LIMIT_BYTES}"
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -438,7 +482,7 @@ def main():
                     help="A/B: weight gradients on a second stream (fused.WGRAD_SIDE_STREAM): -2 ms per step, kernels that share the GPU measure longer")
     ap.add_argument("--via-reference-op", action="store_true",
                     help="A/B: the scan through torch.ops.wind_backstepping.forward/backward (the reference's plug-in point, wkv7_op.cpp:21-29; "
-                         "for bf16 and T % 32 == 0 it launches the same chunked MFMA kernels, with `s` as their arena) instead of the direct calls")
+                         "for bf16 and T %% 32 == 0 it launches the same chunked MFMA kernels, with `s` as their arena) instead of the direct calls")
     ap.add_argument("--no-packed", action="store_true", help="skip the secondary packed-row measurement after the timed region (N = 1)")
     ap.add_argument("--packed", action="store_true",
                     help="SURVEY 8f N1: the same B x L positions as ONE packed variable-length row [1, B L, D] + cu_seqlens on the device "
@@ -446,7 +490,14 @@ def main():
     ap.add_argument("--preflight-timeout", type=float, default=60.0, help="N > 1: seconds each preflight collective may take before the watchdog reports")
     ap.add_argument("--step-timeout", type=float, default=300.0, help="N > 1: seconds a training step may take before the watchdog reports")
     ap.add_argument("--scalar-wkv", action="store_true", help="A/B: scalar WKV7 kernels (reference schema fwd, row-split bwd) instead of the chunked MFMA pair")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements after the timed region: per-kernel times and roofline, box fingerprint, "
+                         "packed row, greedy decode, CPU baseline (each still dropped by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss, gradients and weights of the last timed step to DIR/<name>.npy (float32, see dump_outputs)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(a.gpus)   # does not return
 
@@ -597,12 +648,15 @@ def main():
             print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
     log(f"model built: {sum(p.numel() for p in model.parameters()) / 1e6:.1f} M params, layout {a.layout}, B={B} T={T}, world {world}")
+    # the training forward applies the reference's dropout to inputs_embeds (spark_llm.py, xy_llm.py) with masks from torch's device RNG:
+    # seeded here, so that every step's inputs -- batch AND mask -- follow from the arguments alone and two runs compute the same
+    torch.manual_seed(1234 + rank)
     for i in range(a.warmup):
         loss = one_step(i)
         torch.cuda.synchronize()
         log(f"warmup step {i} done, loss {float(loss):.4f}, mem {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB")
     sync()
-    ops.KERNEL_TIMERS = {}
+    ops.KERNEL_TIMERS = {} if a.full else None
     tr.reducer.measure, tr.reducer.wait_events = world > 1, []
     t0 = time.perf_counter()
     for i in range(a.steps):
@@ -615,78 +669,91 @@ def main():
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         dt = float(tt.item())
     loss_val = float(loss.item())
+    if a.dump_outputs and rank == 0:   # before the secondary measurements, which step the same model again
+        log(f"outputs of the last timed step: {dump_outputs(a.dump_outputs, loss, tr)} -> {a.dump_outputs}")
 
     if rank == 0:
         ms = dt / a.steps * 1e3
         tokens_per_rank = sum(lens) if (a.packed and a.layout == "spark") else B * T    # packed: the real tokens, not the aligned buffer
         value = world * tokens_per_rank * a.steps / dt
-        kern = {k: sum(s.elapsed_time(e) for s, e in v) / len(v) for k, v in timers.items() if v}
-        th = B * T * H
-        chunk_parts = [k for k in ("wkv7c_bseq", "wkv7c_bwd_out") if k in kern]
-        if "wkv7c_op_bwd" in kern:   # --via-reference-op: the op's launches are timed as one unit each way
-            bwd_ms, bwd_name = kern["wkv7c_op_bwd"], f"torch.ops.wind_backstepping.backward -> wkv7c_bseq + wkv7c_bwd_out10 ({cfg.num_hidden_layers}x per step)"
-            fwd_ms, fwd_name = kern["wkv7c_op_fwd"], "torch.ops.wind_backstepping.forward -> wkv7c_prep + wkv7c_fwd9"
-            pmc_bwd, pmc_fwd = "wkv7c_bwd", "wkv7c_fwd"
-        elif "wkv7c_bwd_out" in kern:
-            bwd_ms = sum(kern[k] for k in chunk_parts)
-            bwd_name = "WKV7 backward, chunked MFMA (" + " + ".join(chunk_parts) + f", {cfg.num_hidden_layers}x per step)"
-            fwd_ms = kern["wkv7c_fwd"] + kern.get("wkv7c_prep", 0.0)
-            fwd_name = "wkv7c_prep + wkv7c_fwd (chunked MFMA)"
-            pmc_bwd, pmc_fwd = "wkv7c_bwd", "wkv7c_fwd"
-        else:
-            bwd_ms, bwd_name = kern.get("wkv7_bwd"), "wkv7_bwd_kernel<bf16,2,4> (row-split scalar WKV7 backward)"
-            fwd_ms, fwd_name = kern.get("wkv7_fwd"), "wkv7_fwd_kernel (scalar)"
-            pmc_bwd, pmc_fwd = "wkv7_bwd", "wkv7_fwd"
-        pmc = {}
-        try:
-            pmc = json.load(open(os.path.join(ROOT, "profiles", "pmc_wkv7.json")))
-        except Exception:
-            pass
 
-        stale = {}
+        def full_extras(out):
+            """--full: per-kernel times of the timed steps, the roofline of the WKV7 group and the box fingerprint."""
+            kern = {k: sum(s.elapsed_time(e) for s, e in v) / len(v) for k, v in timers.items() if v}
+            th = B * T * H
+            chunk_parts = [k for k in ("wkv7c_bseq", "wkv7c_bwd_out") if k in kern]
+            if "wkv7c_op_bwd" in kern:   # --via-reference-op: the op's launches are timed as one unit each way
+                bwd_ms, bwd_name = kern["wkv7c_op_bwd"], f"torch.ops.wind_backstepping.backward -> wkv7c_bseq + wkv7c_bwd_out10 ({cfg.num_hidden_layers}x per step)"
+                fwd_ms, fwd_name = kern["wkv7c_op_fwd"], "torch.ops.wind_backstepping.forward -> wkv7c_prep + wkv7c_fwd9"
+                pmc_bwd, pmc_fwd = "wkv7c_bwd", "wkv7c_fwd"
+            elif "wkv7c_bwd_out" in kern:
+                bwd_ms = sum(kern[k] for k in chunk_parts)
+                bwd_name = "WKV7 backward, chunked MFMA (" + " + ".join(chunk_parts) + f", {cfg.num_hidden_layers}x per step)"
+                fwd_ms = kern["wkv7c_fwd"] + kern.get("wkv7c_prep", 0.0)
+                fwd_name = "wkv7c_prep + wkv7c_fwd (chunked MFMA)"
+                pmc_bwd, pmc_fwd = "wkv7c_bwd", "wkv7c_fwd"
+            else:
+                bwd_ms, bwd_name = kern.get("wkv7_bwd"), "wkv7_bwd_kernel<bf16,2,4> (row-split scalar WKV7 backward)"
+                fwd_ms, fwd_name = kern.get("wkv7_fwd"), "wkv7_fwd_kernel (scalar)"
+                pmc_bwd, pmc_fwd = "wkv7_bwd", "wkv7_fwd"
+            pmc = {}
+            try:
+                pmc = json.load(open(os.path.join(ROOT, "profiles", "pmc_wkv7.json")))
+            except Exception:
+                pass
 
-        def pmc_of(key):
-            """The committed PMC record of a kernel group -- only when it covers this shape AND was collected on the kernel sources
-            that are shipped now (sha256 of the files recorded by tools/pmc_distill.py): otherwise the fields are null and
-            `pmc_stale` says why."""
-            d = pmc.get(key) or {}
-            if not (d.get("B") == B and d.get("T") == T and d.get("H") == H):
-                return {}
-            rec = d.get("sources")
-            if not rec or build.source_hashes(list(rec)) != rec:
-                stale[key] = "no source hashes in the record" if not rec else \
-                    "kernel sources changed since the PMC pass: " + ", ".join(n for n, h in build.source_hashes(list(rec)).items() if h != rec[n])
-                return {}
-            return d
+            stale = {}
 
-        def traffic(d):
-            return int((2 * d["FETCH_SIZE_KiB"] + d["WRITE_SIZE_KiB"]) * 1024) if "FETCH_SIZE_KiB" in d else None
+            def pmc_of(key):
+                """The committed PMC record of a kernel group -- only when it covers this shape AND was collected on the kernel sources
+                that are shipped now (sha256 of the files recorded by tools/pmc_distill.py): otherwise the fields are null and
+                `pmc_stale` says why."""
+                d = pmc.get(key) or {}
+                if not (d.get("B") == B and d.get("T") == T and d.get("H") == H):
+                    return {}
+                rec = d.get("sources")
+                if not rec or build.source_hashes(list(rec)) != rec:
+                    stale[key] = "no source hashes in the record" if not rec else \
+                        "kernel sources changed since the PMC pass: " + ", ".join(n for n, h in build.source_hashes(list(rec)).items() if h != rec[n])
+                    return {}
+                return d
 
-        gbs = lambda nbytes, t_ms: nbytes / (t_ms * 1e-3) / 1e9 if t_ms else None
-        b_bytes, f_bytes = th * WKV_BWD_BYTES_PER_TOKEN_HEAD, th * WKV_FWD_BYTES_PER_TOKEN_HEAD
-        ach = gbs(b_bytes, bwd_ms)
-        pb, pf = pmc_of(pmc_bwd), pmc_of(pmc_fwd)
-        roof = {"kernel": bwd_name, "bound": "hbm", "achieved": round(ach, 1) if ach else None, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                "frac": round(ach * 1e9 / HBM_PEAK, 4) if ach else None, "traffic": traffic(pb),
-                "mfma_util": pb.get("mfma_util"), "valu_frac": pb.get("valu_frac"), "pmc_source": pb.get("source"),
-                "algorithmic_bytes_per_launch": b_bytes, "launch_ms": round(bwd_ms, 4) if bwd_ms else None}
-        if fwd_ms:
-            roof["fwd"] = {"kernel": fwd_name, "launch_ms": round(fwd_ms, 4), "achieved": round(gbs(f_bytes, fwd_ms), 1),
-                           "frac": round(gbs(f_bytes, fwd_ms) * 1e9 / HBM_PEAK, 4), "traffic": traffic(pf),
-                           "mfma_util": pf.get("mfma_util"), "valu_frac": pf.get("valu_frac"), "algorithmic_bytes_per_launch": f_bytes}
-        from rwkvtts_amd import fused as _fused
-        if getattr(_fused, "WGRAD_SIDE_STREAM", False):
-            # the durations above are measured in the step, where the weight-gradient GEMMs of fused._wgrad run on a second stream
-            # beside these kernels (same-box A/B: the step is 2 ms shorter, these kernels ~5 % longer than when they run alone)
-            roof["concurrent"] = ("weight-gradient GEMMs on a side stream share the GPU with these kernels (without it: WKV7 group "
-                                  "1.05 ms / frac 0.16, step +2 ms)")
-        roof["pmc_stale"] = bool(stale)
-        if stale:
-            roof["pmc_stale_why"] = stale
-        if fwd_ms and bwd_ms:
-            both = gbs(f_bytes + b_bytes, fwd_ms + bwd_ms)
-            roof["fwd_bwd"] = {"launch_ms": round(fwd_ms + bwd_ms, 4), "achieved": round(both, 1), "frac": round(both * 1e9 / HBM_PEAK, 4),
-                               "target_frac": 0.40}
+            def traffic(d):
+                return int((2 * d["FETCH_SIZE_KiB"] + d["WRITE_SIZE_KiB"]) * 1024) if "FETCH_SIZE_KiB" in d else None
+
+            gbs = lambda nbytes, t_ms: nbytes / (t_ms * 1e-3) / 1e9 if t_ms else None
+            b_bytes, f_bytes = th * WKV_BWD_BYTES_PER_TOKEN_HEAD, th * WKV_FWD_BYTES_PER_TOKEN_HEAD
+            ach = gbs(b_bytes, bwd_ms)
+            pb, pf = pmc_of(pmc_bwd), pmc_of(pmc_fwd)
+            roof = {"kernel": bwd_name, "bound": "hbm", "achieved": round(ach, 1) if ach else None, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+                    "frac": round(ach * 1e9 / HBM_PEAK, 4) if ach else None, "traffic": traffic(pb),
+                    "mfma_util": pb.get("mfma_util"), "valu_frac": pb.get("valu_frac"), "pmc_source": pb.get("source"),
+                    "algorithmic_bytes_per_launch": b_bytes, "launch_ms": round(bwd_ms, 4) if bwd_ms else None}
+            if fwd_ms:
+                roof["fwd"] = {"kernel": fwd_name, "launch_ms": round(fwd_ms, 4), "achieved": round(gbs(f_bytes, fwd_ms), 1),
+                               "frac": round(gbs(f_bytes, fwd_ms) * 1e9 / HBM_PEAK, 4), "traffic": traffic(pf),
+                               "mfma_util": pf.get("mfma_util"), "valu_frac": pf.get("valu_frac"), "algorithmic_bytes_per_launch": f_bytes}
+            from rwkvtts_amd import fused as _fused
+            if getattr(_fused, "WGRAD_SIDE_STREAM", False):
+                # the durations above are measured in the step, where the weight-gradient GEMMs of fused._wgrad run on a second stream
+                # beside these kernels (same-box A/B: the step is 2 ms shorter, these kernels ~5 % longer than when they run alone)
+                roof["concurrent"] = ("weight-gradient GEMMs on a side stream share the GPU with these kernels (without it: WKV7 group "
+                                      "1.05 ms / frac 0.16, step +2 ms)")
+            roof["pmc_stale"] = bool(stale)
+            if stale:
+                roof["pmc_stale_why"] = stale
+            if fwd_ms and bwd_ms:
+                both = gbs(f_bytes + b_bytes, fwd_ms + bwd_ms)
+                roof["fwd_bwd"] = {"launch_ms": round(fwd_ms + bwd_ms, 4), "achieved": round(both, 1), "frac": round(both * 1e9 / HBM_PEAK, 4),
+                                   "target_frac": 0.40}
+            out["kernel_ms"] = {k: round(v, 4) for k, v in kern.items()}
+            out["roofline"] = roof
+            try:   # the box-class indicator (DESIGN section 5): the isolated WKV7 group, and the step expressed in units of it
+                out["device"]["wkv7_group_probe_ms"] = wkv7_probe(torch, dev)
+                out["device"]["step_over_wkv7_probe"] = round(ms / out["device"]["wkv7_group_probe_ms"], 2)
+            except Exception as e:
+                out["device"]["wkv7_probe_error"] = repr(e)
+
         which = {("spark", 1): 1, ("spark", 0): 2, ("xy", 1): 3, ("xy", 0): 3}[(a.layout, 1 if world == 1 else 0)]
         out = {
             "metric": "audio-tokens/sec/GPU (train fwd+bwd) RWKV7-0.4B L=4096; 1->8 GPU scaling",
@@ -703,15 +770,10 @@ def main():
                                           "bucket pieces reduced to slab owners + sharded AdamW + parameter broadcast") if world > 1 else "none"},
             "loss": round(loss_val, 4),
             "peak_mem_gib": round(torch.cuda.max_memory_allocated() / 2**30, 1),
-            "kernel_ms": {k: round(v, 4) for k, v in kern.items()},
-            "device": _device_info(torch, dev),
-            "roofline": roof,
+            "device": _device_info(torch, dev, probes=a.full),
         }
-        try:   # the box-class indicator: the isolated WKV7 group, and the step expressed in units of it
-            out["device"]["wkv7_group_probe_ms"] = wkv7_probe(torch, dev)
-            out["device"]["step_over_wkv7_probe"] = round(ms / out["device"]["wkv7_group_probe_ms"], 2)
-        except Exception as e:
-            out["device"]["wkv7_probe_error"] = repr(e)
+        if a.full:
+            full_extras(out)
         if a.packed and a.layout == "spark":
             out["config"]["workload"] += (f"; PACKED: one row [1, {sum(lens)}, D] of {len(lens)} sequences ({min(lens)}..{max(lens)} positions; "
                                           f"32-aligned layout = {B * T} positions), cu_seqlens on the device (SURVEY 8f N1); value counts the {sum(lens)} real tokens")
@@ -725,14 +787,14 @@ def main():
         if world > 1:
             r = tr.reducer
             ev_ms = sum(s_.elapsed_time(e_) for s_, e_ in r.wait_events) / a.steps
-            out["comm"] = {"preflight": pre, "rccl_ranks": world, "backend": r.backend, "bytes_allreduced_per_step": tr.flat.numel * tr.flat.flat_grad.element_size(),
+            out["comm"] ={"preflight": pre, "rccl_ranks": world, "backend": r.backend, "bytes_allreduced_per_step": tr.flat.numel * tr.flat.flat_grad.element_size(),
                            "buckets": len(r.buckets), "bucket_order": "rank 0's gradient-ready order, broadcast (re-cut after the first backward pass); launched in index order" if r.rebuilt else "reverse registration order",
                            "optimizer": "AdamW bucket by bucket as each all-reduce completes" if tr.bucket_optimizer and not tr.shard_optimizer else "one pass behind the last bucket",
                            "bucket_mib": [round(sum(e - s for s, e in runs) * tr.flat.flat_grad.element_size() / 2**20, 1) for runs in r.runs],
                            "bucket_runs": [len(runs) for runs in r.runs],
                            "exposed_wait_ms_per_step": round(sum(s_.elapsed_time(e_) for s_, e_ in r.wait_events) / a.steps, 3),
                            "note": "exposed = time the compute stream stalls in the buckets' wait() calls (HIP event pairs around each bucket's waits, rank 0; the optimizer launches between them are not counted)"}
-        if world == 1 and not a.no_packed and not a.packed and a.layout == "spark" and B * T >= 8192:
+        if a.full and world == 1 and not a.no_packed and not a.packed and a.layout == "spark" and B * T >= 8192:
             # SURVEY 8f N1, after the timed region and not part of `value`: the same model and trainer on the PACKED variable-length
             # workload of --packed (one row of 15 sequences, cu_seqlens on the device), 1 warm-up + 3 timed steps
             try:
@@ -750,12 +812,12 @@ def main():
                                  "vs_plain_step": round(pdt * 1e3 / ms, 4)}
             except Exception as e:
                 out["packed"] = {"error": repr(e)}
-        if world == 1 and not a.no_decode and a.layout == "spark":
+        if a.full and world == 1 and not a.no_decode and a.layout == "spark":
             try:
                 out["decode"] = decode_rate(model, dev)
             except Exception as e:  # the headline number must not depend on the secondary measurement
                 out["decode"] = {"error": repr(e)}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if world > 1:

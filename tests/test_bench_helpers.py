@@ -85,3 +85,37 @@ def test_lora_down_direct_predicate_mirrors_the_kernels_limits():
     assert sup(2, 2048, 1024, (32, 32, 32, 32))           # four one-tile branches: two per half
     assert sup(2, 2048, 1024, (32, 32, 32))               # three one-tile branches: 2 + 1
     assert not sup(2, 2048, 1024, (32,))                  # a single tile cannot be cut in two
+
+
+def test_dump_outputs_writes_the_same_float32_sample_every_time(tmp_path):
+    """bench.py --dump-outputs on a CPU model: the loss, and per parameter the whole tensor (small ones) or a fixed sample of
+    DUMP_PER_TENSOR elements (large ones) of its gradient, bf16 weight and fp32 master -- float32, the same positions in every
+    call, within the size bound."""
+    import types
+    import numpy as np
+    import torch
+    from rwkvtts_amd.trainer import FlatBuffers
+    b = _bench()
+    torch.manual_seed(0)
+    m = torch.nn.Sequential(torch.nn.Linear(100, 90), torch.nn.Linear(90, 7)).to(torch.bfloat16)
+    flat = FlatBuffers(m)
+    m(torch.randn(5, 100, dtype=torch.bfloat16)).float().square().sum().backward()
+    flat.finish_backward()
+    tr = types.SimpleNamespace(flat=flat, master=flat.flat_param.float() + 1e-3, shard_optimizer=False)
+    loss = torch.tensor(1.25)
+    names = b.dump_outputs(str(tmp_path / "a"), loss, tr)
+    assert names == ["grad_sample", "loss", "master_sample", "param_sample"]
+    b.dump_outputs(str(tmp_path / "b"), loss, tr)
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    for n in names:
+        assert got[n].dtype == np.float32
+        assert np.array_equal(got[n], np.load(tmp_path / "b" / (n + ".npy"))), n
+    assert got["loss"].tolist() == [1.25]
+    sizes = [min(p.numel(), b.DUMP_PER_TENSOR) for p in flat.params]
+    assert sizes == [b.DUMP_PER_TENSOR, 90, 630, 7] and all(len(got[n]) == sum(sizes) for n in names if n != "loss")
+    o = sizes[0]   # the bias of the first layer is taken whole, in order
+    assert np.array_equal(got["param_sample"][o:o + 90], m[0].bias.detach().float().numpy())
+    assert np.array_equal(got["grad_sample"][o:o + 90], m[0].bias.grad.float().numpy())
+    assert np.allclose(got["master_sample"][o:o + 90], m[0].bias.detach().float().numpy() + 1e-3)
+    w = m[0].weight.detach().float().numpy().ravel()   # the 9000-element weight: a sample of its own elements
+    assert np.isin(got["param_sample"][:o], w).all()
