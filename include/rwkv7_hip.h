@@ -350,6 +350,26 @@ int rwkv7_wkv_chunk_bwd_out_z_bf16(int B, int T, int H, const void *w, const voi
                                    const void *a, const void *b, const void *dy, const void *hs, const float *sa,
                                    const float *z, const void *e_vk, void *dw, void *dq, void *dk, void *dv,
                                    void *da, void *db, rwkv7_stream_t stream);
+/* ---- the two sequential chunked kernels with a carried state (bf16, plain rows, T % 32 == 0): training through a recurrent state.
+ *   fwd_state  : rwkv7_wkv_chunk_fwd_seq_bf16 (seq_chunk_off = NULL) starting from h0 instead of zero; hs of chunk 0 then holds h0;
+ *                hT receives the state after the last chunk (fp32, from the recurrence's own accumulators).
+ *   bseq_state : rwkv7_wkv_chunk_bseq_bf16 (seq_chunk_off = NULL) with dhT = dL/d(final state) as the adjoint after the last chunk
+ *                (it flows into e_vk[last] and on); dh0 receives dL/dh0.
+ *   h0, hT, dhT, dh0: fp32 [B,H,64,64], row = value, column = key (the layout of rwkv7_wkv_state_fwd_*'s state).  Each may be NULL
+ *   (a zero input / no output); with all of them NULL the results are bit-identical to the stateless entries.  y, hT, e_vk, z and
+ *   dh0 are correct for any row.
+ *   THE SIX GRADIENTS NEED A FRAMED ROW.  rwkv7_wkv_chunk_bwd_out_z_bf16 (the per-chunk gradients on top of these two) assumes that
+ *   every row starts from the zero state and has no future: a workgroup hands the end state of one chunk on as the start state of
+ *   the next and zeroes it across a row boundary, and the decay gradient of a row's last chunk drops its rowsum(E * H_C) term.  With
+ *   a non-zero h0 or dhT its dw, dq, dk, dv, da, db are therefore valid only if the row starts AND ends with one whole identity
+ *   chunk -- 32 steps with w = -1e4 (exp(w) underflows to 0: decay exactly 1) and q = k = v = a = b = 0 -- whose gradients the
+ *   caller drops (the identity chunks pass h0 and dhT through bit for bit).  rwkvtts_amd/ops.py, wkv7_state_chunked, does this. ---- */
+int rwkv7_wkv_chunk_fwd_state_bf16(int B, int T, int H, const void *w, const void *q, const void *k, const void *v,
+                                   const void *a, const void *b, const float *tinv, void *y, float *sa, void *hs,
+                                   const float *h0, float *hT, rwkv7_stream_t stream);
+int rwkv7_wkv_chunk_bseq_state_bf16(int B, int T, int H, const void *w, const void *q, const void *a, const void *b,
+                                    const void *dy, const float *tinv, void *e_vk, float *z,
+                                    const float *dhT, float *dh0, rwkv7_stream_t stream);
 /*      (The round-3/4 per-chunk gradient kernel, csrc/lab/wkv7_chunk_bwd9.hip, is an A/B twin with its own entry point in the lab build:
  *      include/rwkv7_hip_lab.h.  There are no process-wide switches in this library.) */
 /* ---- head loss: softmax cross-entropy of a chunk of bf16 logits [rows,V], forward and backward in one pass

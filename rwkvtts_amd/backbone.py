@@ -153,11 +153,22 @@ class LayerState:
 
 
 class Cache:
-    """Minimal stand-in for rwkvfla's Cache: a list of LayerState plus seen_tokens (llm.py:254)."""
+    """Minimal stand-in for rwkvfla's Cache: a list of LayerState plus seen_tokens (llm.py:254).
 
-    def __init__(self, states: Optional[List[LayerState]] = None, seen_tokens: int = 0):
+    differentiable: a forward with this cache under autograd trains THROUGH the carried state -- the scan runs on the chunked
+    kernels from the cached state (ops.wkv7_state_chunked), and the new states are rebound to tensors that carry their graph
+    (they are not written in place).  The same path is taken whenever a state tensor requires grad (a tuned initial state).
+    detach() is the truncated-BPTT cut between segments."""
+
+    def __init__(self, states: Optional[List[LayerState]] = None, seen_tokens: int = 0, differentiable: bool = False):
         self.states = states or []
         self.seen_tokens = seen_tokens
+        self.differentiable = bool(differentiable)
+
+    def detach(self):
+        """A new Cache with detached copies of the state tensors, the same seen_tokens and the same flag."""
+        return Cache([LayerState(s.att_x_prev.detach().clone(), s.att_kv.detach().clone(), s.ffn_x_prev.detach().clone())
+                      for s in self.states], self.seen_tokens, self.differentiable)
 
     def __len__(self):
         return len(self.states)
@@ -166,12 +177,12 @@ class Cache:
         return self.states[i]
 
     @classmethod
-    def zeros(cls, cfg: RWKV7Config, B, device, dtype):
+    def zeros(cls, cfg: RWKV7Config, B, device, dtype, differentiable: bool = False):
         H = cfg.num_heads
         return cls([LayerState(torch.zeros(B, cfg.hidden_size, device=device, dtype=dtype),
                                torch.zeros(B, H, HEAD_SIZE, HEAD_SIZE, device=device, dtype=torch.float32),
                                torch.zeros(B, cfg.hidden_size, device=device, dtype=dtype))
-                    for _ in range(cfg.num_hidden_layers)])
+                    for _ in range(cfg.num_hidden_layers)], differentiable=differentiable)
 
 
 def mark_all_ones(attention_mask: torch.Tensor, all_ones: bool):
@@ -261,11 +272,15 @@ class RWKV7Attention(nn.Module):
             self._mix_key = key
         return self._mix_cache
 
-    def forward(self, x, mask, v_first, state: Optional[LayerState] = None, seq_start=None, resid=None):
+    def forward(self, x, mask, v_first, state: Optional[LayerState] = None, seq_start=None, resid=None, diff_state=False):
         """x [B,T,D] (LayerNorm'ed), mask [B,T,1] or None.  Returns (out, v_first); resid: see forward_mixed.
-        With `state`, token shift and the WKV state are carried (and updated in place).
+        With `state`, token shift and the WKV state are carried (and updated in place; with diff_state the state's fields are
+        rebound to the new, differentiable tensors instead).
         seq_start (int32 [nseq+1] chunk offsets): packed rows, see RWKV7Model._forward_packed."""
         x_prev = None if state is None else state.att_x_prev
+        if diff_state:
+            mixed = fused.token_shift_mix6(x, x_prev, self.x_r, self.x_w, self.x_k, self.x_v, self.x_a, self.x_g, mask)
+            return self.forward_mixed(mixed, x, mask, v_first, state, diff_state=True)
         if FUSED_TMIX_CORE and fused.mix_lora_supported(x, state, seq_start, lambda: self.lora_branches()[1], mask):
             # training: the four low-rank branches' down projections taken THROUGH the lerp (fused.mix_lora): x_w, x_a, x_g and the
             # branch copy of x_v are never formed
@@ -286,7 +301,8 @@ class RWKV7Attention(nn.Module):
     def mix_params(self):
         return (self.x_r, self.x_w, self.x_k, self.x_v, self.x_a, self.x_g)
 
-    def forward_mixed(self, mixed, x, mask, v_first, state: Optional[LayerState] = None, seq_start=None, resid=None, hid=None):
+    def forward_mixed(self, mixed, x, mask, v_first, state: Optional[LayerState] = None, seq_start=None, resid=None, hid=None,
+                      diff_state=False):
         """The block after the token-shift lerps (`mixed` = xr, xw, xk, xv, xa, xg; with `hid` -- the low-rank branches' hidden
         pre-activations from fused.mix_lora -- only xr, xk, xv are given); x (the LayerNorm'ed input) is only read for
         the carried state and may be None without one.  resid (training one-pass path): the residual stream; if the output
@@ -351,6 +367,12 @@ class RWKV7Attention(nn.Module):
                 y = ops.RUN_CUDA_RWKV7g(r, w, k2, v2, a_in, b_in)
             else:
                 y = ops.wkv7_forward_nograd(r, w, k2, v2, a_in, b_in)
+        elif diff_state:
+            # training through the carried state: the scan and the new state are on the tape; the fields are REBOUND (the no-grad
+            # path's in-place updates would overwrite tensors the tape still needs)
+            y, state.att_kv = ops.wkv7_state_chunked(state.att_kv, r.contiguous(), w, k2, v2, a_in, b_in)
+            last = x[:, -1]
+            state.att_x_prev = last * mask[:, -1] if mask is not None else last
         else:
             y = ops.RWKV7_BATCH_OP(state.att_kv, r.contiguous(), w, k2, v2, a_in, b_in)
             last = x[:, -1].detach()
@@ -369,10 +391,13 @@ class RWKV7FeedForward(nn.Module):
         self.key = Linear(cfg.hidden_size, cfg.intermediate_size, bias=False)
         self.value = Linear(cfg.intermediate_size, cfg.hidden_size, bias=False)
 
-    def forward(self, x, mask, state: Optional[LayerState] = None):
+    def forward(self, x, mask, state: Optional[LayerState] = None, diff_state=False):
         x_prev = None if state is None else state.ffn_x_prev
         kx = fused.token_shift_mix1(x, x_prev, self.x_k, mask)
-        if state is not None:
+        if diff_state:   # rebound with its graph (see RWKV7Attention.forward_mixed)
+            last = x[:, -1]
+            state.ffn_x_prev = last * mask[:, -1] if mask is not None else last
+        elif state is not None:
             last = x[:, -1].detach()
             state.ffn_x_prev.copy_(last * mask[:, -1] if mask is not None else last)
         return self.forward_mixed(kx)
@@ -405,15 +430,24 @@ class RWKV7Block(nn.Module):
         self.ffn_norm = nn.LayerNorm(D, eps=cfg.norm_eps, bias=cfg.norm_bias)
         self.ffn = RWKV7FeedForward(cfg, layer_idx)
 
-    def forward(self, x, delta, mask, v_first, state: Optional[LayerState] = None, seq_start=None):
+    def forward(self, x, delta, mask, v_first, state: Optional[LayerState] = None, seq_start=None, diff_state=False):
         """The block input is x + delta (delta = the previous block's channel-mix output, None for the first
         block): every residual add is fused with the LayerNorm that follows it (fused.add_layer_norm), so this
-        block's own last add is left to the next block / the model's final norm.  Returns (x, delta, v_first)."""
+        block's own last add is left to the next block / the model's final norm.  Returns (x, delta, v_first).
+        diff_state: train through `state` (RWKV7Model.forward decides; the unfused stages, see RWKV7Attention.forward)."""
         if self.layer_idx == 0:
             if delta is not None:
                 x = x + delta
                 delta = None
             x = fused.layer_norm(x, self.pre_norm)
+        if diff_state:
+            if delta is None:
+                h = fused.layer_norm(x, self.attn_norm)
+            else:
+                x, h = fused.add_layer_norm(x, delta, self.attn_norm)
+            att, v_first = self.attn(h, mask, v_first, state, diff_state=True)
+            x, h = fused.add_layer_norm(x, att, self.ffn_norm)
+            return x, self.ffn(h, mask, state, diff_state=True), v_first
         one_pass = fused.add_ln_mix_supported(x, state)
         if one_pass and (FUSED_ADD_LN_MIX6 or FUSED_ADD_LN_MIX6_FWD):
             x, mixed = fused.add_layer_norm_mix(x, delta, self.attn_norm, mask, self.attn.mix_params(), fwd_only=not FUSED_ADD_LN_MIX6)
@@ -479,6 +513,8 @@ class RWKV7Model(nn.Module):
             raise ValueError("You must specify exactly one of input_ids or inputs_embeds")
         x = self.embeddings(input_ids) if inputs_embeds is None else inputs_embeds
         if cu_seqlens is not None:
+            if past_key_values is not None and len(past_key_values) > 0 and self._differentiable_state(past_key_values, x):
+                raise ValueError("cu_seqlens together with a differentiable cache: initial states per packed sequence are not supported")
             return self._forward_packed(x, cu_seqlens)
         B, T, D = x.shape
         if not x.is_cuda:
@@ -497,6 +533,7 @@ class RWKV7Model(nn.Module):
         if use_cache and past_key_values is None:
             past_key_values = Cache.zeros(self.config, B, x.device, x.dtype)
         stateful = past_key_values is not None and len(past_key_values) > 0
+        diff_state = stateful and self._differentiable_state(past_key_values, x)
         pad = 0
         # the training kernels need T % 16 == 0 (reference), the chunked MFMA pair that bf16 training runs T % 32 == 0: a bf16
         # batch is padded to 32 so that none falls back to the scalar kernels (2.7x slower scan)
@@ -507,7 +544,7 @@ class RWKV7Model(nn.Module):
             x = torch.cat([x.new_zeros(B, pad, D), x], 1)
             m = torch.ones(B, T, 1, dtype=x.dtype, device=x.device) if mask is None else mask
             mask = torch.cat([m.new_zeros(B, pad, 1), m], 1)
-        x = self._run_layers(x, mask, past_key_values if stateful else None)
+        x = self._run_layers(x, mask, past_key_values if stateful else None, diff_state=diff_state)
         if pad:
             x = x[:, pad:]
         if stateful:
@@ -515,13 +552,27 @@ class RWKV7Model(nn.Module):
         return ModelOutput(last_hidden_state=x, past_key_values=past_key_values if stateful else None)
 
 
-    def _run_layers(self, x, mask, cache: Optional[Cache], seq_start=None):
+    @staticmethod
+    def _differentiable_state(cache: Cache, x) -> bool:
+        """Whether a stateful forward trains through the cache: grad mode on, and the cache is marked differentiable or one of
+        its state tensors requires grad.  Everything else (prefill, decode, generate: all under no_grad / inference_mode) keeps
+        the in-place no-grad path."""
+        if not torch.is_grad_enabled() or not (getattr(cache, "differentiable", False) or
+                                               any(t.requires_grad for s in cache.states for t in (s.att_x_prev, s.att_kv, s.ffn_x_prev))):
+            return False
+        if x.dtype != torch.bfloat16:
+            raise ValueError(f"training through a differentiable cache needs a bf16 model (the chunked backward is bf16 only), got {x.dtype}")
+        return True
+
+    def _run_layers(self, x, mask, cache: Optional[Cache], seq_start=None, diff_state=False):
         v_first = delta = None
         for i, layer in enumerate(self.layers):
             st = cache[i] if cache is not None else None
             if self.gradient_checkpointing and self.training and cache is None:
                 x, delta, v_first = torch.utils.checkpoint.checkpoint(layer, x, delta, mask, v_first, None, seq_start,
                                                                       use_reentrant=False)
+            elif diff_state:
+                x, delta, v_first = layer(x, delta, mask, v_first, st, seq_start, diff_state=True)
             else:
                 x, delta, v_first = layer(x, delta, mask, v_first, st, seq_start)
         return fused.add_layer_norm(x, delta, self.norm)[1] if delta is not None else fused.layer_norm(x, self.norm)

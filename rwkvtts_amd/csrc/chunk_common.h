@@ -345,4 +345,26 @@ __device__ __forceinline__ f32x16 zero16() {
     return z;
 }
 
+// ---- carried states at the kernel boundary (the stateful variants of the two sequential kernels) -------------------------------
+// A state S of one head is fp32 [64 (value)][64 (key)] -- LayerState.att_kv's layout and the scalar state kernel's.  The chain waves
+// hold H = S^T (or its adjoint E) as D-layout tiles: register r of lane l = key 32 kt + d_row(r, l), value 32 vh + (l & 31).  The four
+// registers r = 4 j .. 4 j + 3 are four consecutive keys, so a lane moves its tile with four 16-byte accesses (register <-> global,
+// no LDS).
+__device__ __forceinline__ f32x16 state_tile_load(const float *S, int vh, int kt, int lane) {
+    const float *p = S + (vh * 32 + (lane & 31)) * kN + kt * 32 + 4 * (lane >> 5);
+    f32x16 t;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const float4 x = *reinterpret_cast<const float4 *>(p + 8 * j);
+        t[4 * j + 0] = x.x; t[4 * j + 1] = x.y; t[4 * j + 2] = x.z; t[4 * j + 3] = x.w;
+    }
+    return t;
+}
+__device__ __forceinline__ void state_tile_store(float *S, const f32x16 &t, int vh, int kt, int lane) {
+    float *p = S + (vh * 32 + (lane & 31)) * kN + kt * 32 + 4 * (lane >> 5);
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+        *reinterpret_cast<float4 *>(p + 8 * j) = make_float4(t[4 * j + 0], t[4 * j + 1], t[4 * j + 2], t[4 * j + 3]);
+}
+
 }  // namespace rwkv7

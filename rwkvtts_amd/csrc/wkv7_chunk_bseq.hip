@@ -75,11 +75,16 @@ static_assert(BSSmem::end16 % 8 == 0 && BSSmem::BUF % 8 == 0 && BSSmem::BBh % 8 
 static_assert(BSSmem::bytes <= 160 * 1024, "LDS budget");
 }  // namespace
 
+// STATE (the stateful variants, plain rows only): dhT_ (may be NULL = zero) is the adjoint of the state after the last chunk, dh0_ (may be
+// NULL) receives the adjoint of the state chunk c0 started from; both fp32 [B,H,64 (value),64 (key)], the layout of the forward's h0 / hT.
+// E is the adjoint of H = S^T, so E[k][v] = dS[v][k]: the same register <-> global mapping as the forward's state tile.
+template <bool STATE>
 __global__ __launch_bounds__(512) void wkv7c_bseq_kernel(int T_, int H, const bf16_t *__restrict__ w_, const bf16_t *__restrict__ q_,
                                                          const bf16_t *__restrict__ a_, const bf16_t *__restrict__ b_,
                                                          const bf16_t *__restrict__ dy_, const float *__restrict__ tinv_,
                                                          uint16_t *__restrict__ e_vk, float *__restrict__ z_,
-                                                         const int *__restrict__ seq_off_) {
+                                                         const int *__restrict__ seq_off_, const float *__restrict__ dhT_,
+                                                         float *__restrict__ dh0_) {
     extern __shared__ __attribute__((aligned(16))) uint16_t sm[];
     using L = BSSmem;
     float *sh_gC2 = reinterpret_cast<float *>(sm + L::end16) + L::fGC, *sh_Z = reinterpret_cast<float *>(sm + L::end16) + L::fZ;
@@ -130,6 +135,9 @@ __global__ __launch_bounds__(512) void wkv7c_bseq_kernel(int T_, int H, const bf
     if (role == 0) {
         // =================================================================================================== consumer
         f32x16 Emaster = zero16();  // waves 1, 2: D-layout tile (32 keys x 32 value columns) of E_{cc+1}, fp32, not yet decayed
+        // E after the last chunk = the final state's adjoint (zero without one).  It reaches the E planes as E' in interval b of the first
+        // iteration and e_vk[c1 - 1] as the first record: the zero fill of the planes above is overwritten before it is read either way.
+        if (STATE && dhT_ && (wave == 1 || wave == 2)) Emaster = state_tile_load(dhT_ + (long)bh * kN * kN, vh, wave - 1, lane);
         lds_barrier();
         lds_barrier();
         lds_barrier();
@@ -207,6 +215,7 @@ __global__ __launch_bounds__(512) void wkv7c_bseq_kernel(int T_, int H, const bf
             lds_barrier();
             BSSTAMP(3);
         }
+        if (STATE && dh0_ && (wave == 1 || wave == 2)) state_tile_store(dh0_ + (long)bh * kN * kN, Emaster, vh, wave - 1, lane);   // E_{c0}
         if (z_) {   // Z of the last chunk processed (c0)
             const long o = head_base + (long)(c0 * kC + pt) * tstride + vh * VH + pv;
             *reinterpret_cast<float4 *>(z_ + o) = *reinterpret_cast<const float4 *>(&sh_Z[pt * kStageLD + pv]);
@@ -335,14 +344,27 @@ __global__ __launch_bounds__(512) void wkv7c_bseq_kernel(int T_, int H, const bf
 #endif
 }
 
+template <bool STATE>
+static int launch_bseq(int B, int T_, int H, const void *w, const void *q, const void *a, const void *b, const void *dy, const float *tinv,
+                       void *e_vk, float *z, const int *seq_off, int nseq, const float *dhT, float *dh0, hipStream_t st) {
+    static DynLdsOnce lds_once;
+    if (hipError_t e = lds_once.ensure(reinterpret_cast<const void *>(&wkv7c_bseq_kernel<STATE>), (int)BSSmem::bytes); e != hipSuccess) return (int)e;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(wkv7c_bseq_kernel<STATE>, dim3((seq_off ? nseq : B) * H * 2), dim3(512), BSSmem::bytes, st, T_, H, (const bf16_t *)w,
+                       (const bf16_t *)q, (const bf16_t *)a, (const bf16_t *)b, (const bf16_t *)dy, tinv, (uint16_t *)e_vk, z, seq_off, dhT, dh0);
+    return (int)hipGetLastError();
+}
+
 int chunk_bseq_bf16(int B, int T_, int H, const void *w, const void *q, const void *a, const void *b, const void *dy, const float *tinv,
                     void *e_vk, float *z, const int *seq_off, int nseq, hipStream_t st) {
-    static DynLdsOnce lds_once;
-    if (hipError_t e = lds_once.ensure(reinterpret_cast<const void *>(&wkv7c_bseq_kernel), (int)BSSmem::bytes); e != hipSuccess) return (int)e;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(wkv7c_bseq_kernel, dim3((seq_off ? nseq : B) * H * 2), dim3(512), BSSmem::bytes, st, T_, H, (const bf16_t *)w,
-                       (const bf16_t *)q, (const bf16_t *)a, (const bf16_t *)b, (const bf16_t *)dy, tinv, (uint16_t *)e_vk, z, seq_off);
-    return (int)hipGetLastError();
+    return launch_bseq<false>(B, T_, H, w, q, a, b, dy, tinv, e_vk, z, seq_off, nseq, nullptr, nullptr, st);
+}
+
+// plain rows with a carried state (dhT / dh0 may each be NULL; both NULL: the stateless kernel above, bit for bit)
+int chunk_bseq_state_bf16(int B, int T_, int H, const void *w, const void *q, const void *a, const void *b, const void *dy,
+                          const float *tinv, void *e_vk, float *z, const float *dhT, float *dh0, hipStream_t st) {
+    if (!dhT && !dh0) return chunk_bseq_bf16(B, T_, H, w, q, a, b, dy, tinv, e_vk, z, nullptr, 0, st);
+    return launch_bseq<true>(B, T_, H, w, q, a, b, dy, tinv, e_vk, z, nullptr, 0, dhT, dh0, st);
 }
 
 }  // namespace rwkv7

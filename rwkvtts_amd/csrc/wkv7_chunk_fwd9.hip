@@ -79,13 +79,16 @@ static_assert(F9Smem::end16 % 8 == 0 && F9Smem::BUF % 8 == 0 && F9Smem::Wh % 8 =
 static_assert(F9Smem::bytes <= 160 * 1024, "LDS budget");
 }  // namespace
 
-template <bool SAVE>
+// STATE (the stateful variants): h0_ (may be NULL = zero) is the state chunk c0 starts from, hT_ (may be NULL) receives the state after
+// the last chunk; both fp32 [B,H,64 (value),64 (key)], plain rows only (seq_off_ == NULL).  The stateless instantiations never touch them.
+template <bool SAVE, bool STATE>
 __global__ __launch_bounds__(512) void wkv7c_fwd9_kernel(int T_, int H, const bf16_t *__restrict__ w_, const bf16_t *__restrict__ q_,
                                                          const bf16_t *__restrict__ k_, const bf16_t *__restrict__ v_,
                                                          const bf16_t *__restrict__ a_, const bf16_t *__restrict__ b_,
                                                          const float *__restrict__ tinv_, bf16_t *__restrict__ y_,
                                                          float *__restrict__ sa_, uint16_t *__restrict__ hs_,
-                                                         const int *__restrict__ seq_off_) {
+                                                         const int *__restrict__ seq_off_, const float *__restrict__ h0_,
+                                                         float *__restrict__ hT_) {
     extern __shared__ __attribute__((aligned(16))) uint16_t sm[];
     using L = F9Smem;
     float *fm = reinterpret_cast<float *>(sm + L::end16);
@@ -130,7 +133,9 @@ __global__ __launch_bounds__(512) void wkv7c_fwd9_kernel(int T_, int H, const bf
     const int pt = ltid & 31, pk = (ltid >> 5) * 8, pv = (ltid >> 5) * 4;
     const int lt = ltid >> 3, lk = (ltid & 7) * 8, lv = (ltid & 7) * 4;
 
-    for (int i = tid; i < 2 * VH * LDK; i += 512) sm[L::Sh + i] = 0;  // chunk c0 starts from S = 0
+    const bool from_h0 = STATE && h0_ != nullptr;
+    if (!from_h0)
+        for (int i = tid; i < 2 * VH * LDK; i += 512) sm[L::Sh + i] = 0;  // chunk c0 starts from S = 0
     using RawVec = decltype(Raw4<bf16_t>::r);
 #ifdef WKV7C_TIMING
     long long tacc_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -142,6 +147,11 @@ __global__ __launch_bounds__(512) void wkv7c_fwd9_kernel(int T_, int H, const bf
     if (role == 0) {
         // =================================================================================================== consumer
         f32x16 Smaster = zero16();  // waves 1, 2: D-layout tile (32 keys x 32 value columns) of the fp32 state
+        if (from_h0 && (wave == 1 || wave == 2)) {
+            // the initial state straight into the chain waves' fp32 tile and the state planes (read first in interval a, two barriers on)
+            Smaster = state_tile_load(h0_ + (long)bh * kN * kN, vh, wave - 1, lane);
+            store_T_split(Smaster, sm + L::Sh + (wave - 1) * 32, sm + L::Sl + (wave - 1) * 32, LDK, lane);
+        }
         // y (and sa) of a chunk, staged in its interval b, leave at the start of the next interval a: thread (pt, pv) owns 4 value
         // columns of one step.  On the consumer side: the producer's vector-memory queue holds its prefetches, and a store in front
         // of them makes every wait for a prefetched row a wait for the store as well (one in-order counter for loads and stores)
@@ -151,7 +161,7 @@ __global__ __launch_bounds__(512) void wkv7c_fwd9_kernel(int T_, int H, const bf
             *reinterpret_cast<uint2 *>(reinterpret_cast<uint16_t *>(y_) + o) = make_uint2(cvt_pk(yv.x, yv.y), cvt_pk(yv.z, yv.w));
             if (SAVE) *reinterpret_cast<float4 *>(sa_ + o) = *reinterpret_cast<const float4 *>(&sh_U[pt * kStageLD + pv]);
         };
-        if (SAVE && (wave == 1 || wave == 2)) q15_encode_tile(Smaster, hs_ + ((long)bh * nc + c0) * kQRec, vh, wave - 1, lane);   // S = 0
+        if (SAVE && (wave == 1 || wave == 2)) q15_encode_tile(Smaster, hs_ + ((long)bh * nc + c0) * kQRec, vh, wave - 1, lane);   // S = 0 (h0)
         lds_barrier();
         lds_barrier();
         for (int it = c0 - 1; it < c1; it++) {
@@ -243,6 +253,7 @@ __global__ __launch_bounds__(512) void wkv7c_fwd9_kernel(int T_, int H, const bf
             F9STAMP(6);
         }
         store_out(c1 - 1);
+        if (STATE && hT_ && (wave == 1 || wave == 2)) state_tile_store(hT_ + (long)bh * kN * kN, Smaster, vh, wave - 1, lane);
     } else {
         // =================================================================================================== producer
 #if WKV7C_F9_PRODUCER_PRIO
@@ -387,26 +398,36 @@ __global__ __launch_bounds__(512) void wkv7c_fwd9_kernel(int T_, int H, const bf
 #endif
 }
 
+template <bool STATE>
 static int launch_fwd9(bool save, int B, int T_, int H, const void *w, const void *q, const void *k, const void *v, const void *a,
-                       const void *b, const float *tinv, void *y, float *sa, void *hs, const int *seq_off, int nseq, hipStream_t st) {
+                       const void *b, const float *tinv, void *y, float *sa, void *hs, const int *seq_off, int nseq, const float *h0,
+                       float *hT, hipStream_t st) {
     static DynLdsOnce lds_once, lds_once2;
-    if (hipError_t e = lds_once.ensure(reinterpret_cast<const void *>(&wkv7c_fwd9_kernel<true>), (int)F9Smem::bytes); e != hipSuccess) return (int)e;
-    if (hipError_t e = lds_once2.ensure(reinterpret_cast<const void *>(&wkv7c_fwd9_kernel<false>), (int)F9Smem::bytes); e != hipSuccess) return (int)e;
+    if (hipError_t e = lds_once.ensure(reinterpret_cast<const void *>(&wkv7c_fwd9_kernel<true, STATE>), (int)F9Smem::bytes); e != hipSuccess) return (int)e;
+    if (hipError_t e = lds_once2.ensure(reinterpret_cast<const void *>(&wkv7c_fwd9_kernel<false, STATE>), (int)F9Smem::bytes); e != hipSuccess) return (int)e;
     (void)hipGetLastError();
     const dim3 grid((seq_off ? nseq : B) * H * 2), block(512);
     if (save)
-        hipLaunchKernelGGL(wkv7c_fwd9_kernel<true>, grid, block, F9Smem::bytes, st, T_, H, (const bf16_t *)w, (const bf16_t *)q,
-                           (const bf16_t *)k, (const bf16_t *)v, (const bf16_t *)a, (const bf16_t *)b, tinv, (bf16_t *)y, sa, (uint16_t *)hs, seq_off);
+        hipLaunchKernelGGL((wkv7c_fwd9_kernel<true, STATE>), grid, block, F9Smem::bytes, st, T_, H, (const bf16_t *)w, (const bf16_t *)q,
+                           (const bf16_t *)k, (const bf16_t *)v, (const bf16_t *)a, (const bf16_t *)b, tinv, (bf16_t *)y, sa, (uint16_t *)hs, seq_off,
+                           h0, hT);
     else
-        hipLaunchKernelGGL(wkv7c_fwd9_kernel<false>, grid, block, F9Smem::bytes, st, T_, H, (const bf16_t *)w, (const bf16_t *)q,
+        hipLaunchKernelGGL((wkv7c_fwd9_kernel<false, STATE>), grid, block, F9Smem::bytes, st, T_, H, (const bf16_t *)w, (const bf16_t *)q,
                            (const bf16_t *)k, (const bf16_t *)v, (const bf16_t *)a, (const bf16_t *)b, tinv, (bf16_t *)y, nullptr, nullptr,
-                           seq_off);
+                           seq_off, h0, hT);
     return (int)hipGetLastError();
 }
 
 int chunk_fwd9_bf16(int B, int T_, int H, const void *w, const void *q, const void *k, const void *v, const void *a, const void *b,
                     const float *tinv, void *y, float *sa, void *hs, const int *seq_off, int nseq, hipStream_t st) {
-    return launch_fwd9(sa && hs, B, T_, H, w, q, k, v, a, b, tinv, y, sa, hs, seq_off, nseq, st);
+    return launch_fwd9<false>(sa && hs, B, T_, H, w, q, k, v, a, b, tinv, y, sa, hs, seq_off, nseq, nullptr, nullptr, st);
+}
+
+// plain rows with a carried state (h0 / hT may each be NULL; both NULL: the stateless kernel above, bit for bit)
+int chunk_fwd9_state_bf16(int B, int T_, int H, const void *w, const void *q, const void *k, const void *v, const void *a, const void *b,
+                          const float *tinv, void *y, float *sa, void *hs, const float *h0, float *hT, hipStream_t st) {
+    if (!h0 && !hT) return chunk_fwd9_bf16(B, T_, H, w, q, k, v, a, b, tinv, y, sa, hs, nullptr, 0, st);
+    return launch_fwd9<true>(sa && hs, B, T_, H, w, q, k, v, a, b, tinv, y, sa, hs, nullptr, 0, h0, hT, st);
 }
 
 }  // namespace rwkv7

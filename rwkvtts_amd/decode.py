@@ -38,6 +38,9 @@ class DecodeStep:
     are updated in place.  Raises ValueError for shapes/dtypes the kernel does not cover (see `supported`)."""
 
     def __init__(self, backbone, lm_head, cache: Cache, persistent: int = 0, host_table: bool = True):
+        if getattr(cache, "differentiable", False):
+            raise ValueError("DecodeStep updates the cache in place and keeps no tape: pass cache.detach() with "
+                             "differentiable=False, not a differentiable cache")
         why = self.supported(backbone, lm_head, cache)
         if why:
             raise ValueError("rwkv7_decode_step_bf16: " + why)

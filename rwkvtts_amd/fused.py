@@ -86,6 +86,7 @@ class _Mix(torch.autograd.Function):
         xp = None if x_prev is None else _c(x_prev.to(x.dtype))
         _call("mix_fwd", x, B, T, D, nmix, _p(x), _p(xp), _p(mask), _p(params), _p(out), min(B * T, _MIX_FWD_BLOCKS))
         ctx.save_for_backward(x, xp, mask, params)
+        ctx.xp_dtype = None if x_prev is None else x_prev.dtype
         return tuple(out[i] for i in range(nmix))
 
     @staticmethod
@@ -100,7 +101,11 @@ class _Mix(torch.autograd.Function):
         part = torch.empty(nb, nmix, D, dtype=torch.float32, device=x.device)
         ptrs = (ctypes.c_void_p * nmix)(*[g.data_ptr() for g in gs])
         _call("mix_bwd", x, B, T, D, nmix, ptrs, _p(x), _p(xp), _p(mask), _p(params), _p(dx), _p(part), nb, _MIX_BWD_ROWS)
-        return dx, None, None, _colsum(part, params.dtype)
+        dxp = None
+        if ctx.needs_input_grad[1]:
+            # mix_fwd takes the carried row x_prev UNMASKED as the step before t = 0: d out_i[:, 0] / d x_prev = params[i]
+            dxp = (params.float().unsqueeze(1) * torch.stack([g[:, 0, :] for g in gs]).float()).sum(0).to(ctx.xp_dtype)
+        return dx, dxp, None, _colsum(part, params.dtype)
 
 
 # Round 4: the low-rank branches' DOWN projections commute with the token-shift lerp,

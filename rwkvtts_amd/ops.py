@@ -385,3 +385,112 @@ def debug_mma32(X, Y):
     rc = _lib.lib().rwkv7_debug_mma32(_p(X.contiguous()), _p(Y.contiguous()), _p(D), _p(DT), _stream(X))
     _lib.check(rc, "debug_mma32")
     return D, DT
+
+
+# ------------------------------------------------------------------------------------------------
+# chunked WKV7 through a carried state: training across segments / tuning an initial state
+# ------------------------------------------------------------------------------------------------
+# Identity steps: w = W_PAD makes exp(w) underflow to 0 in the kernels' fast_exp (v_exp_f32 of -1.4e4), so the step's decay
+# exp(-exp(w)) is exactly 1, its log -exp(w) exactly 0; with q = k = v = a = b = 0 the step adds nothing, reads nothing and
+# outputs y = 0: S' = S bit for bit.  Every use of w in the chunked kernels goes through -fast_exp(w) (decay logs, their prefix
+# sums, g = exp(prefix), 1/g = exp(-prefix), g_{t-1} = exp(prefix - log)) and the decay gradient dw = dlog * log: no 0 * inf.
+W_PAD = -1.0e4
+
+
+def _pad_rows(x, front, tail, fill):
+    """[B,T,C] -> contiguous [B, front + T + tail, C] with `fill` in the added rows (x itself when nothing is added)."""
+    if front == 0 and tail == 0:
+        return x.contiguous()
+    B, T, C = x.shape
+    out = x.new_full((B, front + T + tail, C), fill)
+    out[:, front:front + T] = x
+    return out
+
+
+class _WkvStateChunked(torch.autograd.Function):
+    """y, hT = scan(h0; r, w, k, v, a, b) on the chunked kernels, differentiable in all seven inputs (see wkv7_state_chunked)."""
+
+    @staticmethod
+    def forward(ctx, h0, r, w, k, v, a, b):
+        B, T, HC = r.shape
+        H = HC // HEAD_SIZE
+        train = any(ctx.needs_input_grad)
+        # T % 32 != 0: identity steps in FRONT (the state reaches the first real step unchanged).  Training frames the row with one
+        # whole identity chunk at EACH end: the per-chunk gradient kernel (csrc/wkv7_chunk_bwd10.hip, unchanged) treats a row as
+        # starting from the zero state and ending with no future -- a workgroup hands the end state of one chunk on as the start
+        # state of the next and zeroes it across a row boundary, and the last chunk's rowsum(E * H_C) decay term is dropped.  With
+        # the pad chunks every real chunk is an inner one: its start state is the checkpoint of the state after the leading pad
+        # (= h0) and its future the adjoint behind the trailing pad (= dhT), both passed through the identity chunks bit for bit.
+        front = (-T) % CHUNK_T + (CHUNK_T if train else 0)
+        tail = CHUNK_T if train else 0
+        Tp = front + T + tail
+        pw = _pad_rows(w, front, tail, W_PAD)
+        pq, pk, pv, pa, pb = [_pad_rows(x, front, tail, 0.0) for x in (r, k, v, a, b)]
+        w4, q4, k4, v4, a4, b4 = [x.view(B, Tp, H, HEAD_SIZE) for x in (pw, pq, pk, pv, pa, pb)]
+        h0c = h0.contiguous()
+        tinv = wkv7_chunk_prep(w4, a4, b4)
+        y = torch.empty_like(v4)
+        sa = torch.empty(B, Tp, H, HEAD_SIZE, dtype=torch.float32, device=r.device) if train else None
+        hs = torch.empty(B, H, Tp // CHUNK_T, Q15_REC, dtype=torch.int16, device=r.device) if train else None
+        hT = torch.empty(B, H, HEAD_SIZE, HEAD_SIZE, dtype=torch.float32, device=r.device)
+        with torch.cuda.device_of(r), _timed("wkv7c_fwd_state", r):
+            rc = _lib.lib().rwkv7_wkv_chunk_fwd_state_bf16(B, Tp, H, _p(w4), _p(q4), _p(k4), _p(v4), _p(a4), _p(b4), _p(tinv), _p(y),
+                                                           _p(sa), _p(hs), _p(h0c), _p(hT), _stream(r))
+        _lib.check(rc, "wkv7_state_chunked")
+        if train:
+            ctx.save_for_backward(w4, q4, k4, v4, a4, b4, tinv, sa, hs)
+            ctx.front, ctx.tail = front, tail
+        ctx.set_materialize_grads(False)
+        y = y.view(B, Tp, HC)
+        return (y if Tp == T else y[:, front:front + T].contiguous()), hT
+
+    @staticmethod
+    def backward(ctx, dy, dhT):
+        w4, q4, k4, v4, a4, b4, tinv, sa, hs = ctx.saved_tensors
+        B, Tp, H, C = w4.shape
+        front, tail = ctx.front, ctx.tail
+        T = Tp - front - tail
+        if dy is None:
+            dy4 = torch.zeros_like(v4)
+        else:
+            dy4 = _pad_rows(dy.to(w4.dtype), front, tail, 0.0).view(B, Tp, H, C)
+        dhT = None if dhT is None else dhT.to(torch.float32).contiguous()
+        dh0 = torch.empty(B, H, C, C, dtype=torch.float32, device=w4.device) if ctx.needs_input_grad[0] else None
+        e_vk = torch.empty(B, H, Tp // CHUNK_T, Q15_REC, dtype=torch.int16, device=w4.device)
+        z = torch.empty(B, Tp, H, C, dtype=torch.float32, device=w4.device)
+        with torch.cuda.device_of(w4), _timed("wkv7c_bseq_state", w4):
+            rc = _lib.lib().rwkv7_wkv_chunk_bseq_state_bf16(B, Tp, H, _p(w4), _p(q4), _p(a4), _p(b4), _p(dy4), _p(tinv), _p(e_vk),
+                                                            _p(z), _p(dhT), _p(dh0), _stream(w4))
+        _lib.check(rc, "wkv7_state_chunked backward (bseq)")
+        grads = [torch.empty_like(w4) for _ in range(6)]   # dw dq dk dv da db
+        with torch.cuda.device_of(w4), _timed("wkv7c_bwd_out", w4):
+            rc = _lib.lib().rwkv7_wkv_chunk_bwd_out_z_bf16(B, Tp, H, _p(w4), _p(q4), _p(k4), _p(v4), _p(a4), _p(b4), _p(dy4), _p(hs),
+                                                           _p(sa), _p(z), _p(e_vk), *[_p(g) for g in grads], _stream(w4))
+        _lib.check(rc, "wkv7_state_chunked backward (bwd_out)")
+        dw, dq, dk, dv, da, db = [g.view(B, Tp, H * C) for g in grads]
+        if Tp != T:
+            dw, dq, dk, dv, da, db = [g[:, front:front + T].contiguous() for g in (dw, dq, dk, dv, da, db)]
+        return dh0, dq, dw, dk, dv, da, db
+
+
+def wkv7_state_chunked(h0, r, w, k, v, a, b):
+    """The WKV7 scan from a carried state on the chunked (MFMA) kernels, differentiable in all seven inputs: what a stateful
+    training forward (truncated BPTT over segments, initial-state tuning) needs.  RWKV7_BATCH_OP computes the same forward
+    without a tape (scalar kernel, state updated in place).
+      h0: fp32 [B,H,64,64] (row = value, column = key: LayerState.att_kv's layout)
+      r, w, k, v, a, b: bf16 [B,T,H*64] as RWKV7_BATCH_OP takes them (w: the pre-activation, decay = exp(-exp(w))); any T >= 1
+    Returns (y bf16 [B,T,H*64], hT fp32 [B,H,64,64]); h0 is not modified.  bf16 only (the chunked backward is)."""
+    B, T, HC = r.shape
+    for t in (w, k, v, a, b):
+        if t.shape != r.shape:
+            raise ValueError(f"wkv7_state_chunked: r..b must share one shape [B,T,H*64], got {tuple(r.shape)} / {tuple(t.shape)}")
+    if HC % HEAD_SIZE != 0 or T < 1:
+        raise ValueError(f"wkv7_state_chunked: need T >= 1 and H*64 channels, got {tuple(r.shape)}")
+    if any(t.dtype != torch.bfloat16 for t in (r, w, k, v, a, b)):
+        raise TypeError("wkv7_state_chunked: r..b must be bfloat16 (the chunked backward is bf16 only)")
+    if not all(t.is_cuda for t in (h0, r, w, k, v, a, b)):
+        raise NotImplementedError("wkv7_state_chunked: HIP device tensors only (no CPU path)")
+    if h0.dtype != torch.float32 or tuple(h0.shape) != (B, HC // HEAD_SIZE, HEAD_SIZE, HEAD_SIZE):
+        raise TypeError(f"wkv7_state_chunked: h0 must be float32 [B,H,64,64] = {(B, HC // HEAD_SIZE, 64, 64)}, got "
+                        f"{h0.dtype} {tuple(h0.shape)}")
+    return _WkvStateChunked.apply(h0, r, w, k, v, a, b)
