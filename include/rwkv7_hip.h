@@ -370,6 +370,27 @@ int rwkv7_wkv_chunk_fwd_state_bf16(int B, int T, int H, const void *w, const voi
 int rwkv7_wkv_chunk_bseq_state_bf16(int B, int T, int H, const void *w, const void *q, const void *a, const void *b,
                                     const void *dy, const float *tinv, void *e_vk, float *z,
                                     const float *dhT, float *dh0, rwkv7_stream_t stream);
+/* ---- the same two kernels on packed rows (seq_chunk_off / nseq as rwkv7_wkv_chunk_fwd_seq_bf16; NULL / 0: plain rows, as above):
+ *   one carried state per SEQUENCE.  h0, hT, dhT, dh0: fp32 [nseq,H,64,64] (entry s * H + h: sequence s, head h), each may be NULL;
+ *   with all of them NULL the results are bit-identical to rwkv7_wkv_chunk_fwd_seq_bf16 / rwkv7_wkv_chunk_bseq_bf16 with the same
+ *   seq_chunk_off.  A sequence with an empty chunk range writes hT = h0 and dh0 = dhT (zeros for a NULL input).  y, hT, e_vk, z and
+ *   dh0 are correct for any packed row; seq_chunk_off must cover every chunk the per-chunk gradients read (as for the stateless op).
+ *   FRAMING FOR THE SIX GRADIENTS ON A PACKED ROW (B = 1).  rwkv7_wkv_chunk_bwd_out_z_bf16 reads the end state H_C of chunk c from
+ *   hs[c + 1], the next chunk's start record: for a sequence's last chunk that is the NEXT sequence's h0 (or zero at the row's end),
+ *   and with a non-zero dhT its decay term rowsum(E * H_C) is then wrong.  Each sequence therefore needs ONE TRAILING identity chunk
+ *   (32 steps with w = -1e4 and q = k = v = a = b = 0, inside its chunk range, gradients dropped) whenever dhT is non-zero.  Inside
+ *   the row no sequence needs a leading one: the start state of a sequence's first chunk is hs[c0] = h0 whether the gradient
+ *   workgroup loads it directly or takes it as the H_C of the chunk before (hs[c0] again).  But the ROW needs one leading identity
+ *   chunk when its first sequence has a non-zero h0: that kernel's workgroups walk the [H][T/32] chunk space across head
+ *   boundaries and hand a zero state into each head's first chunk (measured: without it dq of the row's first sequence was wrong on
+ *   every head but head 0).  tests/test_varlen_state_gpu.py checks the six gradients and dh0 against fp64 autograd and bit for bit
+ *   against the framed plain op.  rwkvtts_amd/ops.py, packed_state_layout / wkv7_state_chunked_varlen, lay rows out this way. ---- */
+int rwkv7_wkv_chunk_fwd_state_seq_bf16(int B, int T, int H, const void *w, const void *q, const void *k, const void *v,
+                                       const void *a, const void *b, const float *tinv, void *y, float *sa, void *hs,
+                                       const int *seq_chunk_off, int nseq, const float *h0, float *hT, rwkv7_stream_t stream);
+int rwkv7_wkv_chunk_bseq_state_seq_bf16(int B, int T, int H, const void *w, const void *q, const void *a, const void *b,
+                                        const void *dy, const float *tinv, void *e_vk, float *z, const int *seq_chunk_off, int nseq,
+                                        const float *dhT, float *dh0, rwkv7_stream_t stream);
 /*      (The round-3/4 per-chunk gradient kernel, csrc/lab/wkv7_chunk_bwd9.hip, is an A/B twin with its own entry point in the lab build:
  *      include/rwkv7_hip_lab.h.  There are no process-wide switches in this library.) */
 /* ---- head loss: softmax cross-entropy of a chunk of bf16 logits [rows,V], forward and backward in one pass

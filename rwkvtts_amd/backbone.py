@@ -224,6 +224,62 @@ def _row_align(n):
 PACKED_NATIVE = True
 
 
+class _PackedState:
+    """What the layers of RWKV7Model._forward_packed_state share: the aligned row's sequence chunks, the rows of each non-empty
+    sequence's first and last token, and the masked rows (identity steps of the scan)."""
+
+    def __init__(self, lay, keep, device):
+        ne = [i for i, f in enumerate(lay.first.tolist()) if f >= 0]
+        self.nseq = lay.seq_off.numel() - 1
+        self.seq_off = lay.seq_off.to(device, non_blocking=True)
+        self.keep = keep                                                   # bool [1, T_al, 1]: rows that hold a token
+        self.ne = torch.tensor(ne, dtype=torch.long).to(device, non_blocking=True)          # non-empty sequences
+        self.first = lay.first[ne].long().to(device, non_blocking=True)
+        self.last = lay.last[ne].long().to(device, non_blocking=True)
+        self.any = len(ne) > 0
+
+    def carry(self, mixed, x, x_prev, params):
+        """The token-shift lerps saw 0 before each sequence's first token (a masked row): recompute those rows with the carried
+        predecessor, x + (x_prev - x) * mu as the lerp kernel does (fp32, one rounding).  Autograd then returns dx_prev[s] =
+        sum_i mu_i * g_i[first_s]; without a tape the rows are written in place."""
+        if not self.any:
+            return mixed
+        xf = x[0].index_select(0, self.first).float()
+        d = x_prev.index_select(0, self.ne).float() - xf
+        out = []
+        for m, p in zip(mixed, params):
+            rows = torch.addcmul(xf, d, p.reshape(1, -1).float()).to(m.dtype).unsqueeze(0)
+            if torch.is_grad_enabled() and (m.requires_grad or rows.requires_grad):
+                out.append(m.index_copy(1, self.first, rows))
+            else:
+                out.append(m.index_copy_(1, self.first, rows))
+        return out
+
+    def identity_w(self, w):
+        """w (the scan's decay pre-activation) with W_PAD at every masked row: a select, not a multiply."""
+        if torch.is_grad_enabled() and w.requires_grad:
+            return torch.where(self.keep, w, ops.W_PAD)
+        return w.masked_fill_(~self.keep, ops.W_PAD)
+
+    @staticmethod
+    def store(state, name, new, diff):
+        if diff:
+            setattr(state, name, new)
+        else:
+            getattr(state, name).copy_(new.detach())   # in place: the addresses stay (captured decode graphs, DecodeStep)
+
+    def store_last(self, state, name, x, diff):
+        """The token-shift predecessor after each non-empty sequence: x at its last row (empty sequences keep theirs)."""
+        if not self.any:
+            return
+        old = getattr(state, name)
+        rows = x[0].index_select(0, self.last).to(old.dtype)
+        if diff:
+            setattr(state, name, old.index_copy(0, self.ne, rows))
+        else:
+            old.index_copy_(0, self.ne, rows.detach())
+
+
 class RWKV7Attention(nn.Module):
     """Time-mix block (rwkv_s2s_single_ffn.py:158-196; Appendix A of SURVEY.md)."""
 
@@ -272,12 +328,18 @@ class RWKV7Attention(nn.Module):
             self._mix_key = key
         return self._mix_cache
 
-    def forward(self, x, mask, v_first, state: Optional[LayerState] = None, seq_start=None, resid=None, diff_state=False):
+    def forward(self, x, mask, v_first, state: Optional[LayerState] = None, seq_start=None, resid=None, diff_state=False,
+                packed: Optional["_PackedState"] = None):
         """x [B,T,D] (LayerNorm'ed), mask [B,T,1] or None.  Returns (out, v_first); resid: see forward_mixed.
         With `state`, token shift and the WKV state are carried (and updated in place; with diff_state the state's fields are
         rebound to the new, differentiable tensors instead).
-        seq_start (int32 [nseq+1] chunk offsets): packed rows, see RWKV7Model._forward_packed."""
+        seq_start (int32 [nseq+1] chunk offsets): packed rows, see RWKV7Model._forward_packed.
+        packed: a packed row with one carried state per sequence (RWKV7Model._forward_packed_state; `state` holds N rows)."""
         x_prev = None if state is None else state.att_x_prev
+        if packed is not None:
+            mixed = fused.token_shift_mix6(x, None, self.x_r, self.x_w, self.x_k, self.x_v, self.x_a, self.x_g, mask)
+            mixed = packed.carry(mixed, x, state.att_x_prev, self.mix_params())
+            return self.forward_mixed(mixed, x, mask, v_first, state, diff_state=diff_state, packed=packed)
         if diff_state:
             mixed = fused.token_shift_mix6(x, x_prev, self.x_r, self.x_w, self.x_k, self.x_v, self.x_a, self.x_g, mask)
             return self.forward_mixed(mixed, x, mask, v_first, state, diff_state=True)
@@ -302,7 +364,7 @@ class RWKV7Attention(nn.Module):
         return (self.x_r, self.x_w, self.x_k, self.x_v, self.x_a, self.x_g)
 
     def forward_mixed(self, mixed, x, mask, v_first, state: Optional[LayerState] = None, seq_start=None, resid=None, hid=None,
-                      diff_state=False):
+                      diff_state=False, packed: Optional["_PackedState"] = None):
         """The block after the token-shift lerps (`mixed` = xr, xw, xk, xv, xa, xg; with `hid` -- the low-rank branches' hidden
         pre-activations from fused.mix_lora -- only xr, xk, xv are given); x (the LayerNorm'ed input) is only read for
         the carried state and may be None without one.  resid (training one-pass path): the residual stream; if the output
@@ -367,6 +429,13 @@ class RWKV7Attention(nn.Module):
                 y = ops.RUN_CUDA_RWKV7g(r, w, k2, v2, a_in, b_in)
             else:
                 y = ops.wkv7_forward_nograd(r, w, k2, v2, a_in, b_in)
+        elif packed is not None:
+            # packed row, one state per sequence: masked rows become exact identity steps of the scan (k, v, a, b, r are already 0
+            # there; w = 0 would decay the state by e^-1 per row)
+            w = packed.identity_w(w)
+            y, hT = ops.wkv7_state_chunked_seq(state.att_kv, r.contiguous(), w, k2, v2, a_in, b_in, packed.seq_off, packed.nseq)
+            packed.store(state, "att_kv", hT, diff_state)
+            packed.store_last(state, "att_x_prev", x, diff_state)
         elif diff_state:
             # training through the carried state: the scan and the new state are on the tape; the fields are REBOUND (the no-grad
             # path's in-place updates would overwrite tensors the tape still needs)
@@ -391,7 +460,11 @@ class RWKV7FeedForward(nn.Module):
         self.key = Linear(cfg.hidden_size, cfg.intermediate_size, bias=False)
         self.value = Linear(cfg.intermediate_size, cfg.hidden_size, bias=False)
 
-    def forward(self, x, mask, state: Optional[LayerState] = None, diff_state=False):
+    def forward(self, x, mask, state: Optional[LayerState] = None, diff_state=False, packed: Optional["_PackedState"] = None):
+        if packed is not None:   # packed row, one state per sequence (see RWKV7Attention.forward)
+            kx = packed.carry((fused.token_shift_mix1(x, None, self.x_k, mask),), x, state.ffn_x_prev, (self.x_k,))[0]
+            packed.store_last(state, "ffn_x_prev", x, diff_state)
+            return self.forward_mixed(kx)
         x_prev = None if state is None else state.ffn_x_prev
         kx = fused.token_shift_mix1(x, x_prev, self.x_k, mask)
         if diff_state:   # rebound with its graph (see RWKV7Attention.forward_mixed)
@@ -430,24 +503,26 @@ class RWKV7Block(nn.Module):
         self.ffn_norm = nn.LayerNorm(D, eps=cfg.norm_eps, bias=cfg.norm_bias)
         self.ffn = RWKV7FeedForward(cfg, layer_idx)
 
-    def forward(self, x, delta, mask, v_first, state: Optional[LayerState] = None, seq_start=None, diff_state=False):
+    def forward(self, x, delta, mask, v_first, state: Optional[LayerState] = None, seq_start=None, diff_state=False,
+                packed: Optional["_PackedState"] = None):
         """The block input is x + delta (delta = the previous block's channel-mix output, None for the first
         block): every residual add is fused with the LayerNorm that follows it (fused.add_layer_norm), so this
         block's own last add is left to the next block / the model's final norm.  Returns (x, delta, v_first).
-        diff_state: train through `state` (RWKV7Model.forward decides; the unfused stages, see RWKV7Attention.forward)."""
+        diff_state: train through `state` (RWKV7Model.forward decides; the unfused stages, see RWKV7Attention.forward).
+        packed: a packed row with per-sequence states (RWKV7Model._forward_packed_state): the same unfused stages."""
         if self.layer_idx == 0:
             if delta is not None:
                 x = x + delta
                 delta = None
             x = fused.layer_norm(x, self.pre_norm)
-        if diff_state:
+        if diff_state or packed is not None:
             if delta is None:
                 h = fused.layer_norm(x, self.attn_norm)
             else:
                 x, h = fused.add_layer_norm(x, delta, self.attn_norm)
-            att, v_first = self.attn(h, mask, v_first, state, diff_state=True)
+            att, v_first = self.attn(h, mask, v_first, state, diff_state=diff_state, packed=packed)
             x, h = fused.add_layer_norm(x, att, self.ffn_norm)
-            return x, self.ffn(h, mask, state, diff_state=True), v_first
+            return x, self.ffn(h, mask, state, diff_state=diff_state, packed=packed), v_first
         one_pass = fused.add_ln_mix_supported(x, state)
         if one_pass and (FUSED_ADD_LN_MIX6 or FUSED_ADD_LN_MIX6_FWD):
             x, mixed = fused.add_layer_norm_mix(x, delta, self.attn_norm, mask, self.attn.mix_params(), fwd_only=not FUSED_ADD_LN_MIX6)
@@ -513,8 +588,8 @@ class RWKV7Model(nn.Module):
             raise ValueError("You must specify exactly one of input_ids or inputs_embeds")
         x = self.embeddings(input_ids) if inputs_embeds is None else inputs_embeds
         if cu_seqlens is not None:
-            if past_key_values is not None and len(past_key_values) > 0 and self._differentiable_state(past_key_values, x):
-                raise ValueError("cu_seqlens together with a differentiable cache: initial states per packed sequence are not supported")
+            if past_key_values is not None and len(past_key_values) > 0:
+                return self._forward_packed_state(x, cu_seqlens, past_key_values)
             return self._forward_packed(x, cu_seqlens)
         B, T, D = x.shape
         if not x.is_cuda:
@@ -564,13 +639,15 @@ class RWKV7Model(nn.Module):
             raise ValueError(f"training through a differentiable cache needs a bf16 model (the chunked backward is bf16 only), got {x.dtype}")
         return True
 
-    def _run_layers(self, x, mask, cache: Optional[Cache], seq_start=None, diff_state=False):
+    def _run_layers(self, x, mask, cache: Optional[Cache], seq_start=None, diff_state=False, packed=None):
         v_first = delta = None
         for i, layer in enumerate(self.layers):
             st = cache[i] if cache is not None else None
             if self.gradient_checkpointing and self.training and cache is None:
                 x, delta, v_first = torch.utils.checkpoint.checkpoint(layer, x, delta, mask, v_first, None, seq_start,
                                                                       use_reentrant=False)
+            elif packed is not None:
+                x, delta, v_first = layer(x, delta, mask, v_first, st, None, diff_state=diff_state, packed=packed)
             elif diff_state:
                 x, delta, v_first = layer(x, delta, mask, v_first, st, seq_start, diff_state=True)
             else:
@@ -614,6 +691,51 @@ class RWKV7Model(nn.Module):
         out = self._run_layers(x_al.unsqueeze(0), mask.unsqueeze(0), None, seq_off)
         packed = fused.gather_rows(out[0], dest, src_of)
         return ModelOutput(last_hidden_state=packed.unsqueeze(0), past_key_values=None)
+
+    def _forward_packed_state(self, x, cu_seqlens, cache: Cache):
+        """A packed row [1, total, D] (cu_seqlens, N sequences) that carries state: sequence i starts from row i of `cache` (its WKV
+        state and both token-shift predecessors) and leaves the state after its last token there -- the same as running each
+        sequence alone as [1, n_i] with cache row i (fla chunk_rwkv7's initial_state / output_final_state with cu_seqlens).  An
+        empty sequence leaves its row unchanged; seen_tokens grows by cu[-1] - cu[0].  Under no_grad or with a non-differentiable
+        cache the state tensors are updated IN PLACE (captured decode graphs and DecodeStep hold their addresses); with a
+        differentiable cache (Cache.zeros(..., differentiable=True) or state tensors that require grad) the fields are rebound to
+        tensors that carry their graph, as on plain rows.  bf16 only; a device cu_seqlens costs one host read-back; no gradient
+        checkpointing (as on every stateful path).
+
+        Layout (ops.packed_state_layout): every sequence ends on a chunk boundary with at least one masked row in front of it; under
+        autograd one identity chunk follows every sequence and one leads the row; the row is rounded by _row_align.  Masked rows are identity steps of the scan
+        (w = W_PAD, the rest 0); the token shift sees 0 before each first token, whose six (one) lerps are recomputed with the
+        carried predecessor.  The stages are the unfused ones of the differentiable plain-row path; the scan is
+        ops.wkv7_state_chunked_seq (the chunked kernels with one state per sequence)."""
+        n_rows = cache[0].att_kv.shape[0]
+        cu = [int(c) for c in cu_seqlens.tolist()]   # a device cu_seqlens: one host read-back here
+        N = len(cu) - 1
+        if n_rows != N:
+            raise ValueError(f"cu_seqlens holds {N} sequences but the cache has batch size {n_rows}: a packed row with a cache needs "
+                             "one cache row per sequence")
+        if x.dtype != torch.bfloat16:
+            raise ValueError(f"cu_seqlens with a cache needs a bf16 model (the stateful packed scan is bf16 only), got {x.dtype}")
+        if x.shape[0] != 1 or not x.is_cuda:
+            raise ValueError("cu_seqlens expects a packed [1, total, D] row on the HIP device")
+        total = x.shape[1]
+        if any(b < a for a, b in zip(cu[:-1], cu[1:])) or cu[0] < 0 or cu[-1] > total:
+            raise ValueError(f"cu_seqlens must be non-decreasing within [0, {total}], got {cu}")
+        diff = self._differentiable_state(cache, x)
+        lay = ops.packed_state_layout([b - a for a, b in zip(cu[:-1], cu[1:])], torch.is_grad_enabled(), align=_row_align)
+        cache.seen_tokens += cu[-1] - cu[0]
+        if lay.t_al == 0:
+            return ModelOutput(last_hidden_state=x.new_zeros(x.shape), past_key_values=cache)
+        dev = x.device
+        dest = torch.full((total,), -1, dtype=torch.int32)
+        dest[cu[0]:cu[-1]] = lay.dest
+        src_of = torch.full((lay.t_al,), -1, dtype=torch.int32)
+        src_of[lay.dest.long()] = torch.arange(cu[0], cu[-1], dtype=torch.int32)
+        dest, src_of = dest.to(dev, non_blocking=True), src_of.to(dev, non_blocking=True)
+        x_al = fused.gather_rows(x[0], src_of, dest)
+        keep = (src_of >= 0).view(1, -1, 1)
+        packed = _PackedState(lay, keep, dev)
+        out = self._run_layers(x_al.unsqueeze(0), keep.to(x.dtype), cache, diff_state=diff, packed=packed)
+        return ModelOutput(last_hidden_state=fused.gather_rows(out[0], dest, src_of).unsqueeze(0), past_key_values=cache)
 
     def _forward_packed(self, x, cu_seqlens):
         """Packed variable-length batch (data/utils/spark_dataset.py:111-162,

@@ -75,8 +75,9 @@ static_assert(BSSmem::end16 % 8 == 0 && BSSmem::BUF % 8 == 0 && BSSmem::BBh % 8 
 static_assert(BSSmem::bytes <= 160 * 1024, "LDS budget");
 }  // namespace
 
-// STATE (the stateful variants, plain rows only): dhT_ (may be NULL = zero) is the adjoint of the state after the last chunk, dh0_ (may be
-// NULL) receives the adjoint of the state chunk c0 started from; both fp32 [B,H,64 (value),64 (key)], the layout of the forward's h0 / hT.
+// STATE (the stateful variants): dhT_ (may be NULL = zero) is the adjoint of the state after the last chunk, dh0_ (may be NULL) receives
+// the adjoint of the state chunk c0 started from; both fp32 [R,H,64 (value),64 (key)], the layout of the forward's h0 / hT (R = B on plain
+// rows, R = nseq on packed rows: entry sq * H + hh).  A sequence with an empty chunk range copies dhT to dh0 (zeros for a NULL dhT).
 // E is the adjoint of H = S^T, so E[k][v] = dS[v][k]: the same register <-> global mapping as the forward's state tile.
 template <bool STATE>
 __global__ __launch_bounds__(512) void wkv7c_bseq_kernel(int T_, int H, const bf16_t *__restrict__ w_, const bf16_t *__restrict__ q_,
@@ -106,6 +107,7 @@ __global__ __launch_bounds__(512) void wkv7c_bseq_kernel(int T_, int H, const bf
     const int role = __builtin_amdgcn_readfirstlane(tid >> 8), wave = __builtin_amdgcn_readfirstlane(ltid >> 6);
     const int nc = T_ / kC;
     int bb, hh, c0 = 0, c1 = nc;
+    [[maybe_unused]] int sbh = bh;   // STATE: the entry of dhT_ / dh0_ (the row's head on plain rows, the sequence's on packed rows)
     if (seq_off_) {  // packed rows: one workgroup pair per (sequence, head) walks only that sequence's chunks
         const int sq = bh / H;
         hh = bh - sq * H;
@@ -114,6 +116,16 @@ __global__ __launch_bounds__(512) void wkv7c_bseq_kernel(int T_, int H, const bf
         c0 = g0 - bb * nc;
         c1 = c0 + (g1 - g0);
         bh = bb * H + hh;
+        if constexpr (STATE) {
+            sbh = sq * H + hh;
+            if (c1 <= c0) {   // no chunks: dh0 = dhT; this workgroup's 32 value rows, one float4 per thread (512 x 4 = 32 x 64)
+                if (dh0_) {
+                    const long o = (long)sbh * kN * kN + (long)vh * VH * kN + threadIdx.x * 4;
+                    *reinterpret_cast<float4 *>(dh0_ + o) = dhT_ ? *reinterpret_cast<const float4 *>(dhT_ + o) : make_float4(0.f, 0.f, 0.f, 0.f);
+                }
+                return;
+            }
+        }
         if (c1 <= c0) return;
     } else {
         bb = bh / H;
@@ -137,7 +149,7 @@ __global__ __launch_bounds__(512) void wkv7c_bseq_kernel(int T_, int H, const bf
         f32x16 Emaster = zero16();  // waves 1, 2: D-layout tile (32 keys x 32 value columns) of E_{cc+1}, fp32, not yet decayed
         // E after the last chunk = the final state's adjoint (zero without one).  It reaches the E planes as E' in interval b of the first
         // iteration and e_vk[c1 - 1] as the first record: the zero fill of the planes above is overwritten before it is read either way.
-        if (STATE && dhT_ && (wave == 1 || wave == 2)) Emaster = state_tile_load(dhT_ + (long)bh * kN * kN, vh, wave - 1, lane);
+        if (STATE && dhT_ && (wave == 1 || wave == 2)) Emaster = state_tile_load(dhT_ + (long)sbh * kN * kN, vh, wave - 1, lane);
         lds_barrier();
         lds_barrier();
         lds_barrier();
@@ -215,7 +227,7 @@ __global__ __launch_bounds__(512) void wkv7c_bseq_kernel(int T_, int H, const bf
             lds_barrier();
             BSSTAMP(3);
         }
-        if (STATE && dh0_ && (wave == 1 || wave == 2)) state_tile_store(dh0_ + (long)bh * kN * kN, Emaster, vh, wave - 1, lane);   // E_{c0}
+        if (STATE && dh0_ && (wave == 1 || wave == 2)) state_tile_store(dh0_ + (long)sbh * kN * kN, Emaster, vh, wave - 1, lane);   // E_{c0}
         if (z_) {   // Z of the last chunk processed (c0)
             const long o = head_base + (long)(c0 * kC + pt) * tstride + vh * VH + pv;
             *reinterpret_cast<float4 *>(z_ + o) = *reinterpret_cast<const float4 *>(&sh_Z[pt * kStageLD + pv]);
@@ -365,6 +377,14 @@ int chunk_bseq_state_bf16(int B, int T_, int H, const void *w, const void *q, co
                           const float *tinv, void *e_vk, float *z, const float *dhT, float *dh0, hipStream_t st) {
     if (!dhT && !dh0) return chunk_bseq_bf16(B, T_, H, w, q, a, b, dy, tinv, e_vk, z, nullptr, 0, st);
     return launch_bseq<true>(B, T_, H, w, q, a, b, dy, tinv, e_vk, z, nullptr, 0, dhT, dh0, st);
+}
+
+// packed rows with one carried state per sequence (dhT / dh0 [nseq,H,64,64], each may be NULL; both NULL: the stateless packed kernel)
+int chunk_bseq_state_seq_bf16(int B, int T_, int H, const void *w, const void *q, const void *a, const void *b, const void *dy,
+                              const float *tinv, void *e_vk, float *z, const int *seq_off, int nseq, const float *dhT, float *dh0,
+                              hipStream_t st) {
+    if (!dhT && !dh0) return chunk_bseq_bf16(B, T_, H, w, q, a, b, dy, tinv, e_vk, z, seq_off, nseq, st);
+    return launch_bseq<true>(B, T_, H, w, q, a, b, dy, tinv, e_vk, z, seq_off, nseq, dhT, dh0, st);
 }
 
 }  // namespace rwkv7

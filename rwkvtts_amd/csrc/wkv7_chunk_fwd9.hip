@@ -80,7 +80,9 @@ static_assert(F9Smem::bytes <= 160 * 1024, "LDS budget");
 }  // namespace
 
 // STATE (the stateful variants): h0_ (may be NULL = zero) is the state chunk c0 starts from, hT_ (may be NULL) receives the state after
-// the last chunk; both fp32 [B,H,64 (value),64 (key)], plain rows only (seq_off_ == NULL).  The stateless instantiations never touch them.
+// the last chunk; both fp32 [R,H,64 (value),64 (key)] with R = B on plain rows and R = nseq on packed rows (seq_off_ != NULL: the state
+// of sequence sq, head hh is entry sq * H + hh).  A sequence with an empty chunk range copies h0 to hT (zeros for a NULL h0).  The
+// stateless instantiations never touch them.
 template <bool SAVE, bool STATE>
 __global__ __launch_bounds__(512) void wkv7c_fwd9_kernel(int T_, int H, const bf16_t *__restrict__ w_, const bf16_t *__restrict__ q_,
                                                          const bf16_t *__restrict__ k_, const bf16_t *__restrict__ v_,
@@ -112,6 +114,7 @@ __global__ __launch_bounds__(512) void wkv7c_fwd9_kernel(int T_, int H, const bf
     const int role = __builtin_amdgcn_readfirstlane(tid >> 8), wave = __builtin_amdgcn_readfirstlane(ltid >> 6);
     const int nc = T_ / kC;
     int bb, hh, c0 = 0, c1 = nc;
+    [[maybe_unused]] int sbh = bh;   // STATE: the entry of h0_ / hT_ (the row's head on plain rows, the sequence's on packed rows)
     if (seq_off_) {  // packed rows: one workgroup pair per (sequence, head) walks only that sequence's chunks
         const int sq = bh / H;
         hh = bh - sq * H;
@@ -120,6 +123,16 @@ __global__ __launch_bounds__(512) void wkv7c_fwd9_kernel(int T_, int H, const bf
         c0 = g0 - bb * nc;
         c1 = c0 + (g1 - g0);
         bh = bb * H + hh;
+        if constexpr (STATE) {
+            sbh = sq * H + hh;
+            if (c1 <= c0) {   // no chunks: hT = h0; this workgroup's 32 value rows, one float4 per thread (512 x 4 = 32 x 64)
+                if (hT_) {
+                    const long o = (long)sbh * kN * kN + (long)vh * VH * kN + threadIdx.x * 4;
+                    *reinterpret_cast<float4 *>(hT_ + o) = h0_ ? *reinterpret_cast<const float4 *>(h0_ + o) : make_float4(0.f, 0.f, 0.f, 0.f);
+                }
+                return;
+            }
+        }
         if (c1 <= c0) return;
     } else {
         bb = bh / H;
@@ -149,7 +162,7 @@ __global__ __launch_bounds__(512) void wkv7c_fwd9_kernel(int T_, int H, const bf
         f32x16 Smaster = zero16();  // waves 1, 2: D-layout tile (32 keys x 32 value columns) of the fp32 state
         if (from_h0 && (wave == 1 || wave == 2)) {
             // the initial state straight into the chain waves' fp32 tile and the state planes (read first in interval a, two barriers on)
-            Smaster = state_tile_load(h0_ + (long)bh * kN * kN, vh, wave - 1, lane);
+            Smaster = state_tile_load(h0_ + (long)sbh * kN * kN, vh, wave - 1, lane);
             store_T_split(Smaster, sm + L::Sh + (wave - 1) * 32, sm + L::Sl + (wave - 1) * 32, LDK, lane);
         }
         // y (and sa) of a chunk, staged in its interval b, leave at the start of the next interval a: thread (pt, pv) owns 4 value
@@ -253,7 +266,7 @@ __global__ __launch_bounds__(512) void wkv7c_fwd9_kernel(int T_, int H, const bf
             F9STAMP(6);
         }
         store_out(c1 - 1);
-        if (STATE && hT_ && (wave == 1 || wave == 2)) state_tile_store(hT_ + (long)bh * kN * kN, Smaster, vh, wave - 1, lane);
+        if (STATE && hT_ && (wave == 1 || wave == 2)) state_tile_store(hT_ + (long)sbh * kN * kN, Smaster, vh, wave - 1, lane);
     } else {
         // =================================================================================================== producer
 #if WKV7C_F9_PRODUCER_PRIO
@@ -428,6 +441,14 @@ int chunk_fwd9_state_bf16(int B, int T_, int H, const void *w, const void *q, co
                           const float *tinv, void *y, float *sa, void *hs, const float *h0, float *hT, hipStream_t st) {
     if (!h0 && !hT) return chunk_fwd9_bf16(B, T_, H, w, q, k, v, a, b, tinv, y, sa, hs, nullptr, 0, st);
     return launch_fwd9<true>(sa && hs, B, T_, H, w, q, k, v, a, b, tinv, y, sa, hs, nullptr, 0, h0, hT, st);
+}
+
+// packed rows with one carried state per sequence (h0 / hT [nseq,H,64,64], each may be NULL; both NULL: the stateless packed kernel)
+int chunk_fwd9_state_seq_bf16(int B, int T_, int H, const void *w, const void *q, const void *k, const void *v, const void *a,
+                              const void *b, const float *tinv, void *y, float *sa, void *hs, const int *seq_off, int nseq,
+                              const float *h0, float *hT, hipStream_t st) {
+    if (!h0 && !hT) return chunk_fwd9_bf16(B, T_, H, w, q, k, v, a, b, tinv, y, sa, hs, seq_off, nseq, st);
+    return launch_fwd9<true>(sa && hs, B, T_, H, w, q, k, v, a, b, tinv, y, sa, hs, seq_off, nseq, h0, hT, st);
 }
 
 }  // namespace rwkv7

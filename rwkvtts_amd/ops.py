@@ -494,3 +494,160 @@ def wkv7_state_chunked(h0, r, w, k, v, a, b):
         raise TypeError(f"wkv7_state_chunked: h0 must be float32 [B,H,64,64] = {(B, HC // HEAD_SIZE, 64, 64)}, got "
                         f"{h0.dtype} {tuple(h0.shape)}")
     return _WkvStateChunked.apply(h0, r, w, k, v, a, b)
+
+
+# ------------------------------------------------------------------------------------------------
+# the same on packed rows (fla's cu_seqlens): one carried state per sequence
+# ------------------------------------------------------------------------------------------------
+class PackedStateLayout:
+    """Where a packed row's sequences sit in the chunk-aligned row the stateful packed scan runs on (packed_state_layout).
+      t_al     rows of the aligned row (a multiple of CHUNK_T)
+      dest     int32 [sum(lens)]: aligned row of every packed position (positions counted from cu_seqlens[0])
+      seq_off  int32 [N + 1]: sequence i owns chunks seq_off[i] .. seq_off[i + 1] - 1 (empty range for an empty sequence)
+      first, last  int32 [N]: aligned rows of each sequence's first and last token (-1 for an empty sequence)"""
+    __slots__ = ("t_al", "dest", "seq_off", "first", "last")
+
+    def __init__(self, t_al, dest, seq_off, first, last):
+        self.t_al, self.dest, self.seq_off, self.first, self.last = t_al, dest, seq_off, first, last
+
+
+def packed_state_layout(lens, train, align=None):
+    """The chunk-aligned row for sequences of `lens` tokens that carry a state in and out (host ints; pure, no device work):
+      - every sequence ENDS on a chunk boundary and has at least one identity row in front of it (32 - n % 32 of them, 1 .. 32):
+        its first chunk is padded in front, so the scan reaches its first token with the carried state untouched, and the model's
+        token shift sees a masked predecessor there (RWKV7Model._forward_packed_state adds the carried one);
+      - train: one whole identity chunk follows every sequence, inside its chunk range -- the per-chunk gradient kernel reads the
+        end state of a sequence's last real chunk from the next chunk's start record, which must be this sequence's own state --
+        and one leads the ROW (in the first non-empty sequence's range): that kernel's workgroups run across the head boundaries of
+        the [H][chunk] space and start each head's first chunk from zero (include/rwkv7_hip.h, rwkv7_wkv_chunk_fwd_state_seq_bf16;
+        the sequences after the first need no leading one);
+      - align(rows) -> rows rounds the row up (RWKV7Model: _row_align); the rows it adds are identity chunks of the last non-empty
+        sequence, so every chunk of the row belongs to a sequence and none is left to uninitialised memory.
+    An empty sequence owns no chunk (first = last = -1).  With no tokens at all t_al = 0."""
+    C = CHUNK_T
+    lens = [int(n) for n in lens]
+    if any(n < 0 for n in lens):
+        raise ValueError(f"packed_state_layout: negative sequence length in {lens}")
+    dest = torch.empty(sum(lens), dtype=torch.int32)
+    seq_off, first, last = [0], [], []
+    t, pos, last_ne = (C if train and sum(lens) > 0 else 0), 0, -1
+    for i, n in enumerate(lens):
+        if n == 0:
+            first.append(-1)
+            last.append(-1)
+            seq_off.append(seq_off[-1])
+            continue
+        else:
+            lo = t + (C - n % C)
+            dest[pos:pos + n] = torch.arange(lo, lo + n, dtype=torch.int32)
+            first.append(lo)
+            last.append(lo + n - 1)
+            t = lo + n + (C if train else 0)
+            pos += n
+            last_ne = i
+            seq_off.append(t // C)
+    t_al = align(t) if (align is not None and t > 0) else t
+    if t_al > t:
+        for i in range(last_ne + 1, len(seq_off)):
+            seq_off[i] = t_al // C
+    return PackedStateLayout(t_al, dest, torch.tensor(seq_off, dtype=torch.int32), torch.tensor(first, dtype=torch.int32),
+                             torch.tensor(last, dtype=torch.int32))
+
+
+class _WkvStateChunkedSeq(torch.autograd.Function):
+    """y, hT = the per-sequence scans of an ALIGNED packed row on the chunked kernels, differentiable in h0 and r..b (see
+    wkv7_state_chunked_seq)."""
+
+    @staticmethod
+    def forward(ctx, h0, r, w, k, v, a, b, seq_off, nseq):
+        _, T, HC = r.shape
+        H = HC // HEAD_SIZE
+        train = any(ctx.needs_input_grad[:7])
+        w4, q4, k4, v4, a4, b4 = [x.contiguous().view(1, T, H, HEAD_SIZE) for x in (w, r, k, v, a, b)]
+        h0c = h0.contiguous()
+        tinv = wkv7_chunk_prep(w4, a4, b4)
+        y = torch.empty_like(v4)
+        sa = torch.empty(1, T, H, HEAD_SIZE, dtype=torch.float32, device=r.device) if train else None
+        hs = torch.empty(1, H, T // CHUNK_T, Q15_REC, dtype=torch.int16, device=r.device) if train else None
+        hT = torch.empty(nseq, H, HEAD_SIZE, HEAD_SIZE, dtype=torch.float32, device=r.device)
+        with torch.cuda.device_of(r), _timed("wkv7c_fwd_state_seq", r):
+            rc = _lib.lib().rwkv7_wkv_chunk_fwd_state_seq_bf16(1, T, H, _p(w4), _p(q4), _p(k4), _p(v4), _p(a4), _p(b4), _p(tinv), _p(y),
+                                                               _p(sa), _p(hs), _p(seq_off), nseq, _p(h0c), _p(hT), _stream(r))
+        _lib.check(rc, "wkv7_state_chunked_seq")
+        if train:
+            ctx.save_for_backward(w4, q4, k4, v4, a4, b4, tinv, sa, hs, seq_off)
+            ctx.nseq = nseq
+        ctx.set_materialize_grads(False)
+        return y.view(1, T, HC), hT
+
+    @staticmethod
+    def backward(ctx, dy, dhT):
+        w4, q4, k4, v4, a4, b4, tinv, sa, hs, seq_off = ctx.saved_tensors
+        _, T, H, C = w4.shape
+        dy4 = torch.zeros_like(v4) if dy is None else dy.to(w4.dtype).contiguous().view(1, T, H, C)
+        dhT = None if dhT is None else dhT.to(torch.float32).contiguous()
+        dh0 = torch.empty(ctx.nseq, H, C, C, dtype=torch.float32, device=w4.device) if ctx.needs_input_grad[0] else None
+        e_vk = torch.empty(1, H, T // CHUNK_T, Q15_REC, dtype=torch.int16, device=w4.device)
+        z = torch.empty(1, T, H, C, dtype=torch.float32, device=w4.device)
+        with torch.cuda.device_of(w4), _timed("wkv7c_bseq_state_seq", w4):
+            rc = _lib.lib().rwkv7_wkv_chunk_bseq_state_seq_bf16(1, T, H, _p(w4), _p(q4), _p(a4), _p(b4), _p(dy4), _p(tinv), _p(e_vk),
+                                                                _p(z), _p(seq_off), ctx.nseq, _p(dhT), _p(dh0), _stream(w4))
+        _lib.check(rc, "wkv7_state_chunked_seq backward (bseq)")
+        grads = [torch.empty_like(w4) for _ in range(6)]   # dw dq dk dv da db
+        with torch.cuda.device_of(w4), _timed("wkv7c_bwd_out", w4):
+            rc = _lib.lib().rwkv7_wkv_chunk_bwd_out_z_bf16(1, T, H, _p(w4), _p(q4), _p(k4), _p(v4), _p(a4), _p(b4), _p(dy4), _p(hs),
+                                                           _p(sa), _p(z), _p(e_vk), *[_p(g) for g in grads], _stream(w4))
+        _lib.check(rc, "wkv7_state_chunked_seq backward (bwd_out)")
+        dw, dq, dk, dv, da, db = [g.view(1, T, H * C) for g in grads]
+        return dh0, dq, dw, dk, dv, da, db, None, None
+
+
+def wkv7_state_chunked_seq(h0, r, w, k, v, a, b, seq_off, nseq):
+    """The per-sequence scans of a packed row that is ALREADY laid out (packed_state_layout): r..b bf16 [1, T_al, H*64] with
+    identity steps (w = W_PAD, the rest 0) at every row outside a sequence, seq_off int32 [nseq + 1] on the device, h0 fp32
+    [nseq,H,64,64].  Returns (y [1, T_al, H*64], hT [nseq,H,64,64]); the gradients at the identity rows are not meaningful."""
+    return _WkvStateChunkedSeq.apply(h0, r, w, k, v, a, b, seq_off, nseq)
+
+
+def wkv7_state_chunked_varlen(h0, r, w, k, v, a, b, cu_seqlens):
+    """wkv7_state_chunked on a packed row (fla chunk_rwkv7's initial_state / output_final_state with cu_seqlens): sequence i occupies
+    [cu_seqlens[i], cu_seqlens[i+1]) of r..b (bf16 [1, total, H*64]) and starts from h0[i] (fp32 [N,H,64,64]).  Returns
+    (y [1, total, H*64], hT [N,H,64,64]); differentiable in all seven inputs.  An empty sequence passes its state through
+    (hT[i] = h0[i], dh0[i] = dhT[i]); positions outside [cu_seqlens[0], cu_seqlens[-1]) give y = 0.  The op lays the sequences out
+    on its own chunk-aligned row (packed_state_layout, identity steps in every pad row, framed for training when any input requires
+    grad) and drops the pad rows' gradients.  A device cu_seqlens costs one host read-back."""
+    _, total, HC = r.shape
+    for t in (w, k, v, a, b):
+        if t.shape != r.shape:
+            raise ValueError(f"wkv7_state_chunked_varlen: r..b must share one shape [1,total,H*64], got {tuple(r.shape)} / {tuple(t.shape)}")
+    if r.shape[0] != 1 or HC % HEAD_SIZE != 0:
+        raise ValueError(f"wkv7_state_chunked_varlen: need a packed [1, total, H*64] row, got {tuple(r.shape)}")
+    if any(t.dtype != torch.bfloat16 for t in (r, w, k, v, a, b)):
+        raise TypeError("wkv7_state_chunked_varlen: r..b must be bfloat16 (the chunked backward is bf16 only)")
+    if not all(t.is_cuda for t in (h0, r, w, k, v, a, b)):
+        raise NotImplementedError("wkv7_state_chunked_varlen: HIP device tensors only (no CPU path)")
+    cu = [int(c) for c in cu_seqlens.tolist()]
+    N, H = len(cu) - 1, HC // HEAD_SIZE
+    if N < 1 or any(b_ < a_ for a_, b_ in zip(cu[:-1], cu[1:])) or cu[0] < 0 or cu[-1] > total:
+        raise ValueError(f"wkv7_state_chunked_varlen: cu_seqlens must be non-decreasing within [0, {total}], got {cu}")
+    if h0.dtype != torch.float32 or tuple(h0.shape) != (N, H, HEAD_SIZE, HEAD_SIZE):
+        raise TypeError(f"wkv7_state_chunked_varlen: h0 must be float32 [N,H,64,64] = {(N, H, 64, 64)}, got {h0.dtype} {tuple(h0.shape)}")
+    train = torch.is_grad_enabled() and any(t.requires_grad for t in (h0, r, w, k, v, a, b))
+    lay = packed_state_layout([b_ - a_ for a_, b_ in zip(cu[:-1], cu[1:])], train)
+    if lay.t_al == 0:
+        return r.new_zeros(r.shape), h0.clone()
+    dev = r.device
+    src = torch.full((lay.t_al,), cu[-1] - cu[0], dtype=torch.long)   # index of the fill row
+    src[lay.dest.long()] = torch.arange(cu[-1] - cu[0])
+    src = src.to(dev, non_blocking=True)
+
+    def lay_out(x, fill):
+        rows = torch.cat([x[0, cu[0]:cu[-1]], x.new_full((1, HC), fill)], 0)
+        return rows.index_select(0, src).unsqueeze(0)
+
+    ins = [lay_out(x, f) for x, f in ((r, 0.0), (w, W_PAD), (k, 0.0), (v, 0.0), (a, 0.0), (b, 0.0))]
+    y_al, hT = wkv7_state_chunked_seq(h0, *ins, lay.seq_off.to(dev, non_blocking=True), N)
+    y = y_al[0].index_select(0, lay.dest.to(dev, non_blocking=True).long())
+    if cu[0] > 0 or cu[-1] < total:
+        y = torch.cat([y.new_zeros(cu[0], HC), y, y.new_zeros(total - cu[-1], HC)], 0)
+    return y.unsqueeze(0), hT
