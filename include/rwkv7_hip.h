@@ -587,6 +587,40 @@ int rwkv7_sample_rows_tail_f32(int rows, const float *logits, long ld, const int
                                const int *allow_hi, const int *suppress, int nsuppress, int max_domain, int do_sample, int top_k, float top_p,
                                float temperature, unsigned long long seed, const long *step, long *out, const rwkv7_sample_tail *tail,
                                int min_eos_id, long min_eos_until, rwkv7_stream_t stream);
+/* rwkv7_sample_slots_f32: the one-segment draw + decode-loop bookkeeping per SLOT of a continuous-batching engine
+ * (rwkvtts_amd/continuous.py), where every slot runs its own request.  Logits row r belongs to slot s = row_slot[r] (row_slot NULL:
+ * s = r; rows with s outside [0, slots) are skipped).  A slot with live[s] == 0 is left untouched (x[s] keeps its row).  A live
+ * slot draws one id with its own do_sample / inv_temp / top_k / top_p, EOS barred while step[s] < min_until[s], from the ids
+ * [allow_lo[0], allow_hi[0]) of the row (NULL: the first max_domain columns) minus `suppress`; Philox key seed[s], counter
+ * (step[s], 0): the id is bit-identical to a ONE-row rwkv7_sample_rows_tail_f32 call with *step = step[s] and the same key,
+ * parameters (temperature = 1 / inv_temp) and logits.  Then seq[s][step[s]] = id (if step[s] < seq_ld), ids[s] = id,
+ * x[s] = emb[id] (emb NULL: no copy), step[s] += 1, live[s] = id != eos && step[s] < limit[s].  All per-slot fields are DEVICE
+ * arrays of `slots` entries; eos < 0: no EOS.  top_k_max (host): the largest top_k[] value, in [0, 64]; a slot's top_k is
+ * clamped to it.  A sampled slot with top_k = 0 draws from the whole distribution (top_p is ignored there).  Errors:
+ * RWKV7_EINVAL for rows <= 0, a null st / logits / per-slot array, seq_ld <= 0, slots <= 0, emb without x; RWKV7_ESHAPE for
+ * max_domain > 15360, nsuppress > 256, top_k_max outside [0, 64], D % 8 != 0. */
+typedef struct rwkv7_slot_state {
+    long *step;                 /* ids emitted so far = output column of the next id */
+    long *limit;                /* max_new_tokens of the slot's request */
+    long *min_until;            /* EOS barred while step < min_until (0: none) */
+    unsigned long long *seed;   /* the request's Philox key */
+    float *inv_temp;
+    int *top_k;
+    float *top_p;
+    unsigned char *do_sample;
+    unsigned char *live;        /* 1 while the slot's request runs */
+    long *ids;                  /* next input id */
+    long *seq;                  /* [slots][seq_ld] generated ids */
+    long seq_ld;
+    const void *emb;            /* bf16 [V][D] embedding table, or NULL */
+    void *x;                    /* bf16 [slots][D]: the next decode step's input */
+    int D;
+    int slots;
+    int top_k_max;
+    long eos;
+} rwkv7_slot_state;
+int rwkv7_sample_slots_f32(int rows, const float *logits, long ld, const int *row_slot, const int *allow_lo, const int *allow_hi,
+                           const int *suppress, int nsuppress, int max_domain, const rwkv7_slot_state *st, rwkv7_stream_t stream);
 int rwkv7_ras_step_f32(int V, const float *logits, long *tok, long *recent, long *ptr, long *step_i, long n_ignore, int eos, float top_p,
                        int top_k, int win_size, float tau_r, unsigned long long seed, rwkv7_stream_t stream);
 

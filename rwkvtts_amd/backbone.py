@@ -583,10 +583,13 @@ class RWKV7Model(nn.Module):
         self.gradient_checkpointing = False
 
     def forward(self, input_ids=None, attention_mask=None, inputs_embeds=None, past_key_values: Optional[Cache] = None,
-                use_cache: Optional[bool] = None, cu_seqlens=None, attention_mask_all_ones: Optional[bool] = None, **kwargs):
+                use_cache: Optional[bool] = None, cu_seqlens=None, attention_mask_all_ones: Optional[bool] = None, cache_rows=None,
+                **kwargs):
         if (input_ids is None) == (inputs_embeds is None):
             raise ValueError("You must specify exactly one of input_ids or inputs_embeds")
         x = self.embeddings(input_ids) if inputs_embeds is None else inputs_embeds
+        if cache_rows is not None:
+            return self._forward_packed_rows(x, cu_seqlens, past_key_values, cache_rows)
         if cu_seqlens is not None:
             if past_key_values is not None and len(past_key_values) > 0:
                 return self._forward_packed_state(x, cu_seqlens, past_key_values)
@@ -736,6 +739,35 @@ class RWKV7Model(nn.Module):
         packed = _PackedState(lay, keep, dev)
         out = self._run_layers(x_al.unsqueeze(0), keep.to(x.dtype), cache, diff_state=diff, packed=packed)
         return ModelOutput(last_hidden_state=fused.gather_rows(out[0], dest, src_of).unsqueeze(0), past_key_values=cache)
+
+    def _forward_packed_rows(self, x, cu_seqlens, cache: Cache, cache_rows):
+        """`_forward_packed_state` into chosen rows of a larger cache: sequence i starts from and ends in cache row cache_rows[i] (N
+        distinct rows of a cache with batch >= N); every other row stays as it was, bit for bit.  The named rows are gathered into an
+        N-row cache, run as `_forward_packed_state`, and copied back IN PLACE (captured decode graphs and DecodeStep keep their
+        addresses), so the result is that of the same pack on an N-row cache holding those rows.  No-grad or plain caches only.  The
+        rows are read on the host (one read-back for a device tensor)."""
+        if cu_seqlens is None or cache is None or len(cache) == 0:
+            raise ValueError("cache_rows needs cu_seqlens and past_key_values")
+        if getattr(cache, "differentiable", False) or any(t.requires_grad for s in cache.states
+                                                          for t in (s.att_x_prev, s.att_kv, s.ffn_x_prev)):
+            raise ValueError("cache_rows updates the cache in place: a differentiable cache is not supported")
+        rows = [int(r) for r in torch.as_tensor(cache_rows).reshape(-1).tolist()]
+        n_rows, N = cache[0].att_kv.shape[0], cu_seqlens.numel() - 1
+        if len(rows) != N:
+            raise ValueError(f"cache_rows names {len(rows)} rows for {N} sequences")
+        if len(set(rows)) != N or any(not 0 <= r < n_rows for r in rows):
+            raise ValueError(f"cache_rows must be {N} distinct rows in [0, {n_rows}), got {rows}")
+        idx = torch.tensor(rows, dtype=torch.int64).to(cache[0].att_kv.device, non_blocking=True)
+        sub = Cache([LayerState(s.att_x_prev.index_select(0, idx), s.att_kv.index_select(0, idx), s.ffn_x_prev.index_select(0, idx))
+                     for s in cache.states], cache.seen_tokens)
+        out = self._forward_packed_state(x, cu_seqlens, sub)
+        with torch.no_grad():
+            for s, t in zip(cache.states, sub.states):
+                s.att_x_prev.index_copy_(0, idx, t.att_x_prev)
+                s.att_kv.index_copy_(0, idx, t.att_kv)
+                s.ffn_x_prev.index_copy_(0, idx, t.ffn_x_prev)
+        cache.seen_tokens = sub.seen_tokens
+        return ModelOutput(last_hidden_state=out.last_hidden_state, past_key_values=cache)
 
     def _forward_packed(self, x, cu_seqlens):
         """Packed variable-length batch (data/utils/spark_dataset.py:111-162,

@@ -1,0 +1,327 @@
+"""Continuous batching: a decode batch that admits new requests while it runs ("persistent multi-request decode").
+
+GraphDecoder runs a closed batch until its longest sequence ends, so a slot whose request finished early idles until then.  Here
+every one of up to 32 SLOTS (rows of the step kernel's batch) runs its own request:
+
+  * one captured step: DecodeStep on the live cache, then rwkv7_sample_slots_f32 (csrc/sampling.hip) on its logits, which draws
+    every live slot's id with that slot's own key, step counter and sampling parameters and does the slot's bookkeeping (output
+    column, next input embedding, step, live flag);
+  * admission, eagerly between replays on the same stream: pending requests in FIFO order take free slots, their cache rows are
+    reset to zero and prefilled as ONE packed row (RWKV7Model(..., cu_seqlens, past_key_values, cache_rows)), the head runs on each
+    sequence's last position, and the same per-slot entry (with row_slot) draws the first id;
+  * retirement: without EOS the host knows every budget and retires slots on the exact step with no read-back; with EOS it reads
+    the live flags and step counters back every `check_every` replays.
+
+A request's draws use (its seed, its step) only, so its ids do not depend on its slot or on when it was admitted.  Slots without a
+request keep stepping on stale state; admission resets the row.  The scheduling lives in SlotScheduler, which never touches the
+device.
+"""
+from __future__ import annotations
+
+import collections
+import ctypes
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import torch
+
+from . import _lib
+from .backbone import Cache
+from .sampling import MAX_TOP_K, RowSampler, fresh_seed
+
+
+@dataclass
+class Request:
+    handle: int
+    embeds: object            # [T, D] prompt embeddings (device tensor) -- opaque to the scheduler
+    max_new_tokens: int
+    min_new_tokens: int = 0
+    do_sample: bool = False
+    temperature: float = 1.0
+    top_k: int = 0
+    top_p: float = 1.0
+    seed: int = 0
+
+
+class SlotScheduler:
+    """Device-free bookkeeping of ContinuousDecoder: the FIFO queue of pending requests, the free slots, and every busy slot's budget.
+
+    A request admitted into a slot has drawn its first id; `remaining[slot]` is the number of replays until its budget
+    (max_new_tokens) is exhausted.  advance(n) accounts for n replays."""
+
+    def __init__(self, slots: int):
+        if slots < 1:
+            raise ValueError("slots must be >= 1")
+        self.slots = slots
+        self.pending: collections.deque = collections.deque()
+        self.free: List[int] = list(range(slots))     # ascending; admission takes the lowest free slot
+        self.busy: Dict[int, Request] = {}            # slot -> request
+        self.remaining: Dict[int, int] = {}           # slot -> replays left in its budget
+        self._next = 0
+
+    def submit(self, **fields) -> int:
+        h = self._next
+        self._next += 1
+        req = Request(handle=h, **fields)
+        if req.max_new_tokens < 1:
+            raise ValueError("max_new_tokens must be >= 1")
+        self.pending.append(req)
+        return h
+
+    def admit(self) -> List[Tuple[int, Request]]:
+        """Pending requests in FIFO order into the free slots: [(slot, request)]."""
+        out = []
+        while self.pending and self.free:
+            slot = self.free.pop(0)
+            req = self.pending.popleft()
+            self.busy[slot] = req
+            self.remaining[slot] = req.max_new_tokens - 1
+            out.append((slot, req))
+        return out
+
+    def advance(self, n: int):
+        for s in self.remaining:
+            self.remaining[s] = max(0, self.remaining[s] - n)
+
+    def due(self) -> List[int]:
+        """Busy slots whose budget is exhausted."""
+        return sorted(s for s, r in self.remaining.items() if r == 0)
+
+    def replays_until_due(self) -> int:
+        """Replays until the next busy slot exhausts its budget (0: one already has; 0 too when nothing is busy)."""
+        return min(self.remaining.values(), default=0)
+
+    def longest(self) -> int:
+        return max(self.remaining.values(), default=0)
+
+    def retire(self, slot: int) -> Request:
+        req = self.busy.pop(slot)
+        del self.remaining[slot]
+        self.free.append(slot)
+        self.free.sort()
+        return req
+
+    @property
+    def idle(self) -> bool:
+        return not self.pending and not self.busy
+
+
+class SlotState(ctypes.Structure):
+    """rwkv7_slot_state (include/rwkv7_hip.h)."""
+    _fields_ = [("step", ctypes.c_void_p), ("limit", ctypes.c_void_p), ("min_until", ctypes.c_void_p), ("seed", ctypes.c_void_p),
+                ("inv_temp", ctypes.c_void_p), ("top_k", ctypes.c_void_p), ("top_p", ctypes.c_void_p), ("do_sample", ctypes.c_void_p),
+                ("live", ctypes.c_void_p), ("ids", ctypes.c_void_p), ("seq", ctypes.c_void_p), ("seq_ld", ctypes.c_long),
+                ("emb", ctypes.c_void_p), ("x", ctypes.c_void_p), ("D", ctypes.c_int), ("slots", ctypes.c_int),
+                ("top_k_max", ctypes.c_int), ("eos", ctypes.c_long)]
+
+
+def sample_slots(logits: torch.Tensor, st: SlotState, row_slot: Optional[torch.Tensor] = None, allow_lo=None, allow_hi=None,
+                 suppress=None, max_domain: Optional[int] = None):
+    """rwkv7_sample_slots_f32 on the current stream: logits fp32 [rows, >= max_domain] (unit column stride); row_slot int32 [rows] or
+    None (row r is slot r); allow_lo / allow_hi int32 [1] device tensors or None; suppress int32 device tensor or None."""
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    if row_slot is not None:
+        assert row_slot.dtype == torch.int32 and row_slot.is_contiguous() and row_slot.numel() == logits.shape[0]
+    p = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)
+    with torch.cuda.device_of(logits):
+        rc = _lib.lib().rwkv7_sample_slots_f32(logits.shape[0], p(logits), ctypes.c_long(logits.stride(0)), p(row_slot), p(allow_lo),
+                                               p(allow_hi), p(suppress), 0 if suppress is None else suppress.numel(),
+                                               int(logits.shape[1] if max_domain is None else max_domain), ctypes.byref(st),
+                                               ctypes.c_void_p(torch.cuda.current_stream(logits.device).cuda_stream))
+    _lib.check(rc, "rwkv7_sample_slots_f32")
+
+
+class ContinuousDecoder:
+    """eng = ContinuousDecoder(model, slots=32, ...); h = eng.submit(...); eng.step() -> [(handle, ids)]; eng.run() -> {handle: ids}.
+
+    model: a bf16 RWKV7ForSpeech / RWKV7ForCausalLM on the HIP device that the step kernel covers (DecodeStep.supported); slots <= 32.
+    A request's ids run up to and including its EOS, or up to its max_new_tokens (<= max_new_tokens_cap), with no pad tail; they are
+    device int64 tensors.  pad_token_id is accepted for signature compatibility with GraphDecoder and not used: no pad is emitted."""
+
+    def __init__(self, model, slots: int = 32, max_new_tokens_cap: int = 3000, eos_token_id: Optional[int] = None,
+                 pad_token_id: Optional[int] = None, suppress_tokens: Optional[Sequence[int]] = None, check_every: int = 16):
+        from .decode import DecodeStep
+        if not 1 <= slots <= 32:
+            raise ValueError(f"slots = {slots}: the step kernel's batch is 1..32")
+        if max_new_tokens_cap < 1 or check_every < 1:
+            raise ValueError("max_new_tokens_cap and check_every must be >= 1")
+        self.model = model.eval()
+        m = self.model
+        dev = m.device
+        self.device, self.slots, self.cap, self.check_every = dev, slots, int(max_new_tokens_cap), int(check_every)
+        self.eos = None if eos_token_id is None else int(eos_token_id)
+        self.pad = pad_token_id
+        self.cache = Cache.zeros(m.config, slots, dev, m.dtype)
+        why = DecodeStep.supported(m.model, m.lm_head, self.cache)
+        if why is None and m.dtype != torch.bfloat16:
+            why = "the model must be bf16"
+        emb_w = m.get_input_embeddings().weight.detach()
+        if why is None and not (emb_w.dtype == torch.bfloat16 and emb_w.is_contiguous() and emb_w.shape[1] % 8 == 0):
+            why = "the input embedding table must be a contiguous bf16 [V, D] with D % 8 == 0"
+        if why:
+            raise ValueError("ContinuousDecoder needs the persistent decode step: " + why)
+        self.emb_w = emb_w
+        self.V = m.lm_head.weight.shape[0]
+        allow, sup = RowSampler.fold_suppress(self.V, None if not suppress_tokens else list(suppress_tokens))
+        self.allow = None if allow is None else [allow]
+        self.sup = sup
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.allow_lo = self.allow_hi = None
+        if allow is not None:
+            self.allow_lo, self.allow_hi = torch.tensor([allow[0]], **i32), torch.tensor([allow[1]], **i32)
+        self.max_domain = (allow[1] - allow[0]) if allow is not None else self.V
+        if emb_w.shape[0] < (allow[1] if allow is not None else self.V):
+            raise ValueError("the input embedding table has fewer rows than the head draws ids")
+        self.suppress = torch.tensor([int(t) for t in sup], **i32) if sup else None
+        why = RowSampler.supported(dev, [self.V], self.allow, self.sup)
+        if why:
+            raise ValueError("rwkv7_sample_slots_f32: " + why)
+
+        S, D = slots, m.config.hidden_size
+        l64 = dict(dtype=torch.int64, device=dev)
+        self.step_t = torch.zeros(S, **l64)
+        self.live = torch.zeros(S, dtype=torch.uint8, device=dev)
+        self.ids = torch.zeros(S, **l64)
+        self.seq = torch.zeros(S, self.cap, **l64)
+        self.x = torch.zeros(S, D, dtype=torch.bfloat16, device=dev)
+        # the parameters the device never writes: one block, mirrored on the host and copied whole at admission
+        self._par_host = {"limit": torch.ones(S, dtype=torch.int64), "min_until": torch.zeros(S, dtype=torch.int64),
+                          "seed": torch.zeros(S, dtype=torch.int64), "inv_temp": torch.ones(S, dtype=torch.float32),
+                          "top_k": torch.zeros(S, dtype=torch.int32), "top_p": torch.ones(S, dtype=torch.float32),
+                          "do_sample": torch.zeros(S, dtype=torch.uint8)}
+        self._par_dev = {k: torch.empty_like(v, device=dev) for k, v in self._par_host.items()}
+        for k, v in self._par_host.items():
+            self._par_dev[k].copy_(v)
+        st = SlotState()
+        pd = self._par_dev
+        st.step, st.limit, st.min_until, st.seed = (t.data_ptr() for t in (self.step_t, pd["limit"], pd["min_until"], pd["seed"]))
+        st.inv_temp, st.top_k, st.top_p, st.do_sample = (pd[k].data_ptr() for k in ("inv_temp", "top_k", "top_p", "do_sample"))
+        st.live, st.ids, st.seq, st.seq_ld = self.live.data_ptr(), self.ids.data_ptr(), self.seq.data_ptr(), self.cap
+        st.emb, st.x, st.D, st.slots, st.top_k_max = emb_w.data_ptr(), self.x.data_ptr(), D, S, MAX_TOP_K
+        st.eos = -1 if self.eos is None else self.eos
+        self.st = st
+
+        self.sched = SlotScheduler(slots)
+        self.dstep = DecodeStep(m.model, m.lm_head, self.cache)
+        # capture the step.  Every slot is idle (live = 0): the draw writes nothing, and the warm-up's change to the state of idle
+        # rows does not matter (admission resets a row before it is used)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            self._step()
+        torch.cuda.current_stream().wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self._step()
+        self.replays = 0   # captured steps run so far
+
+    def _step(self):
+        sample_slots(self.dstep(self.x), self.st, None, self.allow_lo, self.allow_hi, self.suppress, self.max_domain)
+
+    # ---- public interface ----------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def submit(self, input_ids=None, inputs_embeds=None, max_new_tokens: int = 256, min_new_tokens: int = 0, do_sample: bool = False,
+               temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: Optional[int] = None) -> int:
+        """Queue one request (a prompt of T ids [T] / [1, T] or embeddings [T, D] / [1, T, D]); returns its handle.  Non-blocking."""
+        if (input_ids is None) == (inputs_embeds is None):
+            raise ValueError("pass exactly one of input_ids or inputs_embeds")
+        if not 1 <= int(max_new_tokens) <= self.cap:
+            raise ValueError(f"max_new_tokens = {max_new_tokens} outside 1..{self.cap} (max_new_tokens_cap)")
+        top_k, top_p = int(top_k or 0), 1.0 if top_p is None else float(top_p)
+        why = RowSampler.supported(self.device, [self.V], self.allow, self.sup, do_sample, top_k, top_p, temperature)
+        if why:
+            raise ValueError("rwkv7_sample_slots_f32: " + why)
+        if inputs_embeds is None:
+            ids = torch.as_tensor(input_ids).reshape(-1).to(self.device)
+            e = self.model.get_input_embeddings()(ids)
+        else:
+            e = inputs_embeds.reshape(-1, inputs_embeds.shape[-1]).to(self.device, self.model.dtype)
+        if e.shape[0] < 1 or e.shape[1] != self.model.config.hidden_size:
+            raise ValueError(f"prompt of shape {tuple(e.shape)}")
+        seed = int(fresh_seed() if seed is None else seed) & ((1 << 64) - 1)
+        return self.sched.submit(embeds=e.detach(), max_new_tokens=int(max_new_tokens), min_new_tokens=int(min_new_tokens or 0),
+                                 do_sample=bool(do_sample), temperature=float(temperature or 1.0), top_k=top_k, top_p=top_p, seed=seed)
+
+    @torch.no_grad()
+    def step(self) -> List[Tuple[int, torch.Tensor]]:
+        """Admit what fits, run up to check_every replays, retire what finished: [(handle, ids)] of the requests that finished."""
+        done = []
+        if self.eos is None:
+            done += self._retire(self.sched.due(), None)
+        self._admit()
+        if self.eos is None:
+            done += self._retire(self.sched.due(), None)   # max_new_tokens = 1: finished with its first id
+            n = min(self.check_every, self.sched.replays_until_due())
+        else:
+            n = min(self.check_every, self.sched.longest())
+        if not self.sched.busy:
+            return done
+        for _ in range(n):
+            self.graph.replay()
+        self.replays += n
+        self.sched.advance(n)
+        if self.eos is None:
+            done += self._retire(self.sched.due(), None)
+        else:
+            both = torch.stack([self.live.to(torch.int64), self.step_t]).cpu()   # one small read-back
+            done += self._retire([s for s in sorted(self.sched.busy) if not both[0, s]], both[1])
+        if self.dstep.barrier_timed_out():
+            raise _lib.Rwkv7HipError("rwkv7_decode_step_bf16: a grid barrier timed out; the generated ids are invalid")
+        return done
+
+    @torch.no_grad()
+    def run(self) -> Dict[int, torch.Tensor]:
+        """Step until everything submitted so far has finished: {handle: ids}."""
+        out = {}
+        while not self.sched.idle:
+            for h, ids in self.step():
+                out[h] = ids
+        return out
+
+    # ---- internals -----------------------------------------------------------------------------------------------------------
+    def _retire(self, slots, steps) -> List[Tuple[int, torch.Tensor]]:
+        out = []
+        for s in slots:
+            req = self.sched.retire(s)
+            n = req.max_new_tokens if steps is None else int(steps[s])
+            out.append((req.handle, self.seq[s, :n].clone()))
+        return out
+
+    def _admit(self):
+        took = self.sched.admit()
+        if not took:
+            return
+        m, dev = self.model, self.device
+        slots = [s for s, _ in took]
+        lens = [r.embeds.shape[0] for _, r in took]
+        cu = [0]
+        for n in lens:
+            cu.append(cu[-1] + n)
+        rows64 = torch.tensor(slots, dtype=torch.int64).to(dev, non_blocking=True)
+        for st in self.cache.states:   # a fresh state for every admitted request
+            st.att_x_prev.index_fill_(0, rows64, 0)
+            st.att_kv.index_fill_(0, rows64, 0)
+            st.ffn_x_prev.index_fill_(0, rows64, 0)
+        packed = torch.cat([r.embeds for _, r in took], 0).unsqueeze(0)
+        cu_t = torch.tensor(cu, dtype=torch.int32)
+        h = m.model(inputs_embeds=packed, cu_seqlens=cu_t, past_key_values=self.cache, cache_rows=torch.tensor(slots)).last_hidden_state
+        last = torch.tensor([c - 1 for c in cu[1:]], dtype=torch.int64).to(dev, non_blocking=True)
+        logits = m.lm_head(h[0].index_select(0, last)).float()
+        # the slots' parameters: host mirror -> one copy per field; step = 0 and live = 1 for the admitted slots only (the device
+        # advances the other slots' counters)
+        ph = self._par_host
+        for s, r in took:
+            ph["limit"][s] = r.max_new_tokens
+            ph["min_until"][s] = r.min_new_tokens
+            ph["seed"][s] = r.seed - (1 << 64) if r.seed >= (1 << 63) else r.seed
+            ph["inv_temp"][s] = (torch.tensor(1.0, dtype=torch.float32) / torch.tensor(r.temperature, dtype=torch.float32)
+                                 if r.do_sample else torch.tensor(1.0))
+            ph["top_k"][s] = r.top_k if r.do_sample else 0
+            ph["top_p"][s] = r.top_p
+            ph["do_sample"][s] = int(r.do_sample)
+        for k, v in ph.items():
+            self._par_dev[k].copy_(v.pin_memory(), non_blocking=True)
+        self.step_t.index_fill_(0, rows64, 0)
+        self.live.index_fill_(0, rows64, 1)
+        row_slot = torch.tensor(slots, dtype=torch.int32).to(dev, non_blocking=True)
+        sample_slots(logits, self.st, row_slot, self.allow_lo, self.allow_hi, self.suppress, self.max_domain)

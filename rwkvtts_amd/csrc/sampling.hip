@@ -489,6 +489,105 @@ __global__ __launch_bounds__(kSmpThreads) void sample_rows_kernel(int nseg, cons
     }
 }
 
+// ---- continuous batching: one draw per decode SLOT, each slot with its own request ------------------------------------------------
+// = rwkv7_slot_state (include/rwkv7_hip.h).  Every per-slot field is a DEVICE array of `slots` entries.
+struct SlotState {
+    long *step, *limit, *min_until;
+    unsigned long long *seed;
+    float *inv_temp;
+    int *top_k;
+    float *top_p;
+    unsigned char *do_sample, *live;
+    long *ids, *seq;
+    long seq_ld;
+    const uint16_t *emb;
+    uint16_t *x;
+    int D, slots, top_k_max;
+    long eos;
+};
+
+// Row r of `logits` belongs to slot s = row_slot[r] (row_slot NULL: s = r).  The draw is the one of sample_rows_kernel for a ONE-row
+// launch (workgroup 0) with the slot's key, step counter, parameters and min-EOS bound, so a request's ids do not depend on the slot
+// it occupies or on when it was admitted; then the slot's bookkeeping (output column, next id, its embedding row, step, live flag).
+// The body repeats sample_rows_kernel's draw instead of sharing it so that the existing kernels stay byte-for-byte as they were.
+template <int EPT>
+__global__ __launch_bounds__(kSmpThreads) void sample_slots_kernel(const float *__restrict__ logits, long ld, const int *__restrict__ row_slot,
+                                                                   const int *__restrict__ allow_lo, const int *__restrict__ allow_hi,
+                                                                   const int *__restrict__ suppress, int nsuppress, int max_domain, SlotState st) {
+    __shared__ SmpShared sm;
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const int s = row_slot ? row_slot[row] : row;
+    if (s < 0 || s >= st.slots || !st.live[s]) return;   // uniform over the workgroup; a slot that is not live is left untouched
+    const long step = st.step[s];
+    const int do_sample = st.do_sample[s] != 0;
+    const float inv_temp = do_sample ? st.inv_temp[s] : 1.f;
+    const int top_k = min(max(st.top_k[s], 0), st.top_k_max);
+    const float top_p = st.top_p[s];
+    const float *xg = logits + (long)row * ld;
+    const int lo = allow_lo ? max(allow_lo[0], 0) : 0, hi = allow_hi ? min(allow_hi[0], lo + max_domain) : max_domain;
+    const int m = hi - lo;
+    Vals<EPT> x;
+#pragma unroll
+    for (int e = 0; e < EPT; e++) {
+        const int j = tid + kSmpThreads * e;
+        const float t = xg[lo + min(j, m - 1)];
+        x.v[e] = j < m ? t * inv_temp : -INFINITY;
+    }
+    for (int t = 0; t < nsuppress; t++) {
+        const int sidx = suppress[t] - lo;
+        if (sidx >= 0 && sidx < m && (sidx & (kSmpThreads - 1)) == tid) x.drop(sidx);
+    }
+    if (st.eos >= 0 && step < st.min_until[s]) {
+        const long sidx = st.eos - lo;
+        if (sidx >= 0 && sidx < m && (sidx & (kSmpThreads - 1)) == tid) x.drop((int)sidx);
+    }
+    int choice;
+    if (!do_sample) {
+        choice = key_idx(block_max(x.local_max(), sm, 0));
+    } else {
+        const uint2 key = make_uint2((uint32_t)st.seed[s], (uint32_t)(st.seed[s] >> 32));
+        const uint4 r = philox(make_uint4((uint32_t)step, (uint32_t)((uint64_t)step >> 32), 0u, 0x5a17u), key);
+        if (top_k > 0) {
+            const int nc = select_bins(x, sm, min(top_k, m), true);
+            const float ej = tid < nc ? __expf(sm.cand_v[tid] - sm.cand_v[0]) : 0.f;
+            float z;
+            const float cj = block_scan(ej, z, sm);
+            const bool keep = tid < nc && (tid == 0 || cj - ej < top_p * z);
+            float kept;
+            (void)block_scan(keep ? ej : 0.f, kept, sm);
+            const float target = u01(r.x) * kept;
+            if (tid == 0) sm.pick[1] = 0;
+            __syncthreads();
+            if (keep && cj <= target) atomicAdd(&sm.pick[1], 1);
+            __syncthreads();
+            float f;
+            (void)block_scan(keep ? 1.f : 0.f, f, sm);
+            const int nk = (int)f;
+            if (tid == 0) sm.pick[0] = nk > 0 ? sm.cand_i[min(sm.pick[1], nk - 1)] : 0;
+            __syncthreads();
+            choice = sm.pick[0];
+        } else {
+            const unsigned long long k = block_max(x.local_max(), sm, 0);
+            int i0, i1;
+            draw_full(x, sm, key_val(k), -1, u01(r.x), 0.f, i0, i1);
+            choice = i0 >= 0 ? i0 : key_idx(k);
+        }
+    }
+    // every thread holds the same choice (it came out of LDS after a barrier), and every read of the slot's state lies before that barrier
+    const long id = lo + min(max(choice, 0), m - 1);
+    if (tid == 0) {
+        if (step >= 0 && step < st.seq_ld) st.seq[(long)s * st.seq_ld + step] = id;
+        st.ids[s] = id;
+        st.step[s] = step + 1;
+        st.live[s] = id != st.eos && step + 1 < st.limit[s];
+    }
+    if (st.emb) {
+        const uint16_t *src = st.emb + id * st.D;
+        uint16_t *dst = st.x + (long)s * st.D;
+        for (int d = tid * 8; d < st.D; d += kSmpThreads * 8) *reinterpret_cast<uint4 *>(dst + d) = *reinterpret_cast<const uint4 *>(src + d);
+    }
+}
+
 // ---- CosyVoice streaming step: draw + bookkeeping --------------------------------------------------------------------------------
 template <int EPT>
 __global__ __launch_bounds__(kSmpThreads) void ras_step_kernel(int V, const float *__restrict__ logits, long *__restrict__ tok,
@@ -695,6 +794,21 @@ int sample_rows_f32(int rows, int nseg, const float *logits, long ld, const int 
     else
         sample_rows_kernel<kEptL><<<grid, block, 0, st>>>(nseg, logits, ld, seg_off, seg_len, allow_lo, allow_hi, suppress, nsuppress, do_sample,
                                                           top_k, top_p, it, key, step, out, tail, min_id, min_until);
+    return (int)hipGetLastError();
+}
+
+int sample_slots_f32(int rows, const float *logits, long ld, const int *row_slot, const int *allow_lo, const int *allow_hi,
+                     const int *suppress, int nsuppress, int max_domain, const void *st_, hipStream_t stream) {
+    const SlotState st = *(const SlotState *)st_;
+    if (max_domain > kSmpMaxN || nsuppress > 256 || st.top_k_max < 0 || st.top_k_max > 64 || (st.emb && st.D % 8 != 0)) return -4;
+    (void)hipGetLastError();
+    const dim3 grid(rows), block(kSmpThreads);
+    if (max_domain <= kEptS * kSmpThreads)
+        sample_slots_kernel<kEptS><<<grid, block, 0, stream>>>(logits, ld, row_slot, allow_lo, allow_hi, suppress, nsuppress, max_domain, st);
+    else if (max_domain <= kEptM * kSmpThreads)
+        sample_slots_kernel<kEptM><<<grid, block, 0, stream>>>(logits, ld, row_slot, allow_lo, allow_hi, suppress, nsuppress, max_domain, st);
+    else
+        sample_slots_kernel<kEptL><<<grid, block, 0, stream>>>(logits, ld, row_slot, allow_lo, allow_hi, suppress, nsuppress, max_domain, st);
     return (int)hipGetLastError();
 }
 
