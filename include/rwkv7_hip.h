@@ -363,7 +363,8 @@ int rwkv7_wkv_chunk_bwd_out_z_bf16(int B, int T, int H, const void *w, const voi
  *   the next and zeroes it across a row boundary, and the decay gradient of a row's last chunk drops its rowsum(E * H_C) term.  With
  *   a non-zero h0 or dhT its dw, dq, dk, dv, da, db are therefore valid only if the row starts AND ends with one whole identity
  *   chunk -- 32 steps with w = -1e4 (exp(w) underflows to 0: decay exactly 1) and q = k = v = a = b = 0 -- whose gradients the
- *   caller drops (the identity chunks pass h0 and dhT through bit for bit).  rwkvtts_amd/ops.py, wkv7_state_chunked, does this. ---- */
+ *   caller drops (the identity chunks pass h0 and dhT through bit for bit).  rwkvtts_amd/ops.py, _WkvStateChunked (with the framing
+ *   wkv7_state_chunked chooses), does this.  Both entries are the packed ones below with seq_chunk_off = NULL, nseq = 0. ---- */
 int rwkv7_wkv_chunk_fwd_state_bf16(int B, int T, int H, const void *w, const void *q, const void *k, const void *v,
                                    const void *a, const void *b, const float *tinv, void *y, float *sa, void *hs,
                                    const float *h0, float *hT, rwkv7_stream_t stream);

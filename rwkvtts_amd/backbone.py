@@ -170,6 +170,11 @@ class Cache:
         return Cache([LayerState(s.att_x_prev.detach().clone(), s.att_kv.detach().clone(), s.ffn_x_prev.detach().clone())
                       for s in self.states], self.seen_tokens, self.differentiable)
 
+    @property
+    def requires_grad(self):
+        """Whether a forward trains through this cache (in grad mode): it is marked differentiable or a state tensor requires grad."""
+        return self.differentiable or any(t.requires_grad for s in self.states for t in (s.att_x_prev, s.att_kv, s.ffn_x_prev))
+
     def __len__(self):
         return len(self.states)
 
@@ -224,6 +229,28 @@ def _row_align(n):
 PACKED_NATIVE = True
 
 
+def _packed_layout(cu_seqlens, total, t_al):
+    """The chunk-aligned row of t_al positions (RWKV7Model._forward_packed) for the packed row [1, total, D] that `cu_seqlens` cuts
+    into sequences, with tensor ops on cu_seqlens' device: every non-empty sequence starts on a chunk boundary and is followed by
+    1 .. 32 masked positions.  Returns (dest, seq_off):
+      dest     int32 [total]: the aligned row of every packed position; -1 outside [cu_seqlens[0], cu_seqlens[-1])
+      seq_off  int32 [nseq + 2]: the sequences' chunk ranges (empty for an empty sequence), then an all-masked pseudo-sequence up to
+               t_al (empty when the sequences fill the row), so no chunk is left to uninitialised memory."""
+    C = ops.CHUNK_T
+    nseq = cu_seqlens.numel() - 1
+    cu = cu_seqlens.to(torch.int64)
+    lens = cu[1:] - cu[:-1]
+    alen = torch.where(lens > 0, (torch.div(lens, C, rounding_mode="floor") + 1) * C, torch.zeros_like(lens))
+    ends = torch.cumsum(alen, 0)
+    starts = ends - alen
+    j = torch.arange(total, device=cu.device)
+    sq = torch.searchsorted(cu[1:].contiguous(), j, right=True).clamp_(max=nseq - 1)
+    valid = (j >= cu[0]) & (j < cu[-1])
+    dest = torch.where(valid, starts[sq] + (j - cu[sq]), torch.full_like(j, -1))
+    seq_off = torch.cat([starts.new_zeros(1), ends, ends.new_full((1,), t_al)])
+    return dest.to(torch.int32), torch.div(seq_off, C, rounding_mode="floor").to(torch.int32)
+
+
 class _PackedState:
     """What the layers of RWKV7Model._forward_packed_state share: the aligned row's sequence chunks, the rows of each non-empty
     sequence's first and last token, and the masked rows (identity steps of the scan)."""
@@ -261,23 +288,30 @@ class _PackedState:
             return torch.where(self.keep, w, ops.W_PAD)
         return w.masked_fill_(~self.keep, ops.W_PAD)
 
-    @staticmethod
-    def store(state, name, new, diff):
-        if diff:
-            setattr(state, name, new)
-        else:
-            getattr(state, name).copy_(new.detach())   # in place: the addresses stay (captured decode graphs, DecodeStep)
 
-    def store_last(self, state, name, x, diff):
-        """The token-shift predecessor after each non-empty sequence: x at its last row (empty sequences keep theirs)."""
-        if not self.any:
-            return
-        old = getattr(state, name)
-        rows = x[0].index_select(0, self.last).to(old.dtype)
-        if diff:
-            setattr(state, name, old.index_copy(0, self.ne, rows))
-        else:
-            old.index_copy_(0, self.ne, rows.detach())
+def _store(state, name, new, diff, rows=None):
+    """Write a carried state back (rows: only those rows of it).  diff (training through the state): the field is REBOUND to a
+    tensor that carries its graph -- an in-place update would overwrite a tensor the tape still needs.  Otherwise it is updated in
+    place: the state tensors keep their addresses (captured decode graphs and DecodeStep replay on them)."""
+    old = getattr(state, name)
+    if diff:
+        setattr(state, name, new if rows is None else old.index_copy(0, rows, new))
+    elif rows is None:
+        old.copy_(new.detach())
+    else:
+        old.index_copy_(0, rows, new.detach())
+
+
+def _store_last(state, name, x, packed: _PackedState, diff):
+    """The token-shift predecessor after each non-empty sequence of a packed row: x at its last row (empty sequences keep theirs)."""
+    if packed.any:
+        _store(state, name, x[0].index_select(0, packed.last).to(getattr(state, name).dtype), diff, packed.ne)
+
+
+def _last_token(x, mask):
+    """The token-shift predecessor after a plain row [B,T,D]: its last position, masked."""
+    last = x[:, -1]
+    return last * mask[:, -1] if mask is not None else last
 
 
 class RWKV7Attention(nn.Module):
@@ -434,19 +468,15 @@ class RWKV7Attention(nn.Module):
             # there; w = 0 would decay the state by e^-1 per row)
             w = packed.identity_w(w)
             y, hT = ops.wkv7_state_chunked_seq(state.att_kv, r.contiguous(), w, k2, v2, a_in, b_in, packed.seq_off, packed.nseq)
-            packed.store(state, "att_kv", hT, diff_state)
-            packed.store_last(state, "att_x_prev", x, diff_state)
-        elif diff_state:
-            # training through the carried state: the scan and the new state are on the tape; the fields are REBOUND (the no-grad
-            # path's in-place updates would overwrite tensors the tape still needs)
-            y, state.att_kv = ops.wkv7_state_chunked(state.att_kv, r.contiguous(), w, k2, v2, a_in, b_in)
-            last = x[:, -1]
-            state.att_x_prev = last * mask[:, -1] if mask is not None else last
+            _store(state, "att_kv", hT, diff_state)
+            _store_last(state, "att_x_prev", x, packed, diff_state)
+        elif diff_state:   # training through the carried state: the scan and the new state are on the tape
+            y, hT = ops.wkv7_state_chunked(state.att_kv, r.contiguous(), w, k2, v2, a_in, b_in)
+            _store(state, "att_kv", hT, True)
+            _store(state, "att_x_prev", _last_token(x, mask), True)
         else:
-            y = ops.RWKV7_BATCH_OP(state.att_kv, r.contiguous(), w, k2, v2, a_in, b_in)
-            last = x[:, -1].detach()
-            # in place: the state tensors keep their addresses (hipGraph-captured decode steps replay on them)
-            state.att_x_prev.copy_(last * mask[:, -1] if mask is not None else last)
+            y = ops.RWKV7_BATCH_OP(state.att_kv, r.contiguous(), w, k2, v2, a_in, b_in)   # the WKV state is updated in place
+            _store(state, "att_x_prev", _last_token(x, mask), False)
         y = fused.tmix_post(y, r, k2, v2, g, self.g_norm.weight, self.g_norm.bias, self.r_k, H, self.g_norm.eps)
         return self.o_proj(y), v_first
 
@@ -463,16 +493,11 @@ class RWKV7FeedForward(nn.Module):
     def forward(self, x, mask, state: Optional[LayerState] = None, diff_state=False, packed: Optional["_PackedState"] = None):
         if packed is not None:   # packed row, one state per sequence (see RWKV7Attention.forward)
             kx = packed.carry((fused.token_shift_mix1(x, None, self.x_k, mask),), x, state.ffn_x_prev, (self.x_k,))[0]
-            packed.store_last(state, "ffn_x_prev", x, diff_state)
+            _store_last(state, "ffn_x_prev", x, packed, diff_state)
             return self.forward_mixed(kx)
-        x_prev = None if state is None else state.ffn_x_prev
-        kx = fused.token_shift_mix1(x, x_prev, self.x_k, mask)
-        if diff_state:   # rebound with its graph (see RWKV7Attention.forward_mixed)
-            last = x[:, -1]
-            state.ffn_x_prev = last * mask[:, -1] if mask is not None else last
-        elif state is not None:
-            last = x[:, -1].detach()
-            state.ffn_x_prev.copy_(last * mask[:, -1] if mask is not None else last)
+        kx = fused.token_shift_mix1(x, None if state is None else state.ffn_x_prev, self.x_k, mask)
+        if state is not None:
+            _store(state, "ffn_x_prev", _last_token(x, mask), diff_state)
         return self.forward_mixed(kx)
 
     def forward_mixed(self, kx):
@@ -635,8 +660,7 @@ class RWKV7Model(nn.Module):
         """Whether a stateful forward trains through the cache: grad mode on, and the cache is marked differentiable or one of
         its state tensors requires grad.  Everything else (prefill, decode, generate: all under no_grad / inference_mode) keeps
         the in-place no-grad path."""
-        if not torch.is_grad_enabled() or not (getattr(cache, "differentiable", False) or
-                                               any(t.requires_grad for s in cache.states for t in (s.att_x_prev, s.att_kv, s.ffn_x_prev))):
+        if not torch.is_grad_enabled() or not cache.requires_grad:
             return False
         if x.dtype != torch.bfloat16:
             raise ValueError(f"training through a differentiable cache needs a bf16 model (the chunked backward is bf16 only), got {x.dtype}")
@@ -645,55 +669,20 @@ class RWKV7Model(nn.Module):
     def _run_layers(self, x, mask, cache: Optional[Cache], seq_start=None, diff_state=False, packed=None):
         v_first = delta = None
         for i, layer in enumerate(self.layers):
-            st = cache[i] if cache is not None else None
             if self.gradient_checkpointing and self.training and cache is None:
                 x, delta, v_first = torch.utils.checkpoint.checkpoint(layer, x, delta, mask, v_first, None, seq_start,
                                                                       use_reentrant=False)
-            elif packed is not None:
-                x, delta, v_first = layer(x, delta, mask, v_first, st, None, diff_state=diff_state, packed=packed)
-            elif diff_state:
-                x, delta, v_first = layer(x, delta, mask, v_first, st, seq_start, diff_state=True)
             else:
-                x, delta, v_first = layer(x, delta, mask, v_first, st, seq_start)
+                x, delta, v_first = layer(x, delta, mask, v_first, None if cache is None else cache[i], seq_start,
+                                          diff_state=diff_state, packed=packed)
         return fused.add_layer_norm(x, delta, self.norm)[1] if delta is not None else fused.layer_norm(x, self.norm)
 
-    def _forward_packed_device(self, x, cu_seqlens):   # noqa: D401
-        """The packed path for a `cu_seqlens` that lives on the DEVICE (as fla consumes it; train_spark_rwkv7speech.py:238-239): no
-        host read-back.  The 32-aligned layout of `_forward_packed` is computed with tensor ops from the cumulative lengths; only its
-        SIZE must be known on the host, and that is bounded by shapes alone: every non-empty sequence grows by at most 32 positions, so
-        the aligned row has at most total + 32 nseq positions (rounded up to a chunk).  Chunks between the last sequence and that bound
-        form one extra all-masked pseudo-sequence, so no chunk is left to uninitialised memory.  Empty sequences own empty chunk ranges
-        (the kernels return at once); positions outside [cu[0], cu[-1]) come back as zeros."""
-        C = ops.CHUNK_T
-        total, D = x.shape[1], x.shape[-1]
-        nseq = cu_seqlens.numel() - 1
-        t_max = _row_align(total + C * nseq)
-        cu = cu_seqlens.to(torch.int64)
-        lens = cu[1:] - cu[:-1]
-        alen = torch.where(lens > 0, (torch.div(lens, C, rounding_mode="floor") + 1) * C, torch.zeros_like(lens))
-        ends = torch.cumsum(alen, 0)
-        starts = ends - alen
-        j = torch.arange(total, device=x.device)
-        sq = torch.searchsorted(cu[1:].contiguous(), j, right=True).clamp_(max=nseq - 1)
-        valid = (j >= cu[0]) & (j < cu[-1])
-        dest = torch.where(valid, starts[sq] + (j - cu[sq]), torch.full_like(j, -1))        # aligned row of every packed position; -1: unowned
-        seq_off = torch.cat([starts.new_zeros(1), ends, ends.new_full((1,), t_max)])
-        seq_off = torch.div(seq_off, C, rounding_mode="floor").to(torch.int32)                 # [nseq + 2]: the sequences + the masked tail
-        return self._run_packed_aligned(x, dest.to(torch.int32), t_max, seq_off)
-
-    def _run_packed_aligned(self, x, dest, t_al, seq_off):
-        """x [1, total, D] -> the 32-aligned row of t_al positions (dest int32 [total]: the aligned row of every packed position, -1 for
-        positions that belong to no sequence), the layers, and back.  Both re-layouts and both of their gradients are row gathers
-        (fused.gather_rows: the maps are injective)."""
-        total = x.shape[1]
-        j = torch.arange(total, device=x.device, dtype=torch.int32)
-        src_of = torch.full((t_al + 1,), -1, dtype=torch.int32, device=x.device)       # packed position held by every aligned row (-1: masked)
-        src_of = src_of.scatter(0, torch.where(dest >= 0, dest, torch.full_like(dest, t_al)).long(), j)[:t_al].contiguous()
-        x_al = fused.gather_rows(x[0], src_of, dest)
-        mask = (src_of >= 0).to(x.dtype).unsqueeze(-1)
-        out = self._run_layers(x_al.unsqueeze(0), mask.unsqueeze(0), None, seq_off)
-        packed = fused.gather_rows(out[0], dest, src_of)
-        return ModelOutput(last_hidden_state=packed.unsqueeze(0), past_key_values=None)
+    def _run_packed_aligned(self, x, cu_seqlens, t_al):
+        """x [1, total, D] -> the 32-aligned row of t_al positions (_packed_layout), the layers, and back (ops.RowMap)."""
+        dest, seq_off = _packed_layout(cu_seqlens, x.shape[1], t_al)
+        rows = ops.RowMap(dest, t_al, x.device)
+        out = self._run_layers(rows.to_aligned(x), rows.keep.to(x.dtype), None, seq_off.to(x.device, non_blocking=True))
+        return ModelOutput(last_hidden_state=rows.to_packed(out), past_key_values=None)
 
     def _forward_packed_state(self, x, cu_seqlens, cache: Cache):
         """A packed row [1, total, D] (cu_seqlens, N sequences) that carries state: sequence i starts from row i of `cache` (its WKV
@@ -728,17 +717,12 @@ class RWKV7Model(nn.Module):
         cache.seen_tokens += cu[-1] - cu[0]
         if lay.t_al == 0:
             return ModelOutput(last_hidden_state=x.new_zeros(x.shape), past_key_values=cache)
-        dev = x.device
         dest = torch.full((total,), -1, dtype=torch.int32)
         dest[cu[0]:cu[-1]] = lay.dest
-        src_of = torch.full((lay.t_al,), -1, dtype=torch.int32)
-        src_of[lay.dest.long()] = torch.arange(cu[0], cu[-1], dtype=torch.int32)
-        dest, src_of = dest.to(dev, non_blocking=True), src_of.to(dev, non_blocking=True)
-        x_al = fused.gather_rows(x[0], src_of, dest)
-        keep = (src_of >= 0).view(1, -1, 1)
-        packed = _PackedState(lay, keep, dev)
-        out = self._run_layers(x_al.unsqueeze(0), keep.to(x.dtype), cache, diff_state=diff, packed=packed)
-        return ModelOutput(last_hidden_state=fused.gather_rows(out[0], dest, src_of).unsqueeze(0), past_key_values=cache)
+        rows = ops.RowMap(dest, lay.t_al, x.device)
+        packed = _PackedState(lay, rows.keep, x.device)
+        out = self._run_layers(rows.to_aligned(x), rows.keep.to(x.dtype), cache, diff_state=diff, packed=packed)
+        return ModelOutput(last_hidden_state=rows.to_packed(out), past_key_values=cache)
 
     def _forward_packed_rows(self, x, cu_seqlens, cache: Cache, cache_rows):
         """`_forward_packed_state` into chosen rows of a larger cache: sequence i starts from and ends in cache row cache_rows[i] (N
@@ -748,8 +732,7 @@ class RWKV7Model(nn.Module):
         rows are read on the host (one read-back for a device tensor)."""
         if cu_seqlens is None or cache is None or len(cache) == 0:
             raise ValueError("cache_rows needs cu_seqlens and past_key_values")
-        if getattr(cache, "differentiable", False) or any(t.requires_grad for s in cache.states
-                                                          for t in (s.att_x_prev, s.att_kv, s.ffn_x_prev)):
+        if cache.requires_grad:
             raise ValueError("cache_rows updates the cache in place: a differentiable cache is not supported")
         rows = [int(r) for r in torch.as_tensor(cache_rows).reshape(-1).tolist()]
         n_rows, N = cache[0].att_kv.shape[0], cu_seqlens.numel() - 1
@@ -784,28 +767,15 @@ class RWKV7Model(nn.Module):
         batch, run, pack again."""
         assert x.shape[0] == 1, "cu_seqlens expects a packed [1, total, D] row"
         native = (PACKED_NATIVE and x.is_cuda and x.dtype == torch.bfloat16 and fused.CHUNKED_WKV_FWD and fused.CHUNKED_WKV_BWD)
+        C, total = ops.CHUNK_T, x.shape[1]
         if native and cu_seqlens.is_cuda:
-            return self._forward_packed_device(x, cu_seqlens)
+            # a DEVICE cu_seqlens (as fla consumes it; train_spark_rwkv7speech.py:238-239): no host read-back.  The row size is bounded
+            # by shapes alone: every non-empty sequence grows by at most 32 positions
+            return self._run_packed_aligned(x, cu_seqlens, _row_align(total + C * (cu_seqlens.numel() - 1)))
         cu = cu_seqlens.tolist()      # a HOST tensor (what the reference's collators build: spark_dataset.py:150-160): no device sync
         lens = [b - a for a, b in zip(cu[:-1], cu[1:])]
-        if native and sum(lens) > 0:
-            C = ops.CHUNK_T
-            D = x.shape[-1]
-            starts, t_al = [], 0
-            for n in lens:
-                starts.append(t_al)
-                if n > 0:
-                    t_al += (n // C + 1) * C      # >= n + 1, multiple of 32
-            dest = torch.full((x.shape[1],), -1, dtype=torch.int32)
-            for s_, n, lo in zip(starts, lens, cu[:-1]):
-                if n > 0:
-                    dest[lo:lo + n] = torch.arange(s_, s_ + n, dtype=torch.int32)
-            seq_chunks = [s_ // C for s_, n in zip(starts, lens) if n > 0] + [t_al // C]
-            if _row_align(t_al) > t_al:      # an all-masked pseudo-sequence up to the next multiple of 256 rows (the fused GEMM paths' tile grid)
-                t_al = _row_align(t_al)
-                seq_chunks.append(t_al // C)
-            seq_off = torch.tensor(seq_chunks, dtype=torch.int32)
-            return self._run_packed_aligned(x, dest.to(x.device, non_blocking=True), t_al, seq_off.to(x.device, non_blocking=True))
+        if native and sum(lens) > 0:   # the exact row size
+            return self._run_packed_aligned(x, cu_seqlens, _row_align(sum((n // C + 1) * C for n in lens if n > 0)))
         seqs = list(x[0, :cu[-1]].split(lens))
         xb = torch.nn.utils.rnn.pad_sequence(seqs, batch_first=True)
         mask = torch.zeros(len(lens), xb.shape[1], dtype=torch.long, device=x.device)

@@ -39,10 +39,6 @@ int adamw_step(long, float *, const void *, float *, float *, void *, const uint
 int lora32_bf16(int, int, int, int, int, const void *, const void *, const void *, const void *, void *, hipStream_t);
 int chunk_bseq_bf16(int, int, int, const void *, const void *, const void *, const void *, const void *, const float *, void *,
                     float *, const int *, int, hipStream_t);
-int chunk_bseq_state_bf16(int, int, int, const void *, const void *, const void *, const void *, const void *, const float *, void *,
-                          float *, const float *, float *, hipStream_t);
-int chunk_fwd9_state_bf16(int, int, int, const void *, const void *, const void *, const void *, const void *, const void *,
-                          const float *, void *, float *, void *, const float *, float *, hipStream_t);
 int chunk_bseq_state_seq_bf16(int, int, int, const void *, const void *, const void *, const void *, const void *, const float *,
                               void *, float *, const int *, int, const float *, float *, hipStream_t);
 int chunk_fwd9_state_seq_bf16(int, int, int, const void *, const void *, const void *, const void *, const void *, const void *,
@@ -472,23 +468,8 @@ int rwkv7_wkv_chunk_bseq_bf16(int B, int T, int H, const void *w, const void *q,
     if (T % 32 != 0) return RWKV7_ECHUNK;
     return rwkv7::chunk_bseq_bf16(B, T, H, w, q, a, b, dy, tinv, e_vk, z, seq_chunk_off, nseq, (hipStream_t)stream);
 }
-// the two sequential kernels with a carried state (plain rows): h0 / hT / dhT / dh0 fp32 [B,H,64,64], each may be NULL
-int rwkv7_wkv_chunk_fwd_state_bf16(int B, int T, int H, const void *w, const void *q, const void *k, const void *v,
-                                   const void *a, const void *b, const float *tinv, void *y, float *sa, void *hs,
-                                   const float *h0, float *hT, rwkv7_stream_t stream) {
-    if (B <= 0 || T <= 0 || H <= 0 || any_null({w, q, k, v, a, b, (const void *)tinv, y})) return RWKV7_EINVAL;
-    if ((sa == nullptr) != (hs == nullptr)) return RWKV7_EINVAL;
-    if (T % 32 != 0) return RWKV7_ECHUNK;
-    return rwkv7::chunk_fwd9_state_bf16(B, T, H, w, q, k, v, a, b, tinv, y, sa, hs, h0, hT, (hipStream_t)stream);
-}
-int rwkv7_wkv_chunk_bseq_state_bf16(int B, int T, int H, const void *w, const void *q, const void *a, const void *b,
-                                    const void *dy, const float *tinv, void *e_vk, float *z,
-                                    const float *dhT, float *dh0, rwkv7_stream_t stream) {
-    if (B <= 0 || T <= 0 || H <= 0 || any_null({w, q, a, b, dy, (const void *)tinv, (const void *)e_vk})) return RWKV7_EINVAL;
-    if (T % 32 != 0) return RWKV7_ECHUNK;
-    return rwkv7::chunk_bseq_state_bf16(B, T, H, w, q, a, b, dy, tinv, e_vk, z, dhT, dh0, (hipStream_t)stream);
-}
-// the same on packed rows (seq_chunk_off / nseq as rwkv7_wkv_chunk_fwd_seq_bf16): one state per sequence, [nseq,H,64,64]
+// the two sequential kernels with a carried state, one per sequence of a packed row (seq_chunk_off / nseq as
+// rwkv7_wkv_chunk_fwd_seq_bf16): h0 / hT / dhT / dh0 fp32 [nseq,H,64,64], each may be NULL
 int rwkv7_wkv_chunk_fwd_state_seq_bf16(int B, int T, int H, const void *w, const void *q, const void *k, const void *v,
                                        const void *a, const void *b, const float *tinv, void *y, float *sa, void *hs,
                                        const int *seq_chunk_off, int nseq, const float *h0, float *hT, rwkv7_stream_t stream) {
@@ -505,6 +486,17 @@ int rwkv7_wkv_chunk_bseq_state_seq_bf16(int B, int T, int H, const void *w, cons
     if ((seq_chunk_off == nullptr) != (nseq <= 0)) return RWKV7_EINVAL;
     if (T % 32 != 0) return RWKV7_ECHUNK;
     return rwkv7::chunk_bseq_state_seq_bf16(B, T, H, w, q, a, b, dy, tinv, e_vk, z, seq_chunk_off, nseq, dhT, dh0, (hipStream_t)stream);
+}
+// plain rows (one state per row, [B,H,64,64]): the packed entries with seq_chunk_off = NULL, nseq = 0
+int rwkv7_wkv_chunk_fwd_state_bf16(int B, int T, int H, const void *w, const void *q, const void *k, const void *v,
+                                   const void *a, const void *b, const float *tinv, void *y, float *sa, void *hs,
+                                   const float *h0, float *hT, rwkv7_stream_t stream) {
+    return rwkv7_wkv_chunk_fwd_state_seq_bf16(B, T, H, w, q, k, v, a, b, tinv, y, sa, hs, nullptr, 0, h0, hT, stream);
+}
+int rwkv7_wkv_chunk_bseq_state_bf16(int B, int T, int H, const void *w, const void *q, const void *a, const void *b,
+                                    const void *dy, const float *tinv, void *e_vk, float *z,
+                                    const float *dhT, float *dh0, rwkv7_stream_t stream) {
+    return rwkv7_wkv_chunk_bseq_state_seq_bf16(B, T, H, w, q, a, b, dy, tinv, e_vk, z, nullptr, 0, dhT, dh0, stream);
 }
 int rwkv7_wkv_chunk_bwd_out_z_bf16(int B, int T, int H, const void *w, const void *q, const void *k, const void *v,
                                    const void *a, const void *b, const void *dy, const void *hs, const float *sa,

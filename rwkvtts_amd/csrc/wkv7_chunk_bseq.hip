@@ -372,14 +372,8 @@ int chunk_bseq_bf16(int B, int T_, int H, const void *w, const void *q, const vo
     return launch_bseq<false>(B, T_, H, w, q, a, b, dy, tinv, e_vk, z, seq_off, nseq, nullptr, nullptr, st);
 }
 
-// plain rows with a carried state (dhT / dh0 may each be NULL; both NULL: the stateless kernel above, bit for bit)
-int chunk_bseq_state_bf16(int B, int T_, int H, const void *w, const void *q, const void *a, const void *b, const void *dy,
-                          const float *tinv, void *e_vk, float *z, const float *dhT, float *dh0, hipStream_t st) {
-    if (!dhT && !dh0) return chunk_bseq_bf16(B, T_, H, w, q, a, b, dy, tinv, e_vk, z, nullptr, 0, st);
-    return launch_bseq<true>(B, T_, H, w, q, a, b, dy, tinv, e_vk, z, nullptr, 0, dhT, dh0, st);
-}
-
-// packed rows with one carried state per sequence (dhT / dh0 [nseq,H,64,64], each may be NULL; both NULL: the stateless packed kernel)
+// a carried state per row (seq_off = NULL) or per sequence of a packed row (dhT / dh0 [B or nseq,H,64,64], each may be NULL;
+// both NULL: the stateless kernel above, bit for bit)
 int chunk_bseq_state_seq_bf16(int B, int T_, int H, const void *w, const void *q, const void *a, const void *b, const void *dy,
                               const float *tinv, void *e_vk, float *z, const int *seq_off, int nseq, const float *dhT, float *dh0,
                               hipStream_t st) {

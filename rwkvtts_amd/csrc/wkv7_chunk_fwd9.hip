@@ -436,14 +436,8 @@ int chunk_fwd9_bf16(int B, int T_, int H, const void *w, const void *q, const vo
     return launch_fwd9<false>(sa && hs, B, T_, H, w, q, k, v, a, b, tinv, y, sa, hs, seq_off, nseq, nullptr, nullptr, st);
 }
 
-// plain rows with a carried state (h0 / hT may each be NULL; both NULL: the stateless kernel above, bit for bit)
-int chunk_fwd9_state_bf16(int B, int T_, int H, const void *w, const void *q, const void *k, const void *v, const void *a, const void *b,
-                          const float *tinv, void *y, float *sa, void *hs, const float *h0, float *hT, hipStream_t st) {
-    if (!h0 && !hT) return chunk_fwd9_bf16(B, T_, H, w, q, k, v, a, b, tinv, y, sa, hs, nullptr, 0, st);
-    return launch_fwd9<true>(sa && hs, B, T_, H, w, q, k, v, a, b, tinv, y, sa, hs, nullptr, 0, h0, hT, st);
-}
-
-// packed rows with one carried state per sequence (h0 / hT [nseq,H,64,64], each may be NULL; both NULL: the stateless packed kernel)
+// a carried state per row (seq_off = NULL) or per sequence of a packed row (h0 / hT [B or nseq,H,64,64], each may be NULL;
+// both NULL: the stateless kernel above, bit for bit)
 int chunk_fwd9_state_seq_bf16(int B, int T_, int H, const void *w, const void *q, const void *k, const void *v, const void *a,
                               const void *b, const float *tinv, void *y, float *sa, void *hs, const int *seq_off, int nseq,
                               const float *h0, float *hT, hipStream_t st) {

@@ -19,7 +19,7 @@ import ctypes
 
 import torch
 
-from . import _lib
+from . import _lib, fused
 
 HEAD_SIZE = 64
 CHUNK_LEN = 16
@@ -312,11 +312,18 @@ def wkv7_chunk_prep(w, a, b):
     return tinv
 
 
-def wkv7_chunk_forward(w, q, k, v, a, b, save=True, seq_off=None):
-    """Chunked forward.  Returns y, and (tinv, sa, hs) when save (what the chunked backward consumes; hs = the state at the
-    start of every chunk as q15 records, see q15_decode).
-    seq_off: packed rows -- int32 [nseq + 1] device tensor of cumulative 32-step chunk counts over the [B][T/32] chunk
-    space; sequence s owns chunks seq_off[s] .. seq_off[s+1] - 1 and starts from the zero state."""
+def _nseq(seq_off):
+    """The sequence count of a packed row's seq_off (0 for plain rows, seq_off = None)."""
+    if seq_off is None:
+        return 0
+    if seq_off.dtype != torch.int32 or seq_off.dim() != 1 or seq_off.numel() < 2 or not seq_off.is_contiguous() or not seq_off.is_cuda:
+        raise TypeError("seq_off must be a contiguous int32 [nseq + 1] device tensor")
+    return seq_off.numel() - 1
+
+
+def _chunk_fwd(w, q, k, v, a, b, save, seq_off, nseq, h0=None):
+    """prep + the sequential chunked forward on [B,T,H,64] rows: (y, tinv, sa, hs, hT), sa = hs = None unless save.
+    h0 (fp32 [B or nseq,H,64,64]): start from it on the carried-state entry, which also returns the end states hT (else None)."""
     B, T, H, C = w.shape
     sfx = _sfx([w, q, k, v, a, b], "wkv7_chunk_forward")
     if T % CHUNK_T != 0:
@@ -325,20 +332,47 @@ def wkv7_chunk_forward(w, q, k, v, a, b, save=True, seq_off=None):
     y = torch.empty_like(v)
     sa = torch.empty(B, T, H, C, dtype=torch.float32, device=w.device) if save else None
     hs = torch.empty(B, H, T // CHUNK_T, Q15_REC, dtype=torch.int16, device=w.device) if save else None
-    with torch.cuda.device_of(w), _timed("wkv7c_fwd", w):
-        args = (B, T, H, _p(w), _p(q), _p(k), _p(v), _p(a), _p(b), _p(tinv), _p(y),
-                None if sa is None else _p(sa), None if hs is None else _p(hs), *_seq_args(seq_off))
-        rc = getattr(_lib.lib(), "rwkv7_wkv_chunk_fwd_seq_" + sfx)(*args, _stream(w))
+    hT = None if h0 is None else torch.empty(nseq if seq_off is not None else B, H, C, C, dtype=torch.float32, device=w.device)
+    args = (B, T, H, _p(w), _p(q), _p(k), _p(v), _p(a), _p(b), _p(tinv), _p(y), _p(sa), _p(hs), _p(seq_off), nseq)
+    with torch.cuda.device_of(w), _timed("wkv7c_fwd" if h0 is None else "wkv7c_fwd_state", w):
+        if h0 is None:
+            rc = getattr(_lib.lib(), "rwkv7_wkv_chunk_fwd_seq_" + sfx)(*args, _stream(w))
+        else:
+            rc = _lib.lib().rwkv7_wkv_chunk_fwd_state_seq_bf16(*args, _p(h0), _p(hT), _stream(w))
     _lib.check(rc, "wkv7_chunk_forward")
+    return y, tinv, sa, hs, hT
+
+
+def wkv7_chunk_forward(w, q, k, v, a, b, save=True, seq_off=None):
+    """Chunked forward.  Returns y, and (tinv, sa, hs) when save (what the chunked backward consumes; hs = the state at the
+    start of every chunk as q15 records, see q15_decode).
+    seq_off: packed rows -- int32 [nseq + 1] device tensor of cumulative 32-step chunk counts over the [B][T/32] chunk
+    space; sequence s owns chunks seq_off[s] .. seq_off[s+1] - 1 and starts from the zero state."""
+    y, tinv, sa, hs, _ = _chunk_fwd(w, q, k, v, a, b, save, seq_off, _nseq(seq_off))
     return (y, tinv, sa, hs) if save else y
 
 
-def _seq_args(seq_off):
-    if seq_off is None:
-        return None, 0
-    if seq_off.dtype != torch.int32 or seq_off.dim() != 1 or seq_off.numel() < 2 or not seq_off.is_contiguous() or not seq_off.is_cuda:
-        raise TypeError("seq_off must be a contiguous int32 [nseq + 1] device tensor")
-    return _p(seq_off), seq_off.numel() - 1
+def _bseq(w, q, a, b, dy, tinv, seq_off, nseq, want_z, state=None):
+    """The adjoint-state recurrence on [B,T,H,64] rows: (e_vk, z), z (fp32 [B,T,H,64]) only with want_z.
+    state = (dhT, dh0), fp32 [B or nseq,H,64,64], each may be None: the carried-state entry (dh0 is written)."""
+    B, T, H, C = w.shape
+    if w.dtype != torch.bfloat16:
+        raise TypeError("the chunked backward is bf16 only")
+    if T % CHUNK_T != 0:
+        raise ValueError(f"chunked WKV7 needs T % {CHUNK_T} == 0, got T={T}")
+    e_vk = torch.empty(B, H, T // CHUNK_T, Q15_REC, dtype=torch.int16, device=w.device)
+    # stateless packed rows may leave positions behind the last sequence untouched: zeros there (the gradient kernel reads every
+    # chunk).  The carried-state layouts give every chunk of the row to a sequence.
+    zeroed = seq_off is not None and state is None
+    z = (torch.zeros if zeroed else torch.empty)(B, T, H, C, dtype=torch.float32, device=w.device) if want_z else None
+    args = (B, T, H, _p(w), _p(q), _p(a), _p(b), _p(dy), _p(tinv), _p(e_vk), _p(z), _p(seq_off), nseq)
+    with torch.cuda.device_of(w), _timed("wkv7c_bseq" if state is None else "wkv7c_bseq_state", w):
+        if state is None:
+            rc = _lib.lib().rwkv7_wkv_chunk_bseq_bf16(*args, _stream(w))
+        else:
+            rc = _lib.lib().rwkv7_wkv_chunk_bseq_state_seq_bf16(*args, *[_p(t) for t in state], _stream(w))
+    _lib.check(rc, "wkv7_chunk_bseq")
+    return e_vk, z
 
 
 def wkv7_chunk_bwd_seq(w, q, a, b, dy, tinv, seq_off=None, want_z=False):
@@ -346,19 +380,21 @@ def wkv7_chunk_bwd_seq(w, q, a, b, dy, tinv, seq_off=None, want_z=False):
     form E_c = E' + A~^T Z + Q~^T dY, Z = (T^T B^) E' + (T^T A_qb^T) dY -- M_c^T / N'_c are not materialised.  Returns e_vk
     (e_vk[b,h,c] = E_{c+1} as q15 records); with want_z also Z (fp32 [B,T,H,64],
     Z_t = dL/du_t) as (e_vk, z)."""
-    B, T, H, C = w.shape
-    if w.dtype != torch.bfloat16:
-        raise TypeError("the chunked backward is bf16 only")
-    if T % CHUNK_T != 0:
-        raise ValueError(f"chunked WKV7 needs T % {CHUNK_T} == 0, got T={T}")
-    e_vk = torch.empty(B, H, T // CHUNK_T, Q15_REC, dtype=torch.int16, device=w.device)
-    # packed rows leave the positions behind the last sequence untouched: zeros there (the gradient kernel reads every chunk)
-    z = (torch.empty if seq_off is None else torch.zeros)(B, T, H, C, dtype=torch.float32, device=w.device) if want_z else None
-    with torch.cuda.device_of(w), _timed("wkv7c_bseq", w):
-        rc = _lib.lib().rwkv7_wkv_chunk_bseq_bf16(B, T, H, _p(w), _p(q), _p(a), _p(b), _p(dy), _p(tinv), _p(e_vk), _p(z),
-                                                  *_seq_args(seq_off), _stream(w))
-    _lib.check(rc, "wkv7_chunk_bseq")
+    e_vk, z = _bseq(w, q, a, b, dy, tinv, seq_off, _nseq(seq_off), want_z)
     return (e_vk, z) if want_z else e_vk
+
+
+def _chunk_bwd(w, q, k, v, a, b, dy, hs, sa, tinv, seq_off, nseq, state=None):
+    """bseq (which also writes Z = dL/du) + the per-chunk gradients from Z on [B,T,H,64] rows: [dw, dq, dk, dv, da, db].
+    state: as _bseq."""
+    B, T, H, C = w.shape
+    e_vk, z = _bseq(w, q, a, b, dy, tinv, seq_off, nseq, True, state)
+    grads = [torch.empty_like(w) for _ in range(6)]
+    with torch.cuda.device_of(w), _timed("wkv7c_bwd_out", w):
+        rc = _lib.lib().rwkv7_wkv_chunk_bwd_out_z_bf16(B, T, H, _p(w), _p(q), _p(k), _p(v), _p(a), _p(b), _p(dy), _p(hs), _p(sa),
+                                                       _p(z), _p(e_vk), *[_p(g) for g in grads], _stream(w))
+    _lib.check(rc, "wkv7_chunk_bwd_out")
+    return grads
 
 
 def wkv7_chunk_backward(w, q, k, v, a, b, dy, hs, sa, tinv, seq_off=None):
@@ -366,16 +402,9 @@ def wkv7_chunk_backward(w, q, k, v, a, b, dy, hs, sa, tinv, seq_off=None):
     wkv7_chunk_forward saved (hs, sa, tinv).  Two launches: the adjoint-state recurrence (csrc/wkv7_chunk_bseq.hip, which also
     writes Z = dL/du) and the per-chunk gradients from Z (csrc/wkv7_chunk_bwd10.hip, two matrix phases).
     Returns (dw, dq, dk, dv, da, db)."""
-    B, T, H, C = w.shape
     if hs.dtype != torch.int16 or hs.shape[-1] != Q15_REC or sa.dtype != torch.float32 or tinv.dtype != torch.float32:
         raise TypeError("wkv7_chunk_backward takes hs (q15 records), sa and tinv (fp32) as saved by wkv7_chunk_forward")
-    e_vk, z = wkv7_chunk_bwd_seq(w, q, a, b, dy, tinv, seq_off, want_z=True)
-    grads = [torch.empty_like(w) for _ in range(6)]
-    with torch.cuda.device_of(w), _timed("wkv7c_bwd_out", w):
-        rc = _lib.lib().rwkv7_wkv_chunk_bwd_out_z_bf16(B, T, H, _p(w), _p(q), _p(k), _p(v), _p(a), _p(b), _p(dy), _p(hs), _p(sa),
-                                                       _p(z), _p(e_vk), *[_p(g) for g in grads], _stream(w))
-    _lib.check(rc, "wkv7_chunk_bwd_out")
-    return tuple(grads)
+    return tuple(_chunk_bwd(w, q, k, v, a, b, dy, hs, sa, tinv, seq_off, _nseq(seq_off)))
 
 
 def debug_mma32(X, Y):
@@ -407,70 +436,45 @@ def _pad_rows(x, front, tail, fill):
     return out
 
 
+def _unpad_rows(x, front, tail):
+    """[B, front + T + tail, C] -> contiguous [B, T, C] (x itself when nothing was added)."""
+    if front == 0 and tail == 0:
+        return x
+    return x[:, front:x.shape[1] - tail].contiguous()
+
+
 class _WkvStateChunked(torch.autograd.Function):
-    """y, hT = scan(h0; r, w, k, v, a, b) on the chunked kernels, differentiable in all seven inputs (see wkv7_state_chunked)."""
+    """y, hT = the scans from carried states of a chunk-aligned row [R, front + T + tail, H*64] on the chunked kernels,
+    differentiable in h0 and r..b.  r..b come in as [R, T, H*64]: the Function adds `front` / `tail` identity rows (w = W_PAD, the
+    rest 0) and drops them again from y and from the input gradients.  seq_off (int32 [nseq + 1] device tensor) / nseq: packed
+    rows with one state per sequence, h0 / hT [nseq,H,64,64]; None / 0: one state per row, [R,H,64,64]."""
 
     @staticmethod
-    def forward(ctx, h0, r, w, k, v, a, b):
-        B, T, HC = r.shape
+    def forward(ctx, h0, r, w, k, v, a, b, seq_off, nseq, front, tail):
+        R, T, HC = r.shape
         H = HC // HEAD_SIZE
-        train = any(ctx.needs_input_grad)
-        # T % 32 != 0: identity steps in FRONT (the state reaches the first real step unchanged).  Training frames the row with one
-        # whole identity chunk at EACH end: the per-chunk gradient kernel (csrc/wkv7_chunk_bwd10.hip, unchanged) treats a row as
-        # starting from the zero state and ending with no future -- a workgroup hands the end state of one chunk on as the start
-        # state of the next and zeroes it across a row boundary, and the last chunk's rowsum(E * H_C) decay term is dropped.  With
-        # the pad chunks every real chunk is an inner one: its start state is the checkpoint of the state after the leading pad
-        # (= h0) and its future the adjoint behind the trailing pad (= dhT), both passed through the identity chunks bit for bit.
-        front = (-T) % CHUNK_T + (CHUNK_T if train else 0)
-        tail = CHUNK_T if train else 0
         Tp = front + T + tail
-        pw = _pad_rows(w, front, tail, W_PAD)
-        pq, pk, pv, pa, pb = [_pad_rows(x, front, tail, 0.0) for x in (r, k, v, a, b)]
-        w4, q4, k4, v4, a4, b4 = [x.view(B, Tp, H, HEAD_SIZE) for x in (pw, pq, pk, pv, pa, pb)]
-        h0c = h0.contiguous()
-        tinv = wkv7_chunk_prep(w4, a4, b4)
-        y = torch.empty_like(v4)
-        sa = torch.empty(B, Tp, H, HEAD_SIZE, dtype=torch.float32, device=r.device) if train else None
-        hs = torch.empty(B, H, Tp // CHUNK_T, Q15_REC, dtype=torch.int16, device=r.device) if train else None
-        hT = torch.empty(B, H, HEAD_SIZE, HEAD_SIZE, dtype=torch.float32, device=r.device)
-        with torch.cuda.device_of(r), _timed("wkv7c_fwd_state", r):
-            rc = _lib.lib().rwkv7_wkv_chunk_fwd_state_bf16(B, Tp, H, _p(w4), _p(q4), _p(k4), _p(v4), _p(a4), _p(b4), _p(tinv), _p(y),
-                                                           _p(sa), _p(hs), _p(h0c), _p(hT), _stream(r))
-        _lib.check(rc, "wkv7_state_chunked")
+        train = any(ctx.needs_input_grad)
+        ins = [_pad_rows(x, front, tail, f) for x, f in ((w, W_PAD), (r, 0.0), (k, 0.0), (v, 0.0), (a, 0.0), (b, 0.0))]
+        w4, q4, k4, v4, a4, b4 = [x.view(R, Tp, H, HEAD_SIZE) for x in ins]
+        y, tinv, sa, hs, hT = _chunk_fwd(w4, q4, k4, v4, a4, b4, train, seq_off, nseq, h0=h0.contiguous())
         if train:
-            ctx.save_for_backward(w4, q4, k4, v4, a4, b4, tinv, sa, hs)
-            ctx.front, ctx.tail = front, tail
+            ctx.save_for_backward(w4, q4, k4, v4, a4, b4, tinv, sa, hs, seq_off)
+            ctx.nseq, ctx.n_states, ctx.front, ctx.tail = nseq, hT.shape[0], front, tail
         ctx.set_materialize_grads(False)
-        y = y.view(B, Tp, HC)
-        return (y if Tp == T else y[:, front:front + T].contiguous()), hT
+        return _unpad_rows(y.view(R, Tp, HC), front, tail), hT
 
     @staticmethod
     def backward(ctx, dy, dhT):
-        w4, q4, k4, v4, a4, b4, tinv, sa, hs = ctx.saved_tensors
-        B, Tp, H, C = w4.shape
+        w4, q4, k4, v4, a4, b4, tinv, sa, hs, seq_off = ctx.saved_tensors
+        R, Tp, H, C = w4.shape
         front, tail = ctx.front, ctx.tail
-        T = Tp - front - tail
-        if dy is None:
-            dy4 = torch.zeros_like(v4)
-        else:
-            dy4 = _pad_rows(dy.to(w4.dtype), front, tail, 0.0).view(B, Tp, H, C)
+        dy4 = torch.zeros_like(v4) if dy is None else _pad_rows(dy.to(w4.dtype), front, tail, 0.0).view(R, Tp, H, C)
         dhT = None if dhT is None else dhT.to(torch.float32).contiguous()
-        dh0 = torch.empty(B, H, C, C, dtype=torch.float32, device=w4.device) if ctx.needs_input_grad[0] else None
-        e_vk = torch.empty(B, H, Tp // CHUNK_T, Q15_REC, dtype=torch.int16, device=w4.device)
-        z = torch.empty(B, Tp, H, C, dtype=torch.float32, device=w4.device)
-        with torch.cuda.device_of(w4), _timed("wkv7c_bseq_state", w4):
-            rc = _lib.lib().rwkv7_wkv_chunk_bseq_state_bf16(B, Tp, H, _p(w4), _p(q4), _p(a4), _p(b4), _p(dy4), _p(tinv), _p(e_vk),
-                                                            _p(z), _p(dhT), _p(dh0), _stream(w4))
-        _lib.check(rc, "wkv7_state_chunked backward (bseq)")
-        grads = [torch.empty_like(w4) for _ in range(6)]   # dw dq dk dv da db
-        with torch.cuda.device_of(w4), _timed("wkv7c_bwd_out", w4):
-            rc = _lib.lib().rwkv7_wkv_chunk_bwd_out_z_bf16(B, Tp, H, _p(w4), _p(q4), _p(k4), _p(v4), _p(a4), _p(b4), _p(dy4), _p(hs),
-                                                           _p(sa), _p(z), _p(e_vk), *[_p(g) for g in grads], _stream(w4))
-        _lib.check(rc, "wkv7_state_chunked backward (bwd_out)")
-        dw, dq, dk, dv, da, db = [g.view(B, Tp, H * C) for g in grads]
-        if Tp != T:
-            dw, dq, dk, dv, da, db = [g[:, front:front + T].contiguous() for g in (dw, dq, dk, dv, da, db)]
-        return dh0, dq, dw, dk, dv, da, db
+        dh0 = torch.empty(ctx.n_states, H, C, C, dtype=torch.float32, device=w4.device) if ctx.needs_input_grad[0] else None
+        grads = _chunk_bwd(w4, q4, k4, v4, a4, b4, dy4, hs, sa, tinv, seq_off, ctx.nseq, state=(dhT, dh0))
+        dw, dq, dk, dv, da, db = [_unpad_rows(g.view(R, Tp, H * C), front, tail) for g in grads]
+        return dh0, dq, dw, dk, dv, da, db, None, None, None, None
 
 
 def wkv7_state_chunked(h0, r, w, k, v, a, b):
@@ -493,7 +497,16 @@ def wkv7_state_chunked(h0, r, w, k, v, a, b):
     if h0.dtype != torch.float32 or tuple(h0.shape) != (B, HC // HEAD_SIZE, HEAD_SIZE, HEAD_SIZE):
         raise TypeError(f"wkv7_state_chunked: h0 must be float32 [B,H,64,64] = {(B, HC // HEAD_SIZE, 64, 64)}, got "
                         f"{h0.dtype} {tuple(h0.shape)}")
-    return _WkvStateChunked.apply(h0, r, w, k, v, a, b)
+    # T % 32 != 0: identity steps in FRONT (the state reaches the first real step unchanged).  Training (any input requires grad:
+    # the Function's needs_input_grad) frames the row with one whole identity chunk at EACH end: the per-chunk gradient kernel
+    # (csrc/wkv7_chunk_bwd10.hip, unchanged) treats a row as starting from the zero state and ending with no future -- a workgroup
+    # hands the end state of one chunk on as the start state of the next and zeroes it across a row boundary, and the last chunk's
+    # rowsum(E * H_C) decay term is dropped.  With the pad chunks every real chunk is an inner one: its start state is the
+    # checkpoint of the state after the leading pad (= h0) and its future the adjoint behind the trailing pad (= dhT), both passed
+    # through the identity chunks bit for bit.
+    train = any(t.requires_grad for t in (h0, r, w, k, v, a, b))
+    front = (-T) % CHUNK_T + (CHUNK_T if train else 0)
+    return _WkvStateChunked.apply(h0, r, w, k, v, a, b, None, 0, front, CHUNK_T if train else 0)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -554,59 +567,34 @@ def packed_state_layout(lens, train, align=None):
                              torch.tensor(last, dtype=torch.int32))
 
 
-class _WkvStateChunkedSeq(torch.autograd.Function):
-    """y, hT = the per-sequence scans of an ALIGNED packed row on the chunked kernels, differentiable in h0 and r..b (see
-    wkv7_state_chunked_seq)."""
-
-    @staticmethod
-    def forward(ctx, h0, r, w, k, v, a, b, seq_off, nseq):
-        _, T, HC = r.shape
-        H = HC // HEAD_SIZE
-        train = any(ctx.needs_input_grad[:7])
-        w4, q4, k4, v4, a4, b4 = [x.contiguous().view(1, T, H, HEAD_SIZE) for x in (w, r, k, v, a, b)]
-        h0c = h0.contiguous()
-        tinv = wkv7_chunk_prep(w4, a4, b4)
-        y = torch.empty_like(v4)
-        sa = torch.empty(1, T, H, HEAD_SIZE, dtype=torch.float32, device=r.device) if train else None
-        hs = torch.empty(1, H, T // CHUNK_T, Q15_REC, dtype=torch.int16, device=r.device) if train else None
-        hT = torch.empty(nseq, H, HEAD_SIZE, HEAD_SIZE, dtype=torch.float32, device=r.device)
-        with torch.cuda.device_of(r), _timed("wkv7c_fwd_state_seq", r):
-            rc = _lib.lib().rwkv7_wkv_chunk_fwd_state_seq_bf16(1, T, H, _p(w4), _p(q4), _p(k4), _p(v4), _p(a4), _p(b4), _p(tinv), _p(y),
-                                                               _p(sa), _p(hs), _p(seq_off), nseq, _p(h0c), _p(hT), _stream(r))
-        _lib.check(rc, "wkv7_state_chunked_seq")
-        if train:
-            ctx.save_for_backward(w4, q4, k4, v4, a4, b4, tinv, sa, hs, seq_off)
-            ctx.nseq = nseq
-        ctx.set_materialize_grads(False)
-        return y.view(1, T, HC), hT
-
-    @staticmethod
-    def backward(ctx, dy, dhT):
-        w4, q4, k4, v4, a4, b4, tinv, sa, hs, seq_off = ctx.saved_tensors
-        _, T, H, C = w4.shape
-        dy4 = torch.zeros_like(v4) if dy is None else dy.to(w4.dtype).contiguous().view(1, T, H, C)
-        dhT = None if dhT is None else dhT.to(torch.float32).contiguous()
-        dh0 = torch.empty(ctx.nseq, H, C, C, dtype=torch.float32, device=w4.device) if ctx.needs_input_grad[0] else None
-        e_vk = torch.empty(1, H, T // CHUNK_T, Q15_REC, dtype=torch.int16, device=w4.device)
-        z = torch.empty(1, T, H, C, dtype=torch.float32, device=w4.device)
-        with torch.cuda.device_of(w4), _timed("wkv7c_bseq_state_seq", w4):
-            rc = _lib.lib().rwkv7_wkv_chunk_bseq_state_seq_bf16(1, T, H, _p(w4), _p(q4), _p(a4), _p(b4), _p(dy4), _p(tinv), _p(e_vk),
-                                                                _p(z), _p(seq_off), ctx.nseq, _p(dhT), _p(dh0), _stream(w4))
-        _lib.check(rc, "wkv7_state_chunked_seq backward (bseq)")
-        grads = [torch.empty_like(w4) for _ in range(6)]   # dw dq dk dv da db
-        with torch.cuda.device_of(w4), _timed("wkv7c_bwd_out", w4):
-            rc = _lib.lib().rwkv7_wkv_chunk_bwd_out_z_bf16(1, T, H, _p(w4), _p(q4), _p(k4), _p(v4), _p(a4), _p(b4), _p(dy4), _p(hs),
-                                                           _p(sa), _p(z), _p(e_vk), *[_p(g) for g in grads], _stream(w4))
-        _lib.check(rc, "wkv7_state_chunked_seq backward (bwd_out)")
-        dw, dq, dk, dv, da, db = [g.view(1, T, H * C) for g in grads]
-        return dh0, dq, dw, dk, dv, da, db, None, None
-
-
 def wkv7_state_chunked_seq(h0, r, w, k, v, a, b, seq_off, nseq):
     """The per-sequence scans of a packed row that is ALREADY laid out (packed_state_layout): r..b bf16 [1, T_al, H*64] with
     identity steps (w = W_PAD, the rest 0) at every row outside a sequence, seq_off int32 [nseq + 1] on the device, h0 fp32
     [nseq,H,64,64].  Returns (y [1, T_al, H*64], hT [nseq,H,64,64]); the gradients at the identity rows are not meaningful."""
-    return _WkvStateChunkedSeq.apply(h0, r, w, k, v, a, b, seq_off, nseq)
+    return _WkvStateChunked.apply(h0, r, w, k, v, a, b, seq_off, nseq, 0, 0)
+
+
+class RowMap:
+    """A packed row [1, total, D] and the chunk-aligned row [1, t_al, D] its sequences are laid out on, from dest (int32 [total]:
+    the aligned row of every packed position, -1 for a position that belongs to no sequence; on the host or the device):
+      dest, src_of  int32 [total] / [t_al] on `device`: src_of = the packed position every aligned row holds, -1 for a masked row
+      keep          bool [1, t_al, 1]: the aligned rows that hold a token
+    Both maps are injective, so both re-layouts and both of their gradients are row gathers (fused.gather_rows)."""
+
+    def __init__(self, dest, t_al, device):
+        j = torch.arange(dest.numel(), dtype=torch.int32, device=dest.device)
+        src_of = torch.full((t_al + 1,), -1, dtype=torch.int32, device=dest.device)   # slot t_al takes the unowned positions
+        src_of = src_of.scatter(0, torch.where(dest >= 0, dest, torch.full_like(dest, t_al)).long(), j)[:t_al]
+        self.dest, self.src_of = dest.to(device, non_blocking=True), src_of.to(device, non_blocking=True)
+        self.keep = (self.src_of >= 0).view(1, -1, 1)
+
+    def to_aligned(self, x):
+        """[1, total, D] -> [1, t_al, D], zeros in the masked rows."""
+        return fused.gather_rows(x[0], self.src_of, self.dest).unsqueeze(0)
+
+    def to_packed(self, y):
+        """[1, t_al, D] -> [1, total, D], zeros at the positions of no sequence."""
+        return fused.gather_rows(y[0], self.dest, self.src_of).unsqueeze(0)
 
 
 def wkv7_state_chunked_varlen(h0, r, w, k, v, a, b, cu_seqlens):
@@ -636,18 +624,10 @@ def wkv7_state_chunked_varlen(h0, r, w, k, v, a, b, cu_seqlens):
     lay = packed_state_layout([b_ - a_ for a_, b_ in zip(cu[:-1], cu[1:])], train)
     if lay.t_al == 0:
         return r.new_zeros(r.shape), h0.clone()
-    dev = r.device
-    src = torch.full((lay.t_al,), cu[-1] - cu[0], dtype=torch.long)   # index of the fill row
-    src[lay.dest.long()] = torch.arange(cu[-1] - cu[0])
-    src = src.to(dev, non_blocking=True)
-
-    def lay_out(x, fill):
-        rows = torch.cat([x[0, cu[0]:cu[-1]], x.new_full((1, HC), fill)], 0)
-        return rows.index_select(0, src).unsqueeze(0)
-
-    ins = [lay_out(x, f) for x, f in ((r, 0.0), (w, W_PAD), (k, 0.0), (v, 0.0), (a, 0.0), (b, 0.0))]
-    y_al, hT = wkv7_state_chunked_seq(h0, *ins, lay.seq_off.to(dev, non_blocking=True), N)
-    y = y_al[0].index_select(0, lay.dest.to(dev, non_blocking=True).long())
-    if cu[0] > 0 or cu[-1] < total:
-        y = torch.cat([y.new_zeros(cu[0], HC), y, y.new_zeros(total - cu[-1], HC)], 0)
-    return y.unsqueeze(0), hT
+    dest = torch.full((total,), -1, dtype=torch.int32)
+    dest[cu[0]:cu[-1]] = lay.dest
+    rows = RowMap(dest, lay.t_al, r.device)
+    r_al, w_al, k_al, v_al, a_al, b_al = [rows.to_aligned(x) for x in (r, w, k, v, a, b)]
+    w_al = torch.where(rows.keep, w_al, W_PAD)   # identity steps in every pad row
+    y_al, hT = wkv7_state_chunked_seq(h0, r_al, w_al, k_al, v_al, a_al, b_al, lay.seq_off.to(r.device, non_blocking=True), N)
+    return rows.to_packed(y_al), hT
