@@ -392,6 +392,38 @@ int rwkv7_wkv_chunk_fwd_state_seq_bf16(int B, int T, int H, const void *w, const
 int rwkv7_wkv_chunk_bseq_state_seq_bf16(int B, int T, int H, const void *w, const void *q, const void *a, const void *b,
                                         const void *dy, const float *tinv, void *e_vk, float *z, const int *seq_chunk_off, int nseq,
                                         const float *dhT, float *dh0, rwkv7_stream_t stream);
+/* ---- stateful packed PREFILL into chosen rows of a cache (rwkvtts_amd/prefill.py, PackedPrefill): bf16, forward only, no tape.  Every
+ *      index below is a device pointer read at run time, so one captured launch serves every pack of the same shapes.
+ *   rwkv7_wkv_chunk_fwd_state_rows_bf16: rwkv7_wkv_chunk_fwd_state_seq_bf16 (B = 1, no sa / hs) on indexed rows of a cache field, IN
+ *      PLACE.  state fp32 [S,H,64,64]; state_row int32 [nseq]: sequence s loads its start state from state[state_row[s]] and stores
+ *      its end state there.  state_row[s] < 0: the sequence is inactive, its workgroups return and write nothing (y of its chunks
+ *      included: give it an empty chunk range).  Bit 30 (RWKV7_STATE_ROW_ZERO) set: start from zero instead of loading.  The row
+ *      index (state_row[s] without bit 30) MUST lie in [0, S) and the active rows must be distinct: they live on the device and are
+ *      NOT checked here -- the caller guarantees both (PackedPrefill.plan validates on the host before it copies).  Each of the two
+ *      workgroups of a (sequence, head) owns its own 32 value rows of the entry, which makes the in-place update safe.  The grid is
+ *      sized by nseq, the capacity, not by the live count.  y and the end states are bit-identical to the _state_seq entry run on
+ *      the gathered rows (h0 = zeros for bit 30).  RWKV7_EINVAL: NULL pointer, T / H / nseq < 1; RWKV7_ESHAPE: T % 32 != 0. */
+#define RWKV7_STATE_ROW_ZERO (1 << 30)
+int rwkv7_wkv_chunk_fwd_state_rows_bf16(int T, int H, const void *w, const void *q, const void *k, const void *v, const void *a,
+                                        const void *b, const float *tinv, void *y, const int *seq_chunk_off, int nseq, float *state,
+                                        const int *state_row, rwkv7_stream_t stream);
+/*   rwkv7_add_ln_mix_rows_fwd_bf16: rwkv7_add_ln_mix_fwd_bf16 (B = 1, nmix = 6 or 1, branch may be NULL, mask per row or NULL, no
+ *      mean / rstd) on a packed row of T rows whose token-shift predecessors may be carried, with two int32 maps of length T:
+ *        prev_src[t]  -1: ordinary, the predecessor is the masked h of row t - 1 (0 for t = 0); -2: the predecessor is zero (the first
+ *                     token of a fresh sequence); r >= 0: the predecessor is row r of the cache field x_prev [S,D]
+ *        last_dst[t]  -1: nothing; r >= 0: this row's hm (h rounded to bf16 and masked, exactly what the lerp reads) -> x_prev[r]
+ *      The lerp on a carried row is the kernel's own hm + (x_prev - hm) * mu in fp32 with one rounding.  x_out and every ordinary
+ *      row are bit-identical to rwkv7_add_ln_mix_fwd_bf16 (one LayerNorm device routine, csrc/ln_row.h).
+ *      x_prev_rd: where carried predecessors are READ; NULL = x_prev itself.  A row that reads and writes the same r (a one-token
+ *      piece) reads first, inside the thread that owns the channels.  A piece of SEVERAL rows whose first row reads r while its
+ *      last row writes r is two different workgroups and a race on x_prev: pass a snapshot of the field as x_prev_rd then (what
+ *      PackedPrefill does).  Rows r are not range-checked (device data; caller's guarantee, as above); each r at most once per map.
+ *      RWKV7_EINVAL: NULL x / gamma / params / out / prev_src / last_dst / x_prev, branch without x_out, T, nblocks or run_len < 1;
+ *      RWKV7_ESHAPE: T % 32 != 0, nmix not in {1, 6}, D % 64 != 0 or D > 4096. ---- */
+int rwkv7_add_ln_mix_rows_fwd_bf16(int T, int D, int nmix, const void *x, const void *branch, const void *gamma, const void *beta,
+                                   float eps, const void *mask, const void *params, const int *prev_src, const int *last_dst,
+                                   const void *x_prev_rd, void *x_prev, void *x_out, void *out, int nblocks, int run_len,
+                                   rwkv7_stream_t stream);
 /*      (The round-3/4 per-chunk gradient kernel, csrc/lab/wkv7_chunk_bwd9.hip, is an A/B twin with its own entry point in the lab build:
  *      include/rwkv7_hip_lab.h.  There are no process-wide switches in this library.) */
 /* ---- head loss: softmax cross-entropy of a chunk of bf16 logits [rows,V], forward and backward in one pass

@@ -8,7 +8,8 @@ every one of up to 32 SLOTS (rows of the step kernel's batch) runs its own reque
     column, next input embedding, step, live flag);
   * admission, eagerly between replays on the same stream: pending requests in FIFO order take free slots, their cache rows are
     reset to zero and prefilled as ONE packed row (RWKV7Model(..., cu_seqlens, past_key_values, cache_rows)), the head runs on each
-    sequence's last position, and the same per-slot entry (with row_slot) draws the first id;
+    sequence's last position, and the same per-slot entry (with row_slot) draws the first id; with admission="graph" the prefill
+    is prefill.PackedPrefill instead: graphs captured once per size class, replayed on this cache, no device read-back;
   * retirement: without EOS the host knows every budget and retires slots on the exact step with no read-back; with EOS it reads
     the live flags and step counters back every `check_every` replays.
 
@@ -136,11 +137,21 @@ class ContinuousDecoder:
 
     model: a bf16 RWKV7ForSpeech / RWKV7ForCausalLM on the HIP device that the step kernel covers (DecodeStep.supported); slots <= 32.
     A request's ids run up to and including its EOS, or up to its max_new_tokens (<= max_new_tokens_cap), with no pad tail; they are
-    device int64 tensors.  pad_token_id is accepted for signature compatibility with GraphDecoder and not used: no pad is emitted."""
+    device int64 tensors.  pad_token_id is accepted for signature compatibility with GraphDecoder and not used: no pad is emitted.
+
+    admission: "eager" (default) prefills admitted prompts through RWKV7Model(..., cache_rows=...), one torch op at a time; "graph"
+    through prefill.PackedPrefill on the engine's cache: graphs captured once per size class and replayed, the rows reset inside the
+    kernels, no device read-back.  In "graph" mode a request's ids do not depend on its slot or on when it is admitted FOR THE SAME PACK
+    COMPOSITION (the prompts admitted together, in order): the composition decides the bucket and with it the GEMM shapes, whose
+    library kernels may round differently from bucket to bucket.  prefill_max_seqs / prefill_buckets: PackedPrefill's."""
 
     def __init__(self, model, slots: int = 32, max_new_tokens_cap: int = 3000, eos_token_id: Optional[int] = None,
-                 pad_token_id: Optional[int] = None, suppress_tokens: Optional[Sequence[int]] = None, check_every: int = 16):
+                 pad_token_id: Optional[int] = None, suppress_tokens: Optional[Sequence[int]] = None, check_every: int = 16,
+                 admission: str = "eager", prefill_max_seqs: int = 8, prefill_buckets: Sequence[int] = (256, 512, 1024, 2048, 4096)):
         from .decode import DecodeStep
+        if admission not in ("eager", "graph"):
+            raise ValueError(f"admission = {admission!r}: 'eager' or 'graph'")
+        self.admission = admission
         if not 1 <= slots <= 32:
             raise ValueError(f"slots = {slots}: the step kernel's batch is 1..32")
         if max_new_tokens_cap < 1 or check_every < 1:
@@ -214,6 +225,10 @@ class ContinuousDecoder:
         with torch.cuda.graph(self.graph):
             self._step()
         self.replays = 0   # captured steps run so far
+        self.prefill = None
+        if admission == "graph":
+            from .prefill import PackedPrefill
+            self.prefill = PackedPrefill(m.model, self.cache, max_seqs=prefill_max_seqs, buckets=prefill_buckets)
 
     def _step(self):
         sample_slots(self.dstep(self.x), self.st, None, self.allow_lo, self.allow_hi, self.suppress, self.max_domain)
@@ -293,6 +308,8 @@ class ContinuousDecoder:
             return
         m, dev = self.model, self.device
         slots = [s for s, _ in took]
+        if self.prefill is not None:
+            return self._admit_graph(took, slots)
         lens = [r.embeds.shape[0] for _, r in took]
         cu = [0]
         for n in lens:
@@ -307,6 +324,17 @@ class ContinuousDecoder:
         h = m.model(inputs_embeds=packed, cu_seqlens=cu_t, past_key_values=self.cache, cache_rows=torch.tensor(slots)).last_hidden_state
         last = torch.tensor([c - 1 for c in cu[1:]], dtype=torch.int64).to(dev, non_blocking=True)
         logits = m.lm_head(h[0].index_select(0, last)).float()
+        self._admit_draw(took, logits, rows64, torch.tensor(slots, dtype=torch.int32).to(dev, non_blocking=True))
+
+    def _admit_graph(self, took, slots):
+        """Admission through PackedPrefill: the rows are reset by the kernels (zero marks), the layout goes over as one pinned index
+        block per replay, and nothing is read back."""
+        h_last = self.prefill.run([r.embeds for _, r in took], slots, fresh=True)
+        logits = self.model.lm_head(h_last).float()
+        row_slot = torch.tensor(slots, dtype=torch.int32).pin_memory().to(self.device, non_blocking=True)
+        self._admit_draw(took, logits, row_slot.long(), row_slot)
+
+    def _admit_draw(self, took, logits, rows64, row_slot):
         # the slots' parameters: host mirror -> one copy per field; step = 0 and live = 1 for the admitted slots only (the device
         # advances the other slots' counters)
         ph = self._par_host
@@ -323,5 +351,4 @@ class ContinuousDecoder:
             self._par_dev[k].copy_(v.pin_memory(), non_blocking=True)
         self.step_t.index_fill_(0, rows64, 0)
         self.live.index_fill_(0, rows64, 1)
-        row_slot = torch.tensor(slots, dtype=torch.int32).to(dev, non_blocking=True)
         sample_slots(logits, self.st, row_slot, self.allow_lo, self.allow_hi, self.suppress, self.max_domain)

@@ -98,6 +98,8 @@ template <typename T> int add_ln_fwd(long, int, const void *, const void *, cons
 template <typename T> int add_ln_bwd(long, int, const void *, const void *, const void *, const float *, const float *, const void *, void *, float *, int, hipStream_t);
 template <typename T> int add_ln_mix_fwd(int, int, int, int, void *, const void *, const void *, const void *, const void *, float, const void *, const void *, void *, void *, float *, float *, int, int, hipStream_t);
 template <typename T> int mix_add_ln_bwd(int, int, int, int, const void *const *, const void *, const void *, const float *, const float *, const void *, const void *, const void *, const void *, void *, float *, int, int, hipStream_t);
+int add_ln_mix_rows_fwd_bf16(int, int, int, const void *, const void *, const void *, const void *, float, const void *, const void *, const int *, const int *, const void *, void *, void *, void *, int, int, hipStream_t);
+int chunk_fwd9_state_rows_bf16(int, int, const void *, const void *, const void *, const void *, const void *, const void *, const float *, void *, const int *, int, float *, const int *, hipStream_t);
 template <typename T> int relusq_fwd(long, const void *, void *, hipStream_t);
 template <typename T> int relusq_bwd(long, const void *, const void *, void *, hipStream_t);
 template <typename T> int relusq_bwd_s(long, const void *, const void *, void *, hipStream_t);
@@ -486,6 +488,28 @@ int rwkv7_wkv_chunk_bseq_state_seq_bf16(int B, int T, int H, const void *w, cons
     if ((seq_chunk_off == nullptr) != (nseq <= 0)) return RWKV7_EINVAL;
     if (T % 32 != 0) return RWKV7_ECHUNK;
     return rwkv7::chunk_bseq_state_seq_bf16(B, T, H, w, q, a, b, dy, tinv, e_vk, z, seq_chunk_off, nseq, dhT, dh0, (hipStream_t)stream);
+}
+// stateful packed prefill into chosen cache rows (rwkvtts_amd/prefill.py): every index is device data read by the kernels
+int rwkv7_wkv_chunk_fwd_state_rows_bf16(int T, int H, const void *w, const void *q, const void *k, const void *v, const void *a,
+                                        const void *b, const float *tinv, void *y, const int *seq_chunk_off, int nseq, float *state,
+                                        const int *state_row, rwkv7_stream_t stream) {
+    if (T <= 0 || H <= 0 || nseq < 1 ||
+        any_null({w, q, k, v, a, b, (const void *)tinv, y, (const void *)seq_chunk_off, (const void *)state, (const void *)state_row}))
+        return RWKV7_EINVAL;
+    if (T % 32 != 0) return RWKV7_ESHAPE;
+    return rwkv7::chunk_fwd9_state_rows_bf16(T, H, w, q, k, v, a, b, tinv, y, seq_chunk_off, nseq, state, state_row, (hipStream_t)stream);
+}
+int rwkv7_add_ln_mix_rows_fwd_bf16(int T, int D, int nmix, const void *x, const void *branch, const void *gamma, const void *beta,
+                                   float eps, const void *mask, const void *params, const int *prev_src, const int *last_dst,
+                                   const void *x_prev_rd, void *x_prev, void *x_out, void *out, int nblocks, int run_len,
+                                   rwkv7_stream_t stream) {
+    if (T <= 0 || nblocks <= 0 || run_len <= 0 ||
+        any_null({x, gamma, params, out, (const void *)prev_src, (const void *)last_dst, (const void *)x_prev}))
+        return RWKV7_EINVAL;
+    if (branch && !x_out) return RWKV7_EINVAL;
+    if (!SHAPE_OK(D) || (nmix != 1 && nmix != 6) || T % 32 != 0) return RWKV7_ESHAPE;
+    return rwkv7::add_ln_mix_rows_fwd_bf16(T, D, nmix, x, branch, gamma, beta, eps, mask, params, prev_src, last_dst,
+                                           x_prev_rd ? x_prev_rd : x_prev, x_prev, x_out, out, nblocks, run_len, (hipStream_t)stream);
 }
 // plain rows (one state per row, [B,H,64,64]): the packed entries with seq_chunk_off = NULL, nseq = 0
 int rwkv7_wkv_chunk_fwd_state_bf16(int B, int T, int H, const void *w, const void *q, const void *k, const void *v,

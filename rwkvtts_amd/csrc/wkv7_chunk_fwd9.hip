@@ -83,14 +83,20 @@ static_assert(F9Smem::bytes <= 160 * 1024, "LDS budget");
 // the last chunk; both fp32 [R,H,64 (value),64 (key)] with R = B on plain rows and R = nseq on packed rows (seq_off_ != NULL: the state
 // of sequence sq, head hh is entry sq * H + hh).  A sequence with an empty chunk range copies h0 to hT (zeros for a NULL h0).  The
 // stateless instantiations never touch them.
-template <bool SAVE, bool STATE>
+// ROWS (STATE, packed rows, no SAVE: stateful prefill into chosen cache rows): hT_ is a cache field [S,H,64,64] updated IN PLACE and
+// state_row_ (int32 [nseq], read here, on the device) names sequence sq's row of it: < 0 = the sequence is inactive (its workgroups
+// return and write nothing); bit 30 (kRowZero) = start from zero instead of loading the row; the rest is the row, which the caller
+// keeps inside [0, S).  Each workgroup loads and stores its own 32 value rows of the (row, head) entry, so in place is safe.
+constexpr int kRowZero = 1 << 30;
+template <bool SAVE, bool STATE, bool ROWS = false>
 __global__ __launch_bounds__(512) void wkv7c_fwd9_kernel(int T_, int H, const bf16_t *__restrict__ w_, const bf16_t *__restrict__ q_,
                                                          const bf16_t *__restrict__ k_, const bf16_t *__restrict__ v_,
                                                          const bf16_t *__restrict__ a_, const bf16_t *__restrict__ b_,
                                                          const float *__restrict__ tinv_, bf16_t *__restrict__ y_,
                                                          float *__restrict__ sa_, uint16_t *__restrict__ hs_,
                                                          const int *__restrict__ seq_off_, const float *__restrict__ h0_,
-                                                         float *__restrict__ hT_) {
+                                                         float *__restrict__ hT_, const int *__restrict__ state_row_) {
+    static_assert(!ROWS || (STATE && !SAVE), "indexed cache rows: the stateful forward without checkpoints");
     extern __shared__ __attribute__((aligned(16))) uint16_t sm[];
     using L = F9Smem;
     float *fm = reinterpret_cast<float *>(sm + L::end16);
@@ -115,6 +121,7 @@ __global__ __launch_bounds__(512) void wkv7c_fwd9_kernel(int T_, int H, const bf
     const int nc = T_ / kC;
     int bb, hh, c0 = 0, c1 = nc;
     [[maybe_unused]] int sbh = bh;   // STATE: the entry of h0_ / hT_ (the row's head on plain rows, the sequence's on packed rows)
+    [[maybe_unused]] bool row_zero = false;
     if (seq_off_) {  // packed rows: one workgroup pair per (sequence, head) walks only that sequence's chunks
         const int sq = bh / H;
         hh = bh - sq * H;
@@ -123,7 +130,17 @@ __global__ __launch_bounds__(512) void wkv7c_fwd9_kernel(int T_, int H, const bf
         c0 = g0 - bb * nc;
         c1 = c0 + (g1 - g0);
         bh = bb * H + hh;
-        if constexpr (STATE) {
+        if constexpr (ROWS) {
+            const int sr = state_row_[sq];
+            if (sr < 0) return;
+            row_zero = (sr & kRowZero) != 0;
+            sbh = (sr & ~kRowZero) * H + hh;
+            if (c1 <= c0) {   // no chunks: the row stays, or becomes zero
+                if (row_zero)
+                    *reinterpret_cast<float4 *>(hT_ + (long)sbh * kN * kN + (long)vh * VH * kN + threadIdx.x * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+                return;
+            }
+        } else if constexpr (STATE) {
             sbh = sq * H + hh;
             if (c1 <= c0) {   // no chunks: hT = h0; this workgroup's 32 value rows, one float4 per thread (512 x 4 = 32 x 64)
                 if (hT_) {
@@ -146,7 +163,8 @@ __global__ __launch_bounds__(512) void wkv7c_fwd9_kernel(int T_, int H, const bf
     const int pt = ltid & 31, pk = (ltid >> 5) * 8, pv = (ltid >> 5) * 4;
     const int lt = ltid >> 3, lk = (ltid & 7) * 8, lv = (ltid & 7) * 4;
 
-    const bool from_h0 = STATE && h0_ != nullptr;
+    const float *const h0p = ROWS ? hT_ : h0_;   // ROWS: one pointer for the load and the store of the row
+    const bool from_h0 = ROWS ? !row_zero : (STATE && h0_ != nullptr);
     if (!from_h0)
         for (int i = tid; i < 2 * VH * LDK; i += 512) sm[L::Sh + i] = 0;  // chunk c0 starts from S = 0
     using RawVec = decltype(Raw4<bf16_t>::r);
@@ -162,7 +180,7 @@ __global__ __launch_bounds__(512) void wkv7c_fwd9_kernel(int T_, int H, const bf
         f32x16 Smaster = zero16();  // waves 1, 2: D-layout tile (32 keys x 32 value columns) of the fp32 state
         if (from_h0 && (wave == 1 || wave == 2)) {
             // the initial state straight into the chain waves' fp32 tile and the state planes (read first in interval a, two barriers on)
-            Smaster = state_tile_load(h0_ + (long)sbh * kN * kN, vh, wave - 1, lane);
+            Smaster = state_tile_load(h0p + (long)sbh * kN * kN, vh, wave - 1, lane);
             store_T_split(Smaster, sm + L::Sh + (wave - 1) * 32, sm + L::Sl + (wave - 1) * 32, LDK, lane);
         }
         // y (and sa) of a chunk, staged in its interval b, leave at the start of the next interval a: thread (pt, pv) owns 4 value
@@ -423,11 +441,11 @@ static int launch_fwd9(bool save, int B, int T_, int H, const void *w, const voi
     if (save)
         hipLaunchKernelGGL((wkv7c_fwd9_kernel<true, STATE>), grid, block, F9Smem::bytes, st, T_, H, (const bf16_t *)w, (const bf16_t *)q,
                            (const bf16_t *)k, (const bf16_t *)v, (const bf16_t *)a, (const bf16_t *)b, tinv, (bf16_t *)y, sa, (uint16_t *)hs, seq_off,
-                           h0, hT);
+                           h0, hT, nullptr);
     else
         hipLaunchKernelGGL((wkv7c_fwd9_kernel<false, STATE>), grid, block, F9Smem::bytes, st, T_, H, (const bf16_t *)w, (const bf16_t *)q,
                            (const bf16_t *)k, (const bf16_t *)v, (const bf16_t *)a, (const bf16_t *)b, tinv, (bf16_t *)y, nullptr, nullptr,
-                           seq_off, h0, hT);
+                           seq_off, h0, hT, nullptr);
     return (int)hipGetLastError();
 }
 
@@ -443,6 +461,22 @@ int chunk_fwd9_state_seq_bf16(int B, int T_, int H, const void *w, const void *q
                               const float *h0, float *hT, hipStream_t st) {
     if (!h0 && !hT) return chunk_fwd9_bf16(B, T_, H, w, q, k, v, a, b, tinv, y, sa, hs, seq_off, nseq, st);
     return launch_fwd9<true>(sa && hs, B, T_, H, w, q, k, v, a, b, tinv, y, sa, hs, seq_off, nseq, h0, hT, st);
+}
+
+// the stateful packed forward on indexed rows of a cache field, in place (no checkpoints): sequence s of seq_off starts from and ends
+// in state[state_row[s]] (state fp32 [S,H,64,64]; state_row int32 [nseq] on the device, see ROWS above).  The grid covers all nseq
+// entries; the inactive ones return at once.
+int chunk_fwd9_state_rows_bf16(int T_, int H, const void *w, const void *q, const void *k, const void *v, const void *a, const void *b,
+                               const float *tinv, void *y, const int *seq_off, int nseq, float *state, const int *state_row,
+                               hipStream_t st) {
+    static DynLdsOnce lds_once;
+    if (hipError_t e = lds_once.ensure(reinterpret_cast<const void *>(&wkv7c_fwd9_kernel<false, true, true>), (int)F9Smem::bytes); e != hipSuccess) return (int)e;
+    (void)hipGetLastError();
+    const dim3 grid(nseq * H * 2), block(512);
+    hipLaunchKernelGGL((wkv7c_fwd9_kernel<false, true, true>), grid, block, F9Smem::bytes, st, T_, H, (const bf16_t *)w, (const bf16_t *)q,
+                       (const bf16_t *)k, (const bf16_t *)v, (const bf16_t *)a, (const bf16_t *)b, tinv, (bf16_t *)y, nullptr, nullptr,
+                       seq_off, nullptr, state, state_row);
+    return (int)hipGetLastError();
 }
 
 }  // namespace rwkv7
