@@ -670,6 +670,55 @@ int rwkv7_xy_frame_step(int B, int C, int rows, long text_shift, long speech_voc
                         unsigned char *all_done, long *n_rows, rwkv7_stream_t stream);
 int rwkv7_xy_embed_bf16(int B, int C, int D, const void *const *tables_host, const long *row, void *x, rwkv7_stream_t stream);
 
+/* ---- one XY frame per SLOT of a continuous-batching engine (csrc/xy_slots.hip; rwkvtts_amd/continuous_xy.py), where every slot runs
+ * its own request.  Logits row r belongs to slot s = row_slot[r] (row_slot NULL: s = r; rows with s outside [0, slots) are skipped;
+ * the named slots must be distinct).  A slot with live[s] == 0 is left completely untouched by both entries: nt, x, row, needs,
+ * step and seq keep their contents.  A frame is the two calls in this order on one stream:
+ * rwkv7_xy_slots_draw_f32: for every live slot and channel c < C one id from logits[r * ld + seg_off[c] .. + seg_len[c]) restricted
+ *      to the ids [allow_lo[c], allow_hi[c]) of the segment (NULL: whole segments), with the slot's own do_sample / inv_temp / top_k /
+ *      top_p; seg_off may be negative when the row holds only the allowed part of a segment (channel 0: the audio range of the text
+ *      head), so that ids keep their vocabulary values.  Philox key seed[s], counter (step[s], c): the C ids are bit-identical to a
+ *      ONE-row rwkv7_sample_rows_f32(rows = 1, nseg = C, *step = step[s], seed = seed[s]) call with the slot's parameters
+ *      (temperature = 1 / inv_temp), the same max_domain and the same logits.  Writes nt[s][0..C) and nothing else.  seg_off / seg_len /
+ *      allow_* are DEVICE int arrays of C entries; max_domain = the largest allow_hi - allow_lo (or seg_len), <= 15360.  One workgroup
+ *      per (row, channel).
+ * rwkv7_xy_slots_frame_bf16: for every live slot the rules of rwkv7_xy_frame_step for a batch of one with pos = step[s],
+ *      total = limit[s], all_done = 0, on nt[s]: a non-audio id on channel 0 starts the flush countdown (needs = C - 1 .. -1), channel 0
+ *      carries eos0 while flushing (eos0 < 0: keeps its id), channel i pads once needs < C - i; stop on step[s] + 1 >= limit[s] or on an
+ *      eos_list hit on channel 0 while not flushing; the slot also ends when the countdown reaches -1 (reference_termination = 1:
+ *      rwkv7_xy_frame_step's literal form).  Then seq[s][step[s]][0..C) = row[s][0..C) = the frame (row index clamped to seq_ld - 1),
+ *      x[s] = sum_c tables[c][row[s][c]] as rwkv7_xy_embed_bf16 forms it (0 ulp), step[s] += 1, needs[s] updated, live[s] = still
+ *      unfinished.  Every id of the frame (eos0 and pad included) must be a row of its channel's table.  One workgroup per row.
+ * All per-slot fields are DEVICE arrays of `slots` entries.  top_k_max (host): the largest top_k[] value, in [0, 64]; a slot's top_k
+ * is clamped to it; a sampled slot with top_k = 0 draws from the whole distribution (top_p is ignored there).  Errors: RWKV7_EINVAL
+ * for rows / slots / C / D / seq_ld / max_domain <= 0, a null st / logits / segment array / per-slot array / table, one of allow_lo /
+ * allow_hi without the other, n_eos > 0 without eos_list; RWKV7_ESHAPE for max_domain > 15360, top_k_max outside [0, 64], C > 16,
+ * D % 8 != 0. */
+typedef struct rwkv7_xy_slot_state {
+    long *step;                 /* frames emitted so far = output row of the next frame */
+    long *limit;                /* the request's frame budget */
+    unsigned long long *seed;   /* the request's Philox key */
+    float *inv_temp;
+    int *top_k;
+    float *top_p;
+    unsigned char *do_sample;
+    unsigned char *live;        /* 1 while the slot's request runs */
+    long *needs;                /* flush countdown, -1: not flushing */
+    long *nt;                   /* [slots][C] the drawn ids of the current frame */
+    long *row;                  /* [slots][C] the frame written last */
+    long *seq;                  /* [slots][seq_ld][C] generated frames */
+    long seq_ld;
+    const void *tables[16];     /* bf16 [V_c][D] embedding tables, C of them */
+    void *x;                    /* bf16 [slots][D]: the next decode step's input */
+    int D, C, slots, top_k_max;
+    long text_shift, speech_vocab, pad, eos0;
+    const long *eos_list;       /* n_eos DEVICE ids for the stopping criterion, or NULL */
+    int n_eos, reference_termination;
+} rwkv7_xy_slot_state;
+int rwkv7_xy_slots_draw_f32(int rows, const float *logits, long ld, const int *row_slot, const int *seg_off, const int *seg_len,
+                            const int *allow_lo, const int *allow_hi, int max_domain, const rwkv7_xy_slot_state *st, rwkv7_stream_t stream);
+int rwkv7_xy_slots_frame_bf16(int rows, const int *row_slot, const rwkv7_xy_slot_state *st, rwkv7_stream_t stream);
+
 /* the low-rank pair of the decode step in one launch: y[M,N] = act(x[M,K] @ w1[R,K]^T) @ w2[N,R]^T (+ bias); M <= 32,
  * K % 64 == 0, R in {32,64,128}, act 0 none / 1 tanh / 2 sigmoid (rwkv_s2s_single_ffn.py:497-500: w, a, v, g branches) */
 int rwkv7_lora32_bf16(int M, int N, int K, int R, int act, const void *x, const void *w1, const void *w2, const void *bias,

@@ -82,6 +82,8 @@ int ras_step_f32(int, const float *, long *, long *, long *, long *, long, int, 
 int xy_frame_step(int, int, int, long, long, long, long, long, const long *, int, int, const long *, long *, long *, long *, long *, long *,
                   unsigned char *, long *, hipStream_t);
 int xy_embed_bf16(int, int, int, const void *const *, const long *, void *, hipStream_t);
+int xy_slots_draw_f32(int, const float *, long, const int *, const int *, const int *, const int *, const int *, int, const void *, hipStream_t);
+int xy_slots_frame_bf16(int, const int *, const void *, hipStream_t);
 int decode_layer_ptrs();
 size_t decode_workspace_bytes(int, int, int, int, int, int, int, int, int);
 int decode_step_bf16(int, int, int, int, int, int, int, int, int, int, float, float, const void *const *, const void *const *, const void *,
@@ -833,6 +835,27 @@ int rwkv7_xy_embed_bf16(int B, int C, int D, const void *const *tables_host, con
     for (int c = 0; c < C && c < 16; c++)
         if (!tables_host[c]) return RWKV7_EINVAL;
     return rwkv7::xy_embed_bf16(B, C, D, tables_host, row, x, (hipStream_t)stream);
+}
+static bool xy_slot_state_ok(const rwkv7_xy_slot_state *st) {
+    if (!st || st->slots <= 0 || st->C <= 0 || st->D <= 0 || st->seq_ld <= 0 || st->n_eos < 0 || (st->n_eos > 0 && !st->eos_list)) return false;
+    if (any_null({(const void *)st->step, (const void *)st->limit, (const void *)st->seed, (const void *)st->inv_temp,
+                  (const void *)st->top_k, (const void *)st->top_p, (const void *)st->do_sample, (const void *)st->live,
+                  (const void *)st->needs, (const void *)st->nt, (const void *)st->row, (const void *)st->seq, (const void *)st->x}))
+        return false;
+    for (int c = 0; c < st->C && c < 16; c++)
+        if (!st->tables[c]) return false;
+    return true;
+}
+int rwkv7_xy_slots_draw_f32(int rows, const float *logits, long ld, const int *row_slot, const int *seg_off, const int *seg_len,
+                            const int *allow_lo, const int *allow_hi, int max_domain, const rwkv7_xy_slot_state *st, rwkv7_stream_t stream) {
+    if (rows <= 0 || max_domain <= 0 || !xy_slot_state_ok(st) || (!allow_lo != !allow_hi) ||
+        any_null({(const void *)logits, (const void *)seg_off, (const void *)seg_len}))
+        return RWKV7_EINVAL;
+    return rwkv7::xy_slots_draw_f32(rows, logits, ld, row_slot, seg_off, seg_len, allow_lo, allow_hi, max_domain, st, (hipStream_t)stream);
+}
+int rwkv7_xy_slots_frame_bf16(int rows, const int *row_slot, const rwkv7_xy_slot_state *st, rwkv7_stream_t stream) {
+    if (rows <= 0 || !xy_slot_state_ok(st)) return RWKV7_EINVAL;
+    return rwkv7::xy_slots_frame_bf16(rows, row_slot, st, (hipStream_t)stream);
 }
 int rwkv7_debug_tr16(const void *in, const int *addr, void *out, rwkv7_stream_t stream) {
     if (!in || !addr || !out) return RWKV7_EINVAL;

@@ -1,0 +1,205 @@
+// rwkvtts_amd/csrc/xy_slots.hip -- one XY frame per decode SLOT of a continuous-batching engine (rwkvtts_amd/continuous_xy.py), where
+// every slot runs its own request: its own Philox key, frame counter, frame budget, sampling parameters, flush countdown and live
+// flag, all in device memory.  Two launches per frame (the closed-batch loop of xy_llm.RWKV7XYLM.generate takes three: draw, frame
+// rules, embedding sum):
+//   1. xy_slot_draw_kernel: one workgroup per (logits row, channel) -- the C draws of a slot run side by side, not one after the other
+//      inside a workgroup (a block-wide selection costs about as much as a launch boundary).  The draw is sample_rows_kernel's for a
+//      ONE-row launch of C segments: workgroup index = channel, key = seed[s], counter = (step[s], channel).  Writes nt[s][c].
+//   2. xy_slot_frame_kernel: one workgroup per logits row.  Lane 0 applies the frame rules of xy_frame_kernel for a batch of one
+//      (pos = step[s], total = limit[s], still running) and leaves the row in LDS; after the barrier every lane adds the C embedding
+//      rows like xy_embed_kernel (bf16 rounding after each addition, channel order) with 16-byte loads.
+// A slot with live[s] == 0, and a row whose row_slot entry lies outside [0, slots), is left completely untouched by both launches.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "sampling_common.h"
+
+namespace rwkv7 {
+namespace {
+
+constexpr int kXYSlotMaxC = 16;
+
+// = rwkv7_xy_slot_state (include/rwkv7_hip.h).  Every per-slot field is a DEVICE array of `slots` entries.
+struct XYSlotState {
+    long *step, *limit;
+    unsigned long long *seed;
+    float *inv_temp;
+    int *top_k;
+    float *top_p;
+    unsigned char *do_sample, *live;
+    long *needs;
+    long *nt, *row, *seq;
+    long seq_ld;
+    const uint16_t *tables[kXYSlotMaxC];
+    uint16_t *x;
+    int D, C, slots, top_k_max;
+    long text_shift, speech_vocab, pad, eos0;
+    const long *eos_list;
+    int n_eos, reference_termination;
+};
+
+// The body repeats sample_rows_kernel's draw (csrc/sampling.hip) with the slot's parameters in place of the launch's: same loads, same
+// selection, same Philox counter for workgroup index = channel, so the id equals that kernel's bit for bit.
+template <int EPT>
+__global__ __launch_bounds__(kSmpThreads) void xy_slot_draw_kernel(const float *__restrict__ logits, long ld, const int *__restrict__ row_slot,
+                                                                   const int *__restrict__ seg_off, const int *__restrict__ seg_len,
+                                                                   const int *__restrict__ allow_lo, const int *__restrict__ allow_hi,
+                                                                   XYSlotState st) {
+    __shared__ SmpShared sm;
+    const int C = st.C;
+    const int seg = blockIdx.x % C, row = blockIdx.x / C, tid = threadIdx.x;
+    const int s = row_slot ? row_slot[row] : row;
+    if (s < 0 || s >= st.slots || !st.live[s]) return;   // uniform over the workgroup
+    const long step = st.step[s];
+    const int do_sample = st.do_sample[s] != 0;
+    const float inv_temp = do_sample ? st.inv_temp[s] : 1.f;
+    const int top_k = min(max(st.top_k[s], 0), st.top_k_max);
+    const float top_p = st.top_p[s];
+    const float *xg = logits + (long)row * ld + seg_off[seg];
+    const int n = seg_len[seg];
+    const int lo = allow_lo ? max(allow_lo[seg], 0) : 0, hi = allow_hi ? min(allow_hi[seg], n) : n;
+    const int m = hi - lo;
+    if (m < 1) return;   // an empty allowed range: nothing is read (uniform)
+    Vals<EPT> x;
+#pragma unroll
+    for (int e = 0; e < EPT; e++) {
+        const int j = tid + kSmpThreads * e;
+        const float t = xg[lo + min(j, m - 1)];
+        x.v[e] = j < m ? t * inv_temp : -INFINITY;
+    }
+    int choice;
+    if (!do_sample) {
+        choice = key_idx(block_max(x.local_max(), sm, 0));
+    } else {
+        const uint2 key = make_uint2((uint32_t)st.seed[s], (uint32_t)(st.seed[s] >> 32));
+        const uint4 r = philox(make_uint4((uint32_t)step, (uint32_t)((uint64_t)step >> 32), (uint32_t)seg, 0x5a17u), key);
+        if (top_k > 0) {
+            const int nc = select_bins(x, sm, min(top_k, m), true);
+            const float ej = tid < nc ? __expf(sm.cand_v[tid] - sm.cand_v[0]) : 0.f;
+            float z;
+            const float cj = block_scan(ej, z, sm);
+            const bool keep = tid < nc && (tid == 0 || cj - ej < top_p * z);
+            float kept;
+            (void)block_scan(keep ? ej : 0.f, kept, sm);
+            const float target = u01(r.x) * kept;
+            if (tid == 0) sm.pick[1] = 0;
+            __syncthreads();
+            if (keep && cj <= target) atomicAdd(&sm.pick[1], 1);
+            __syncthreads();
+            float f;
+            (void)block_scan(keep ? 1.f : 0.f, f, sm);
+            const int nk = (int)f;
+            if (tid == 0) sm.pick[0] = nk > 0 ? sm.cand_i[min(sm.pick[1], nk - 1)] : 0;
+            __syncthreads();
+            choice = sm.pick[0];
+        } else {
+            const unsigned long long k = block_max(x.local_max(), sm, 0);
+            int i0, i1;
+            draw_full(x, sm, key_val(k), -1, u01(r.x), 0.f, i0, i1);
+            choice = i0 >= 0 ? i0 : key_idx(k);
+        }
+    }
+    choice = min(max(choice, 0), m - 1);
+    if (tid == 0) st.nt[(long)s * C + seg] = lo + choice;
+}
+
+// Frame rules (xy_frame_kernel for B = 1, pos = step[s], total = limit[s], all_done = 0) + the next input (xy_embed_kernel).
+__global__ __launch_bounds__(256) void xy_slot_frame_kernel(const int *__restrict__ row_slot, XYSlotState st) {
+    __shared__ long frame[kXYSlotMaxC];
+    __shared__ long next[3];   // needs, step, live after this frame
+    const int C = st.C, D = st.D, tid = threadIdx.x;
+    const int s = row_slot ? row_slot[blockIdx.x] : (int)blockIdx.x;
+    if (s < 0 || s >= st.slots || !st.live[s]) return;   // uniform: every lane reads live[s] before the barrier, lane 0 writes it after
+    if (tid == 0) {
+        const long p0 = st.step[s];
+        long needs = st.needs[s];
+        const long *t = st.nt + (long)s * C;
+        const long t0 = t[0];
+        const bool is_audio = t0 >= st.text_shift && t0 < st.text_shift + st.speech_vocab;
+        if (!is_audio && needs < 0) needs = C - 1;
+        const bool flushing = needs >= 0;
+        const long c0 = (st.eos0 >= 0 && flushing) ? st.eos0 : t0;
+        frame[0] = c0;
+        for (int i = 1; i < C; i++) frame[i] = (flushing && needs < C - i) ? st.pad : t[i];
+        if (flushing) needs -= 1;
+        const long p1 = p0 + 1;
+        const long total = st.limit[s];
+        bool stop = total >= 0 && p1 >= total;
+        bool hit = false;
+        for (int e = 0; e < st.n_eos; e++) hit |= c0 == st.eos_list[e];
+        stop |= st.reference_termination ? hit : (hit && !flushing);
+        const bool gone = st.reference_termination ? needs == -1 : (needs == -1 && flushing);
+        next[0] = needs;
+        next[1] = p1;
+        next[2] = (!stop && !gone) ? 1 : 0;
+    }
+    __syncthreads();
+    if (tid < C) {
+        const long p0 = next[1] - 1;
+        const long pw = min(max(p0, 0L), st.seq_ld - 1);   // clamped like xy_frame_kernel
+        st.seq[((long)s * st.seq_ld + pw) * C + tid] = frame[tid];
+        st.row[(long)s * C + tid] = frame[tid];
+    }
+    if (tid == 0) {
+        st.needs[s] = next[0];
+        st.step[s] = next[1];
+        st.live[s] = (unsigned char)next[2];
+    }
+    for (int d = tid * 8; d < D; d += 256 * 8) {
+        float acc[8];
+#pragma unroll
+        for (int c = 0; c < kXYSlotMaxC; c++) {
+            if (c < C) {
+                const uint4 r = *reinterpret_cast<const uint4 *>(st.tables[c] + frame[c] * D + d);
+                const uint32_t w[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const float lo = __uint_as_float(w[j] << 16), hi = __uint_as_float(w[j] & 0xffff0000u);
+                    if (c == 0) {
+                        acc[2 * j] = lo;
+                        acc[2 * j + 1] = hi;
+                    } else {   // bf16 + bf16 -> bf16 (round to nearest even), as torch adds two bf16 tensors
+                        float s0 = acc[2 * j] + lo, s1 = acc[2 * j + 1] + hi;
+                        uint32_t u0 = __float_as_uint(s0), u1 = __float_as_uint(s1);
+                        u0 += 0x7fffu + ((u0 >> 16) & 1u);
+                        u1 += 0x7fffu + ((u1 >> 16) & 1u);
+                        acc[2 * j] = __uint_as_float(u0 & 0xffff0000u);
+                        acc[2 * j + 1] = __uint_as_float(u1 & 0xffff0000u);
+                    }
+                }
+            }
+        }
+        uint4 o;
+        uint32_t *ow = reinterpret_cast<uint32_t *>(&o);
+#pragma unroll
+        for (int j = 0; j < 4; j++) ow[j] = (__float_as_uint(acc[2 * j]) >> 16) | (__float_as_uint(acc[2 * j + 1]) & 0xffff0000u);
+        *reinterpret_cast<uint4 *>(st.x + (long)s * D + d) = o;
+    }
+}
+
+}  // namespace
+
+int xy_slots_draw_f32(int rows, const float *logits, long ld, const int *row_slot, const int *seg_off, const int *seg_len,
+                      const int *allow_lo, const int *allow_hi, int max_domain, const void *st_, hipStream_t stream) {
+    const XYSlotState st = *(const XYSlotState *)st_;
+    if (max_domain > kSmpMaxN || st.top_k_max < 0 || st.top_k_max > 64 || st.C > kXYSlotMaxC || st.D % 8 != 0) return -4;   // RWKV7_ESHAPE
+    (void)hipGetLastError();
+    const dim3 grid(rows * st.C), block(kSmpThreads);
+    if (max_domain <= kEptS * kSmpThreads)
+        xy_slot_draw_kernel<kEptS><<<grid, block, 0, stream>>>(logits, ld, row_slot, seg_off, seg_len, allow_lo, allow_hi, st);
+    else if (max_domain <= kEptM * kSmpThreads)
+        xy_slot_draw_kernel<kEptM><<<grid, block, 0, stream>>>(logits, ld, row_slot, seg_off, seg_len, allow_lo, allow_hi, st);
+    else
+        xy_slot_draw_kernel<kEptL><<<grid, block, 0, stream>>>(logits, ld, row_slot, seg_off, seg_len, allow_lo, allow_hi, st);
+    return (int)hipGetLastError();
+}
+
+int xy_slots_frame_bf16(int rows, const int *row_slot, const void *st_, hipStream_t stream) {
+    const XYSlotState st = *(const XYSlotState *)st_;
+    if (st.C > kXYSlotMaxC || st.D % 8 != 0) return -4;
+    (void)hipGetLastError();
+    xy_slot_frame_kernel<<<dim3(rows), dim3(256), 0, stream>>>(row_slot, st);
+    return (int)hipGetLastError();
+}
+
+}  // namespace rwkv7
