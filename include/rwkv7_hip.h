@@ -719,6 +719,48 @@ int rwkv7_xy_slots_draw_f32(int rows, const float *logits, long ld, const int *r
                             const int *allow_lo, const int *allow_hi, int max_domain, const rwkv7_xy_slot_state *st, rwkv7_stream_t stream);
 int rwkv7_xy_slots_frame_bf16(int rows, const int *row_slot, const rwkv7_xy_slot_state *st, rwkv7_stream_t stream);
 
+/* ---- CosyVoice's repetition-aware draw per SLOT of a continuous-batching engine (csrc/ras_slots.hip; rwkvtts_amd/continuous_cosy.py),
+ * where every slot runs its own utterance.  Logits row r (fp32, V ids, row stride ld) belongs to slot s = row_slot[r] (row_slot NULL:
+ * s = r; rows with s outside [0, slots) are skipped).  Two rows that name the same slot are a caller error: the slot's state would
+ * be written by two workgroups.  A slot with live[s] == 0 is left completely untouched, its x row included.
+ * rwkv7_ras_slots_f32: a live slot draws one id as rwkv7_ras_step_f32 does: nucleus over the softmax probabilities with top_p[s] /
+ *      top_k[s] (clamped to [1, top_k_max]), EOS removed per stage while step[s] < n_ignore[s], and the draw from the full
+ *      distribution when the candidate already occurs >= win_size * tau_r[s] times in the slot's ring.  Philox key seed[s], counter
+ *      (step[s] lo, step[s] hi, 0, 0x7a5).  Contract: the id, the ring, ptr[s] and step[s] after the call are bit-identical to ONE
+ *      rwkv7_ras_step_f32 call with the slot's logits row, ring, pointer, step, n_ignore, parameters and seed.  Then the streaming
+ *      loop's bookkeeping: ids[s] = id; if id != eos: seq[s][n_out[s]] = id (when n_out[s] < seq_ld), recent[s][ptr[s]] = id,
+ *      ptr[s] = (ptr[s] + 1) % win_size, n_out[s] += 1, x[s] = emb[id] (emb NULL: no copy); step[s] += 1;
+ *      live[s] = id != eos && step[s] < limit[s].  One workgroup per row.
+ * All per-slot fields are DEVICE arrays of `slots` entries.  Errors (nothing is launched): RWKV7_EINVAL for rows / V / slots /
+ * seq_ld <= 0, a null st / logits / per-slot array, emb without x (or with D <= 0); RWKV7_ESHAPE for V > 15360, win_size outside
+ * [1, min(128, win_ld)], top_k_max outside [1, 128], D % 8 != 0. */
+typedef struct rwkv7_ras_slot_state {
+    long *step;                 /* loop index of the utterance: draws made so far */
+    long *limit;                /* max_len: the slot ends when step reaches it */
+    long *n_ignore;             /* EOS is rejected while step < n_ignore */
+    unsigned long long *seed;   /* the request's Philox key */
+    int *top_k;
+    float *top_p;
+    float *tau_r;
+    unsigned char *live;        /* 1 while the slot's request runs */
+    long *recent;               /* [slots][win_ld] ring of the last win_size emitted ids, -1 = empty */
+    long win_ld;
+    long *ptr;                  /* write position in the ring */
+    long *ids;                  /* last drawn id, EOS included */
+    long *n_out;                /* emitted (non-EOS) ids so far */
+    long *seq;                  /* [slots][seq_ld] emitted ids */
+    long seq_ld;
+    const void *emb;            /* bf16 [V][D] speech embedding table, or NULL */
+    void *x;                    /* bf16 [slots][D]: the next decode step's input */
+    int D;
+    int slots;
+    int win_size;               /* <= 128, <= win_ld */
+    int top_k_max;              /* the largest top_k[] value, in [1, 128] */
+    long eos;
+} rwkv7_ras_slot_state;
+int rwkv7_ras_slots_f32(int rows, int V, const float *logits, long ld, const int *row_slot, const rwkv7_ras_slot_state *st,
+                        rwkv7_stream_t stream);
+
 /* the low-rank pair of the decode step in one launch: y[M,N] = act(x[M,K] @ w1[R,K]^T) @ w2[N,R]^T (+ bias); M <= 32,
  * K % 64 == 0, R in {32,64,128}, act 0 none / 1 tanh / 2 sigmoid (rwkv_s2s_single_ffn.py:497-500: w, a, v, g branches) */
 int rwkv7_lora32_bf16(int M, int N, int K, int R, int act, const void *x, const void *w1, const void *w2, const void *bias,

@@ -84,6 +84,7 @@ int xy_frame_step(int, int, int, long, long, long, long, long, const long *, int
 int xy_embed_bf16(int, int, int, const void *const *, const long *, void *, hipStream_t);
 int xy_slots_draw_f32(int, const float *, long, const int *, const int *, const int *, const int *, const int *, int, const void *, hipStream_t);
 int xy_slots_frame_bf16(int, const int *, const void *, hipStream_t);
+int ras_slots_f32(int, int, const float *, long, const int *, const void *, hipStream_t);
 int decode_layer_ptrs();
 size_t decode_workspace_bytes(int, int, int, int, int, int, int, int, int);
 int decode_step_bf16(int, int, int, int, int, int, int, int, int, int, float, float, const void *const *, const void *const *, const void *,
@@ -856,6 +857,17 @@ int rwkv7_xy_slots_draw_f32(int rows, const float *logits, long ld, const int *r
 int rwkv7_xy_slots_frame_bf16(int rows, const int *row_slot, const rwkv7_xy_slot_state *st, rwkv7_stream_t stream) {
     if (rows <= 0 || !xy_slot_state_ok(st)) return RWKV7_EINVAL;
     return rwkv7::xy_slots_frame_bf16(rows, row_slot, st, (hipStream_t)stream);
+}
+int rwkv7_ras_slots_f32(int rows, int V, const float *logits, long ld, const int *row_slot, const rwkv7_ras_slot_state *st,
+                        rwkv7_stream_t stream) {
+    if (rows <= 0 || V <= 0 || !st || !logits) return RWKV7_EINVAL;
+    if (any_null({(const void *)st->step, (const void *)st->limit, (const void *)st->n_ignore, (const void *)st->seed,
+                  (const void *)st->top_k, (const void *)st->top_p, (const void *)st->tau_r, (const void *)st->live,
+                  (const void *)st->recent, (const void *)st->ptr, (const void *)st->ids, (const void *)st->n_out,
+                  (const void *)st->seq}) ||
+        st->slots <= 0 || st->seq_ld <= 0 || (st->emb && (!st->x || st->D <= 0)))
+        return RWKV7_EINVAL;
+    return rwkv7::ras_slots_f32(rows, V, logits, ld, row_slot, st, (hipStream_t)stream);
 }
 int rwkv7_debug_tr16(const void *in, const int *addr, void *out, rwkv7_stream_t stream) {
     if (!in || !addr || !out) return RWKV7_EINVAL;

@@ -1,0 +1,140 @@
+// rwkvtts_amd/csrc/ras_slots.hip -- CosyVoice's repetition-aware draw per decode SLOT of a continuous-batching engine
+// (rwkvtts_amd/continuous_cosy.py), where every slot runs its own utterance: its own Philox key, loop index, EOS bar (n_ignore),
+// length bound, top_k / top_p / tau_r, ring of recent ids and live flag, all in device memory.  One launch per captured step:
+// one workgroup per logits row draws the slot's id as ras_step_kernel (csrc/sampling.hip) does for B = 1 and then does what the
+// streaming loop of RWKV7CosyLM.inference does with it (ring, emitted ids, next input embedding, loop index, end of utterance).
+// A slot with live[s] == 0, and a row whose row_slot entry lies outside [0, slots), is left completely untouched.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "sampling_common.h"
+
+namespace rwkv7 {
+namespace {
+
+// = rwkv7_ras_slot_state (include/rwkv7_hip.h).  Every per-slot field is a DEVICE array of `slots` entries.
+struct RasSlotState {
+    long *step, *limit, *n_ignore;
+    unsigned long long *seed;
+    int *top_k;
+    float *top_p, *tau_r;
+    unsigned char *live;
+    long *recent;
+    long win_ld;
+    long *ptr, *ids, *n_out, *seq;
+    long seq_ld;
+    const uint16_t *emb;
+    uint16_t *x;
+    int D, slots, win_size, top_k_max;
+    long eos;
+};
+
+// The body repeats ras_step_kernel's draw statement for statement, with the slot's fields in place of the launch's arguments, so
+// that the id equals that kernel's bit for bit and csrc/sampling.hip stays as it is.  Every lane reads live[s], step[s] and the
+// ring before the first barrier; lane 0 writes them after the last one, so the early exit is uniform over the workgroup.
+template <int EPT>
+__global__ __launch_bounds__(kSmpThreads) void ras_slots_kernel(int V, const float *__restrict__ logits_, long ld,
+                                                                const int *__restrict__ row_slot, RasSlotState a) {
+    __shared__ SmpShared sm;
+    const int tid = threadIdx.x;
+    const int s = row_slot ? row_slot[blockIdx.x] : (int)blockIdx.x;
+    if (s < 0 || s >= a.slots || !a.live[s]) return;
+    const float *logits = logits_ + (long)blockIdx.x * ld;
+    Vals<EPT> x;
+#pragma unroll
+    for (int e = 0; e < EPT; e++) {
+        const int j = tid + kSmpThreads * e;
+        const float t = logits[min(j, V - 1)];
+        x.v[e] = j < V ? t : -INFINITY;
+    }
+    const long st = a.step[s];
+    const int win_size = a.win_size, eos = (int)a.eos;
+    long *recent = a.recent + (long)s * a.win_ld;
+    long rc[2];   // the ring of recent ids, one entry per lane of wave 0 (win_size <= 128)
+    rc[0] = recent[min(tid, win_size - 1)];
+    rc[1] = recent[min(64 + tid, win_size - 1)];
+    const float top_p = a.top_p[s], tau_r = a.tau_r[s];
+    const int top_k = min(max(a.top_k[s], 1), a.top_k_max);
+    const bool ignore_eos = st < a.n_ignore[s];
+    const uint2 key = make_uint2((uint32_t)a.seed[s], (uint32_t)(a.seed[s] >> 32));
+    const uint4 r = philox(make_uint4((uint32_t)st, (uint32_t)((uint64_t)st >> 32), 0u, 0x7a5u), key);
+    const unsigned long long kmx = block_max(x.local_max(), sm, 0);
+    const float mx = key_val(kmx);
+    const int imx = key_idx(kmx);
+    float zs = 0.f;
+#pragma unroll
+    for (int e = 0; e < EPT; e++) zs += __expf(x.v[e] - mx);
+    const float z = block_sum(zs, sm);
+    int full, alt;
+    draw_full(x, sm, mx, ignore_eos ? eos : -1, u01(r.x), u01(r.y), full, alt);
+    if (full < 0) full = imx;
+    if (alt < 0) alt = imx;
+    const int nc = select_bins(x, sm, min(top_k, V), false);
+    const float pj = tid < nc ? __expf(sm.cand_v[tid] - mx) / z : 0.f;
+    float tot;
+    const float cj = block_scan(pj, tot, sm);
+    const bool keep = tid < nc && cj - pj < top_p;
+    const float wj = keep && !(ignore_eos && sm.cand_i[min(tid, kSmpMaxCand - 1)] == eos) ? pj : 0.f;
+    float mass;
+    const float mj = block_scan(wj, mass, sm);
+    if (tid == 0) {
+        sm.pick[0] = 0x7fffffff;
+        sm.pick[1] = -1;
+    }
+    __syncthreads();
+    const float target = u01(r.z) * mass;
+    if (wj > 0.f) {
+        if (mj > target) atomicMin(&sm.pick[0], tid);
+        atomicMax(&sm.pick[1], tid);
+    }
+    __syncthreads();
+    if (tid < 64) {
+        int cand = alt;
+        if (mass > 0.f) cand = sm.cand_i[sm.pick[0] != 0x7fffffff ? sm.pick[0] : sm.pick[1]];
+        int rep = 0;
+        for (int w0 = 0; w0 < win_size; w0 += 64) rep += __popcll(__ballot(w0 + tid < win_size && rc[w0 / 64] == (long)cand));
+        if (tid == 0) sm.sel[3] = (unsigned)((float)rep >= (float)win_size * tau_r ? full : cand);
+    }
+    __syncthreads();
+    // every thread holds the same id (it came out of LDS after a barrier); all reads of the slot's state that other lanes make lie
+    // before that barrier
+    const long id = min(max((int)sm.sel[3], 0), V - 1);
+    const bool emit = id != (long)eos;   // the reference appends emitted ids only
+    if (tid == 0) {
+        a.ids[s] = id;
+        if (emit) {
+            const long n = a.n_out[s], p = a.ptr[s];
+            if (n >= 0 && n < a.seq_ld) a.seq[(long)s * a.seq_ld + n] = id;
+            if (p >= 0 && p < win_size) recent[p] = id;
+            a.ptr[s] = (p + 1) % win_size;
+            a.n_out[s] = n + 1;
+        }
+        a.step[s] = st + 1;
+        a.live[s] = emit && st + 1 < a.limit[s];
+    }
+    if (emit && a.emb) {
+        const uint16_t *src = a.emb + id * a.D;
+        uint16_t *dst = a.x + (long)s * a.D;
+        for (int d = tid * 8; d < a.D; d += kSmpThreads * 8) *reinterpret_cast<uint4 *>(dst + d) = *reinterpret_cast<const uint4 *>(src + d);
+    }
+}
+
+}  // namespace
+
+int ras_slots_f32(int rows, int V, const float *logits, long ld, const int *row_slot, const void *st_, hipStream_t stream) {
+    const RasSlotState st = *(const RasSlotState *)st_;
+    if (V > kSmpMaxN || st.win_size < 1 || st.win_size > 128 || st.win_size > st.win_ld || st.top_k_max < 1 || st.top_k_max > kSmpMaxCand ||
+        (st.emb && st.D % 8 != 0))
+        return -4;   // RWKV7_ESHAPE
+    (void)hipGetLastError();
+    const dim3 grid(rows), block(kSmpThreads);
+    if (V <= kEptS * kSmpThreads)
+        ras_slots_kernel<kEptS><<<grid, block, 0, stream>>>(V, logits, ld, row_slot, st);
+    else if (V <= kEptM * kSmpThreads)
+        ras_slots_kernel<kEptM><<<grid, block, 0, stream>>>(V, logits, ld, row_slot, st);
+    else
+        ras_slots_kernel<kEptL><<<grid, block, 0, stream>>>(V, logits, ld, row_slot, st);
+    return (int)hipGetLastError();
+}
+
+}  // namespace rwkv7

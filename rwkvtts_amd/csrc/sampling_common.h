@@ -1,4 +1,4 @@
-// rwkvtts_amd/csrc/sampling_common.h -- what the token-draw kernels share (csrc/sampling.hip, csrc/xy_slots.hip): the Philox generator,
+// rwkvtts_amd/csrc/sampling_common.h -- what the token-draw kernels share (csrc/sampling.hip, csrc/xy_slots.hip, csrc/ras_slots.hip): the Philox generator,
 // the (value, index) keys and block-wide reductions, the top-k selections and the multinomial draw.  Everything here is inline
 // device code in an anonymous namespace: each translation unit gets its own copy.
 #pragma once
