@@ -578,6 +578,17 @@ int rwkv7_decode_step_bf16(const rwkv7_decode_dims *dims, const void *const *lay
 int rwkv7_decode_step_tbl_bf16(const rwkv7_decode_dims *dims, const void *const *layer_tbl, const void *const *layer_tbl_host,
                                const void *x_in, const void *norm_w, const void *norm_b, const void *head_w, const void *head_b,
                                float *logits, void *workspace, int persistent, rwkv7_stream_t stream);
+/* the same step for B = 33 .. 128 sequences (csrc/decode_step_wide.hip): RT = ceil(B / 32) row tiles of 32, one launch per phase, and
+ * every weight is streamed ONCE per step -- a GEMV item loads its weight fragments once per k-step and multiplies them against the RT
+ * activation tiles in registers.  Same layer_tbl, tensors and in-place state as above with B rows; layer_tbl_host may be NULL (the
+ * phase kernels then read their row of the device table).  Rows 32 g .. 32 g + 31 get bit for bit what rwkv7_decode_step_bf16 gives a
+ * batch made of those rows; rows >= B of logits and state are never written.  workspace: rwkv7_decode_wide_workspace_bytes() bytes
+ * (the same for every B of one row tile; 0 for B <= 32, B > 128 or an uncovered shape), 256-byte aligned, owned by the caller.  There
+ * is no persistent variant.  Errors: as above with B in [33,128]; the arguments are checked before the first launch. */
+size_t rwkv7_decode_wide_workspace_bytes(const rwkv7_decode_dims *dims);
+int rwkv7_decode_step_wide_bf16(const rwkv7_decode_dims *dims, const void *const *layer_tbl, const void *const *layer_tbl_host,
+                                const void *x_in, const void *norm_w, const void *norm_b, const void *head_w, const void *head_b,
+                                float *logits, void *workspace, rwkv7_stream_t stream);
 
 /* ---- token draws of the generation loops, one launch each (csrc/sampling.hip).
  *

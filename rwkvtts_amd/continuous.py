@@ -1,9 +1,9 @@
 """Continuous batching: a decode batch that admits new requests while it runs ("persistent multi-request decode").
 
 GraphDecoder runs a closed batch until its longest sequence ends, so a slot whose request finished early idles until then.  Here
-every one of up to 32 SLOTS (rows of the step kernel's batch) runs its own request:
+every one of up to 128 SLOTS (rows of the step kernel's batch) runs its own request:
 
-  * one captured step: DecodeStep on the live cache, then rwkv7_sample_slots_f32 (csrc/sampling.hip) on its logits, which draws
+  * one captured step: DecodeStep (WideDecodeStep above 32 slots: decode.step_for) on the live cache, then rwkv7_sample_slots_f32 (csrc/sampling.hip) on its logits, which draws
     every live slot's id with that slot's own key, step counter and sampling parameters and does the slot's bookkeeping (output
     column, next input embedding, step, live flag);
   * admission, eagerly between replays on the same stream: pending requests in FIFO order take free slots, their cache rows are
@@ -28,6 +28,7 @@ import torch
 
 from . import _lib
 from .backbone import Cache
+from .decode import check_slots, step_class, step_for
 from .sampling import MAX_TOP_K, RowSampler, fresh_seed
 
 
@@ -135,7 +136,7 @@ def sample_slots(logits: torch.Tensor, st: SlotState, row_slot: Optional[torch.T
 class ContinuousDecoder:
     """eng = ContinuousDecoder(model, slots=32, ...); h = eng.submit(...); eng.step() -> [(handle, ids)]; eng.run() -> {handle: ids}.
 
-    model: a bf16 RWKV7ForSpeech / RWKV7ForCausalLM on the HIP device that the step kernel covers (DecodeStep.supported); slots <= 32.
+    model: a bf16 RWKV7ForSpeech / RWKV7ForCausalLM on the HIP device that the step kernel covers (DecodeStep.supported); slots in 1..32, or 64, 96 or 128.
     A request's ids run up to and including its EOS, or up to its max_new_tokens (<= max_new_tokens_cap), with no pad tail; they are
     device int64 tensors.  pad_token_id is accepted for signature compatibility with GraphDecoder and not used: no pad is emitted.
 
@@ -148,12 +149,10 @@ class ContinuousDecoder:
     def __init__(self, model, slots: int = 32, max_new_tokens_cap: int = 3000, eos_token_id: Optional[int] = None,
                  pad_token_id: Optional[int] = None, suppress_tokens: Optional[Sequence[int]] = None, check_every: int = 16,
                  admission: str = "eager", prefill_max_seqs: int = 8, prefill_buckets: Sequence[int] = (256, 512, 1024, 2048, 4096)):
-        from .decode import DecodeStep
         if admission not in ("eager", "graph"):
             raise ValueError(f"admission = {admission!r}: 'eager' or 'graph'")
         self.admission = admission
-        if not 1 <= slots <= 32:
-            raise ValueError(f"slots = {slots}: the step kernel's batch is 1..32")
+        check_slots(slots)   # 1..32, or 64 / 96 / 128: ValueError before anything touches the device
         if max_new_tokens_cap < 1 or check_every < 1:
             raise ValueError("max_new_tokens_cap and check_every must be >= 1")
         self.model = model.eval()
@@ -163,7 +162,7 @@ class ContinuousDecoder:
         self.eos = None if eos_token_id is None else int(eos_token_id)
         self.pad = pad_token_id
         self.cache = Cache.zeros(m.config, slots, dev, m.dtype)
-        why = DecodeStep.supported(m.model, m.lm_head, self.cache)
+        why = step_class(slots).supported(m.model, m.lm_head, self.cache)
         if why is None and m.dtype != torch.bfloat16:
             why = "the model must be bf16"
         emb_w = m.get_input_embeddings().weight.detach()
@@ -213,7 +212,7 @@ class ContinuousDecoder:
         self.st = st
 
         self.sched = SlotScheduler(slots)
-        self.dstep = DecodeStep(m.model, m.lm_head, self.cache)
+        self.dstep = step_for(m.model, m.lm_head, self.cache)
         # capture the step.  Every slot is idle (live = 0): the draw writes nothing, and the warm-up's change to the state of idle
         # rows does not matter (admission resets a row before it is used)
         side = torch.cuda.Stream()

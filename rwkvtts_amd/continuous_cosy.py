@@ -1,9 +1,9 @@
 """Continuous batching for the Cosy model (RWKV7CosyLM): the engine of continuous.py with CosyVoice's repetition-aware draw per slot.
 
 RWKV7CosyLM.inference serves one utterance per process: one ring of recent ids, one loop index, one EOS bar, one key, and the id
-crosses to the host every token.  Here every one of up to 32 SLOTS runs its own utterance:
+crosses to the host every token.  Here every one of up to 128 SLOTS runs its own utterance:
 
-  * one captured step: DecodeStep on the live cache, then rwkv7_ras_slots_f32 (csrc/ras_slots.hip) on its logits, which draws every
+  * one captured step: DecodeStep (WideDecodeStep above 32 slots: decode.step_for) on the live cache, then rwkv7_ras_slots_f32 (csrc/ras_slots.hip) on its logits, which draws every
     live slot's id as rwkv7_ras_step_f32 does for B = 1 -- with the slot's own key, loop index, n_ignore, top_k / top_p / tau_r and
     ring -- and does the streaming loop's bookkeeping (ring, emitted ids, next input embedding, loop index, end of utterance);
   * admission as in ContinuousDecoder ("eager": packed prefill through RWKV7Model(..., cache_rows=...); "graph":
@@ -25,6 +25,7 @@ import torch
 
 from . import _lib
 from .backbone import Cache
+from .decode import check_slots, step_class, step_for
 from .continuous import SlotScheduler
 from .sampling import MAX_DOMAIN, fresh_seed
 
@@ -134,7 +135,7 @@ class ContinuousCosyDecoder:
     eng.run() -> {handle: ids}; eng.stream() yields (handle, new_ids, finished) at every read-back.
 
     model: a bf16 RWKV7CosyLM on the HIP device that the step kernel covers, with a head of speech_token_size + 1 rows (the condition
-    inference() uses for its fused path); slots <= 32.  A request's result is a device int64 tensor of its emitted ids -- the ids
+    inference() uses for its fused path); slots in 1..32, or 64, 96 or 128.  A request's result is a device int64 tensor of its emitted ids -- the ids
     inference() would yield, without the EOS -- at most its max_len (<= max_len_cap).  win_size is the engine's; top_p and tau_r are
     defaults that submit() may override per request.  admission / prefill_max_seqs / prefill_buckets: as in ContinuousDecoder.
 
@@ -146,14 +147,12 @@ class ContinuousCosyDecoder:
                  prefill_buckets: Sequence[int] = (256, 512, 1024, 2048, 4096)):
         if admission not in ("eager", "graph"):
             raise ValueError(f"admission = {admission!r}: 'eager' or 'graph'")
-        if not 1 <= slots <= 32:
-            raise ValueError(f"slots = {slots}: the step kernel's batch is 1..32")
+        check_slots(slots)   # 1..32, or 64 / 96 / 128: ValueError before anything touches the device
         if max_len_cap < 1 or check_every < 1:
             raise ValueError("max_len_cap and check_every must be >= 1")
         if not 1 <= win_size <= MAX_WIN:
             raise ValueError(f"win_size = {win_size}: 1..{MAX_WIN}")
         self.admission = admission
-        from .decode import DecodeStep
         self.model = m = model.eval()
         self.eos = int(m.speech_token_size)
         self.V = V = m.lm_head.weight.shape[0]
@@ -170,7 +169,7 @@ class ContinuousCosyDecoder:
         self.device, self.slots, self.cap, self.check_every = dev, slots, int(max_len_cap), int(check_every)
         self.win_size, self.top_p, self.tau_r = int(win_size), float(top_p), float(tau_r)
         self.cache = Cache.zeros(m.config, slots, dev, dtype)
-        why = DecodeStep.supported(m.model, m.lm_head, self.cache)
+        why = step_class(slots).supported(m.model, m.lm_head, self.cache)
         emb_w = m.speech_embedding.weight.detach()
         if why is None and not (emb_w.dtype == torch.bfloat16 and emb_w.is_contiguous() and emb_w.shape[1] % 8 == 0 and emb_w.shape[0] >= V):
             why = "the speech embedding table must be a contiguous bf16 [>= V, D] with D % 8 == 0"
@@ -203,7 +202,7 @@ class ContinuousCosyDecoder:
 
         self.sched = SlotScheduler(slots)
         self._extra: Dict[int, float] = {}   # handle -> tau_r: what the scheduler's request does not carry
-        self.dstep = DecodeStep(m.model, m.lm_head, self.cache)
+        self.dstep = step_for(m.model, m.lm_head, self.cache)
         # capture the step with every slot idle (live = 0): the draw writes nothing, and what the warm-up does to the state of idle
         # rows does not matter (admission resets a row before it is used)
         side = torch.cuda.Stream()

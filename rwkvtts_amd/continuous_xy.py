@@ -1,9 +1,9 @@
 """Continuous batching for the multi-channel XY model (RWKV7XYLM): the engine of continuous.py with an XY FRAME as its unit.
 
 RWKV7XYLM.generate is a closed batch: one position counter and one `all finished` flag for the batch, one seed and one set of
-sampling parameters, and a Philox counter that contains the batch row.  Here every one of up to 32 SLOTS runs its own request:
+sampling parameters, and a Philox counter that contains the batch row.  Here every one of up to 128 SLOTS runs its own request:
 
-  * one captured step: DecodeStep on the live cache with the C heads as ONE concatenated projection (channel 0 sliced to its audio
+  * one captured step: DecodeStep (WideDecodeStep above 32 slots: decode.step_for) on the live cache with the C heads as ONE concatenated projection (channel 0 sliced to its audio
     rows, as generate does), then the two launches of csrc/xy_slots.hip: rwkv7_xy_slots_draw_f32 draws the C ids of every live
     slot with the slot's own key, frame counter and sampling parameters, rwkv7_xy_slots_frame_bf16 applies the frame rules
     (flush countdown, EOS / pad substitution, stopping) per slot, appends the frame, forms the next input embedding sum and
@@ -29,6 +29,7 @@ import torch
 
 from . import _lib
 from .backbone import Cache
+from .decode import check_slots, step_class, step_for
 from .continuous import SlotScheduler
 from .sampling import MAX_DOMAIN, MAX_TOP_K, RowSampler, XYEmbed, fresh_seed
 
@@ -110,7 +111,7 @@ class ContinuousXYDecoder:
     """eng = ContinuousXYDecoder(model, slots=32, ...); h = eng.submit(input_ids [T, C], ...); eng.step() -> [(handle, frames)];
     eng.run() -> {handle: frames}.
 
-    model: a bf16 RWKV7XYLM on the HIP device that the step kernel covers; slots <= 32.  A request's frames are a device int64
+    model: a bf16 RWKV7XYLM on the HIP device that the step kernel covers; slots in 1..32, or 64, 96 or 128.  A request's frames are a device int64
     [n, C] tensor: the frames up to and including the one on which the request ended (budget, EOS on channel 0, or the end of a
     flush) -- the rows RWKV7XYLM.generate would append for B = 1.  Channel 0 is restricted to the audio range, as in generate, and
     its head is sliced to those rows (the full 66 661-id head is outside the draw's domain).  eos_token_id: a channel-0 id that ends a
@@ -120,8 +121,7 @@ class ContinuousXYDecoder:
                  admission: str = "eager", prefill_max_seqs: int = 8, prefill_buckets: Sequence[int] = (256, 512, 1024, 2048, 4096)):
         if admission not in ("eager", "graph"):
             raise ValueError(f"admission = {admission!r}: 'eager' or 'graph'")
-        if not 1 <= slots <= 32:
-            raise ValueError(f"slots = {slots}: the step kernel's batch is 1..32")
+        check_slots(slots)   # 1..32, or 64 / 96 / 128: ValueError before anything touches the device
         if max_new_frames_cap < 1 or check_every < 1:
             raise ValueError("max_new_frames_cap and check_every must be >= 1")
         cfg = model.config
@@ -132,7 +132,6 @@ class ContinuousXYDecoder:
         if not 0 <= int(cfg.speech_pad_token) < cfg.speech_vocab_size:
             raise ValueError(f"speech_pad_token = {cfg.speech_pad_token} is not a speech id")
         self.admission = admission
-        from .decode import DecodeStep
         self.model = m = model.eval()
         dev = m.device
         if dev.type != "cuda":
@@ -147,7 +146,7 @@ class ContinuousXYDecoder:
             weight=torch.cat([m.heads[0].weight.detach()[lo0:hi0]] + [h.weight.detach() for h in m.heads[1:]], 0).contiguous(),
             bias=torch.cat([m.heads[0].bias.detach()[lo0:hi0]] + [h.bias.detach() for h in m.heads[1:]], 0).contiguous())
         self.cache = Cache.zeros(cfg, slots, dev, m.dtype)
-        why = DecodeStep.supported(m.model, self.head, self.cache)
+        why = step_class(slots).supported(m.model, self.head, self.cache)
         if why is None and m.dtype != torch.bfloat16:
             why = "the model must be bf16"
         self.tables = [e.weight.detach() for e in m.embs]
@@ -197,7 +196,7 @@ class ContinuousXYDecoder:
         self.st = st
 
         self.sched = SlotScheduler(slots)
-        self.dstep = DecodeStep(m.model, self.head, self.cache)
+        self.dstep = step_for(m.model, self.head, self.cache)
         # capture the step with every slot idle (live = 0): the frame kernels write nothing, and what the warm-up does to the state
         # of idle rows does not matter (admission resets a row before it is used)
         side = torch.cuda.Stream()

@@ -89,6 +89,9 @@ int decode_layer_ptrs();
 size_t decode_workspace_bytes(int, int, int, int, int, int, int, int, int);
 int decode_step_bf16(int, int, int, int, int, int, int, int, int, int, float, float, const void *const *, const void *const *, const void *,
                      const void *, const void *, const void *, const void *, float *, void *, int, hipStream_t);
+size_t decode_wide_workspace_bytes(int, int, int, int, int, int, int, int, int);
+int decode_step_wide_bf16(int, int, int, int, int, int, int, int, int, int, float, float, const void *const *, const void *const *,
+                          const void *, const void *, const void *, const void *, const void *, float *, void *, hipStream_t);
 struct bf16_t;
 template <typename T> int mix_fwd(int, int, int, int, const void *, const void *, const void *, const void *, void *, int, hipStream_t);
 template <typename T> int mix_bwd(int, int, int, int, const void *const *, const void *, const void *, const void *, const void *, void *, float *, int, int, hipStream_t);
@@ -782,6 +785,20 @@ int rwkv7_decode_step_tbl_bf16(const rwkv7_decode_dims *dm, const void *const *l
     return rwkv7::decode_step_bf16(dm->B, dm->D, dm->H, dm->L, dm->F, dm->V, dm->Rw, dm->Ra, dm->Rv, dm->Rg, dm->ln_eps, dm->gn_eps,
                                    layer_tbl, layer_tbl_host, x_in, norm_w, norm_b, head_w, head_b, logits, workspace, persistent,
                                    (hipStream_t)stream);
+}
+size_t rwkv7_decode_wide_workspace_bytes(const rwkv7_decode_dims *dm) {
+    if (!dm || dm->H * RWKV7_HEAD_SIZE != dm->D) return 0;
+    return rwkv7::decode_wide_workspace_bytes(dm->B, dm->D, dm->H, dm->F, dm->V, dm->Rw, dm->Ra, dm->Rv, dm->Rg);
+}
+int rwkv7_decode_step_wide_bf16(const rwkv7_decode_dims *dm, const void *const *layer_tbl, const void *const *layer_tbl_host,
+                                const void *x_in, const void *norm_w, const void *norm_b, const void *head_w, const void *head_b,
+                                float *logits, void *workspace, rwkv7_stream_t stream) {
+    if (!dm || any_null({(const void *)layer_tbl, x_in, norm_w, norm_b, head_w, (const void *)logits, (const void *)workspace}))
+        return RWKV7_EINVAL;
+    if (dm->H * RWKV7_HEAD_SIZE != dm->D) return RWKV7_EHEAD;
+    return rwkv7::decode_step_wide_bf16(dm->B, dm->D, dm->H, dm->L, dm->F, dm->V, dm->Rw, dm->Ra, dm->Rv, dm->Rg, dm->ln_eps, dm->gn_eps,
+                                        layer_tbl, layer_tbl_host, x_in, norm_w, norm_b, head_w, head_b, logits, workspace,
+                                        (hipStream_t)stream);
 }
 int rwkv7_sample_rows_f32(int rows, int nseg, const float *logits, long ld, const int *seg_off, const int *seg_len, const int *allow_lo,
                           const int *allow_hi, const int *suppress, int nsuppress, int max_domain, int do_sample, int top_k, float top_p,

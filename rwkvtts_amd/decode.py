@@ -2,13 +2,15 @@
 rwkv_s2s_single_ffn.py:417-445, HF generate via inference/rwkv7speech_inference.py:99-107).
 
 Two levels:
+  * WideDecodeStep -- the same step for B = 33 .. 128 through rwkv7_decode_step_wide_bf16 (csrc/decode_step_wide.hip): up to four row
+    tiles of 32 through the same chain of launches, every weight streamed once; step_for() picks between the two.
   * DecodeStep -- the whole T = 1 step of the stack (all layers on the in-place recurrent state, final norm, head
     projection) through rwkv7_decode_step_bf16 (csrc/decode_step.hip): 7 grid-wide phases per layer instead of ~18
     module-level launches, either as one launch per phase (default) or as ONE persistent kernel with device-scope barriers
     between the phases (persistent=1; slower on MI355X, the barrier costs 7.4 us against ~1.5 us for a kernel boundary).
   * GraphDecoder -- greedy or sampled (temperature / top-k / top-p, device RNG) loop around it: embedding lookup of the
     previous ids, the step, suppress + argmax/sampling and the bookkeeping are recorded once into a hipGraph on static buffers
-    and replayed per token; the ids never leave the device until the end.  Models the step kernel does not cover (fp32 weights, B > 32, odd low-rank sizes) run the module-by-module
+    and replayed per token; the ids never leave the device until the end.  Models the step kernel does not cover (fp32 weights, B > 128, odd low-rank sizes) run the module-by-module
     step inside the same graph.
 """
 from __future__ import annotations
@@ -37,13 +39,17 @@ class DecodeStep:
     """logits[B,V] (fp32) = step(x_in[B,D] bf16) on the live `cache` of a bf16 RWKV7Model + head; the cache's state tensors
     are updated in place.  Raises ValueError for shapes/dtypes the kernel does not cover (see `supported`)."""
 
+    ENTRY = "rwkv7_decode_step_bf16"
+    WORKSPACE = "rwkv7_decode_workspace_bytes"
+    ROWS = (1, 32)   # the batch sizes the entry covers
+
     def __init__(self, backbone, lm_head, cache: Cache, persistent: int = 0, host_table: bool = True):
         if getattr(cache, "differentiable", False):
             raise ValueError("DecodeStep updates the cache in place and keeps no tape: pass cache.detach() with "
                              "differentiable=False, not a differentiable cache")
         why = self.supported(backbone, lm_head, cache)
         if why:
-            raise ValueError("rwkv7_decode_step_bf16: " + why)
+            raise ValueError(self.ENTRY + ": " + why)
         # host_table = False: rwkv7_decode_step_bf16 (device table only: every phase kernel fetches its pointer row first)
         self.host_table = bool(host_table)
         cfg = backbone.config
@@ -55,10 +61,11 @@ class DecodeStep:
         self.dims = _Dims(self.B, cfg.hidden_size, cfg.num_heads, len(backbone.layers), backbone.layers[0].ffn.key.weight.shape[0],
                           lm_head.weight.shape[0], a0.w_lora.rank, a0.a_lora.rank, backbone.layers[1].attn.v_lora.rank
                           if len(backbone.layers) > 1 else 32, a0.g_lora.rank, cfg.norm_eps, a0.g_norm.eps)
-        lib.rwkv7_decode_workspace_bytes.restype = ctypes.c_size_t
-        nbytes = lib.rwkv7_decode_workspace_bytes(ctypes.byref(self.dims))
+        query = getattr(lib, self.WORKSPACE)
+        query.restype = ctypes.c_size_t
+        nbytes = query(ctypes.byref(self.dims))
         if nbytes == 0:
-            raise ValueError("rwkv7_decode_step_bf16: unsupported shape")
+            raise ValueError(self.ENTRY + ": unsupported shape")
         dev = lm_head.weight.device
         self.workspace = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
         rows = []
@@ -91,15 +98,16 @@ class DecodeStep:
         self.logits = torch.empty(self.B, self.dims.V, dtype=torch.float32, device=dev)
         self.persistent = int(persistent)   # 2 (debug): the barriers of the persistent kernel without the phases
 
-    @staticmethod
-    def supported(backbone, lm_head, cache: Cache) -> Optional[str]:
+    @classmethod
+    def supported(cls, backbone, lm_head, cache: Cache) -> Optional[str]:
         """None if the step kernel covers this model/cache, else the reason."""
         cfg = backbone.config
         if cache is None or len(cache) != len(backbone.layers):
             return "no per-layer cache"
         B = cache[0].att_x_prev.shape[0]
-        if not 1 <= B <= 32:
-            return f"B = {B} (1..32)"
+        lo, hi = cls.ROWS
+        if not lo <= B <= hi:
+            return f"B = {B} ({lo}..{hi})"
         if cfg.hidden_size > 4096 or cfg.hidden_size % 64:
             return "hidden size"
         if not getattr(cfg, "norm_bias", True):
@@ -138,6 +146,60 @@ class DecodeStep:
     def barrier_timed_out(self) -> bool:
         """True if a grid barrier of an earlier step was not met in time (the kernel bails out instead of hanging)."""
         return bool(self.workspace[4:8].view(torch.int32).item())
+
+
+class WideDecodeStep(DecodeStep):
+    """DecodeStep for B = 33 .. 128 sequences through rwkv7_decode_step_wide_bf16 (csrc/decode_step_wide.hip): ceil(B / 32) row tiles
+    of 32 through the same chain of launches, every weight streamed once per step.  Rows 32 g .. 32 g + 31 get bit for bit what a
+    DecodeStep on a cache of those rows gives.  One launch per phase only: `persistent` must be 0."""
+
+    ENTRY = "rwkv7_decode_step_wide_bf16"
+    WORKSPACE = "rwkv7_decode_wide_workspace_bytes"
+    ROWS = (33, 128)
+
+    def __init__(self, backbone, lm_head, cache: Cache, persistent: int = 0, host_table: bool = True):
+        if persistent:
+            raise ValueError(self.ENTRY + ": there is no persistent variant")
+        super().__init__(backbone, lm_head, cache, 0, host_table)
+
+    def __call__(self, x_in: torch.Tensor) -> torch.Tensor:
+        assert x_in.shape == (self.B, self.dims.D) and x_in.dtype == torch.bfloat16 and x_in.is_contiguous()
+        hb = self.head.bias
+        p = ctypes.c_void_p
+        with torch.cuda.device_of(x_in):
+            rc = _lib.lib().rwkv7_decode_step_wide_bf16(
+                ctypes.byref(self.dims), p(self.table.data_ptr()), p(self.table_host.data_ptr() if self.host_table else None),
+                p(x_in.data_ptr()), p(self.norm.weight.data_ptr()), p(self.norm.bias.data_ptr()), p(self.head.weight.data_ptr()),
+                p(hb.data_ptr() if hb is not None else None), p(self.logits.data_ptr()), p(self.workspace.data_ptr()),
+                p(torch.cuda.current_stream(x_in.device).cuda_stream))
+        _lib.check(rc, self.ENTRY)
+        return self.logits
+
+    def barrier_timed_out(self) -> bool:
+        return False   # no grid barriers: one launch per phase
+
+
+MAX_ROWS = 128   # rows of the widest step (four row tiles of 32)
+
+
+def step_class(batch: int):
+    """The step class for a batch size: DecodeStep up to 32 rows, WideDecodeStep above."""
+    return DecodeStep if batch <= 32 else WideDecodeStep
+
+
+def step_for(backbone, lm_head, cache: Cache, **kw):
+    """A DecodeStep on `cache` for B <= 32 and a WideDecodeStep above; ValueError for what neither covers."""
+    if cache is None or len(cache) == 0:
+        raise ValueError("rwkv7_decode_step_bf16: no per-layer cache")
+    return step_class(cache[0].att_x_prev.shape[0])(backbone, lm_head, cache, **kw)
+
+
+def check_slots(slots: int) -> int:
+    """The slot counts a continuous-batching engine accepts: 1 .. 32 (one row tile, any size), or 64, 96, 128 (whole row tiles of the
+    wide step).  Needs no device."""
+    if not (1 <= slots <= 32 or slots in (64, 96, 128)):
+        raise ValueError(f"slots = {slots}: the step kernel takes 1..32 slots, or 64, 96 or 128 (whole row tiles of 32)")
+    return slots
 
 
 class GraphDecoder:
@@ -278,9 +340,9 @@ class GraphDecoder:
         if max_new_tokens <= 1:
             return self
         if self.step_kernel is not False:
-            why = DecodeStep.supported(m.model, m.lm_head, self.cache)
+            why = step_class(B).supported(m.model, m.lm_head, self.cache)
             if why is None:
-                self.step = DecodeStep(m.model, m.lm_head, self.cache)
+                self.step = step_for(m.model, m.lm_head, self.cache)
             elif self.step_kernel:
                 raise ValueError("persistent decode step unavailable: " + why)
         emb_w = m.get_input_embeddings().weight
