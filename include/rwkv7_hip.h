@@ -424,6 +424,21 @@ int rwkv7_add_ln_mix_rows_fwd_bf16(int T, int D, int nmix, const void *x, const 
                                    float eps, const void *mask, const void *params, const int *prev_src, const int *last_dst,
                                    const void *x_prev_rd, void *x_prev, void *x_out, void *out, int nblocks, int run_len,
                                    rwkv7_stream_t stream);
+/*   rwkv7_cache_rows_commit_bf16: copy whole rows of one cache into chosen rows of another, every field of every layer, in one
+ *      launch (csrc/cache_rows.hip).  ContinuousDecoder(admission="overlap") prefills admitted prompts into a small staging cache on a
+ *      side stream and commits the finished rows into the slots' rows with this entry on the decode stream.
+ *        src_tbl / dst_tbl  DEVICE tables of 3 * layers pointers, per layer in the order att_x_prev (bf16 [S,D]), att_kv (fp32
+ *                           [S,H,64,64]), ffn_x_prev (bf16 [S,D]); every field contiguous and 16-byte aligned.  The two caches may
+ *                           have different row counts S.
+ *        src_row / dst_row  DEVICE int32 [n]: entry i copies row src_row[i] of the source to row dst_row[i] of the destination.  An
+ *                           entry with dst_row[i] < 0 (or src_row[i] < 0) is skipped.  Rows not named keep every bit; the copy
+ *                           preserves bits (NaN payloads included).
+ *      The row indices and the tables live on the device and are NOT checked here: the caller guarantees rows inside the caches and
+ *      distinct destination rows among the active entries (the Python wrapper validates on the host before it copies them over).
+ *      n = 0 returns RWKV7_OK without a launch.  RWKV7_EINVAL: NULL table, NULL index array with n > 0, n < 0, layers < 1, n or
+ *      layers > 65535, D or H < 1; RWKV7_ESHAPE: D % 8 != 0 or D > 4096; RWKV7_EHEAD: D != 64 * H.  Nothing is launched then. */
+int rwkv7_cache_rows_commit_bf16(int layers, int n, const void *const *src_tbl, void *const *dst_tbl, const int *src_row,
+                                 const int *dst_row, int D, int H, rwkv7_stream_t stream);
 /*      (The round-3/4 per-chunk gradient kernel, csrc/lab/wkv7_chunk_bwd9.hip, is an A/B twin with its own entry point in the lab build:
  *      include/rwkv7_hip_lab.h.  There are no process-wide switches in this library.) */
 /* ---- head loss: softmax cross-entropy of a chunk of bf16 logits [rows,V], forward and backward in one pass

@@ -9,7 +9,9 @@ every one of up to 128 SLOTS (rows of the step kernel's batch) runs its own requ
   * admission, eagerly between replays on the same stream: pending requests in FIFO order take free slots, their cache rows are
     reset to zero and prefilled as ONE packed row (RWKV7Model(..., cu_seqlens, past_key_values, cache_rows)), the head runs on each
     sequence's last position, and the same per-slot entry (with row_slot) draws the first id; with admission="graph" the prefill
-    is prefill.PackedPrefill instead: graphs captured once per size class, replayed on this cache, no device read-back;
+    is prefill.PackedPrefill instead: graphs captured once per size class, replayed on this cache, no device read-back; with
+    admission="overlap" that prefill runs on a side stream into a staging cache while the step keeps replaying, and the decode stream
+    later copies the staged rows into the slots' rows in one launch (rwkv7_cache_rows_commit_bf16) and draws the first ids;
   * retirement: without EOS the host knows every budget and retires slots on the exact step with no read-back; with EOS it reads
     the live flags and step counters back every `check_every` replays.
 
@@ -108,6 +110,64 @@ class SlotScheduler:
         return not self.pending and not self.busy
 
 
+class OverlapScheduler(SlotScheduler):
+    """SlotScheduler with a two-stage admission for ContinuousDecoder(admission="overlap"): reserve() takes pending requests into the
+    lowest free slots as ONE staged group (their prefill is in flight on a side stream), commit() makes the group busy.  A staged
+    request is neither free nor busy and has no `remaining`: advance() leaves it alone and due() cannot name it.  The scheduler counts
+    the replays since reserve(), so the commit step is a function of host counters only.  admit() and everything else behave as in
+    SlotScheduler."""
+
+    def __init__(self, slots: int):
+        super().__init__(slots)
+        self.staged: List[Tuple[int, Request]] = []   # the group in flight: [(slot, request)]
+        self.since = 0                                # replays since reserve()
+
+    def reserve(self, limit: int) -> List[Tuple[int, Request]]:
+        """Up to `limit` pending requests in FIFO order into the lowest free slots, as the staged group: [(slot, request)]."""
+        if self.staged:
+            raise RuntimeError("a group is already staged: commit() it first")
+        if limit < 1:
+            raise ValueError("limit must be >= 1")
+        while self.pending and self.free and len(self.staged) < limit:
+            self.staged.append((self.free.pop(0), self.pending.popleft()))
+        self.since = 0
+        return list(self.staged)
+
+    def commit(self) -> List[Tuple[int, Request]]:
+        """The staged group becomes busy (each request has drawn its first id): [(slot, request)]."""
+        took, self.staged = self.staged, []
+        for slot, req in took:
+            self.busy[slot] = req
+            self.remaining[slot] = req.max_new_tokens - 1
+        return took
+
+    def advance(self, n: int):
+        super().advance(n)
+        if self.staged:
+            self.since += n
+
+    def replays_until_commit(self, lag: int) -> int:
+        """Replays until the staged group has seen `lag` replays since reserve() (0: it has; 0 too when nothing is staged)."""
+        return max(0, lag - self.since) if self.staged else 0
+
+    def commit_due(self, lag: int) -> bool:
+        """The commit rule: a group is staged, and `lag` replays have been issued since its launch or nothing is busy."""
+        return bool(self.staged) and (self.since >= lag or not self.busy)
+
+    def can_launch(self) -> bool:
+        return not self.staged and bool(self.pending) and bool(self.free)
+
+    def next_replays(self, check_every: int, lag: int, budgets_known: bool = True) -> int:
+        """Replays to issue now: up to check_every, not past the next budget end (budgets_known: the no-EOS case; else not past the
+        longest budget) and not past the staged group's commit."""
+        n = min(check_every, self.replays_until_due() if budgets_known else self.longest())
+        return min(n, self.replays_until_commit(lag)) if self.staged else n
+
+    @property
+    def idle(self) -> bool:
+        return not self.pending and not self.busy and not self.staged
+
+
 class SlotState(ctypes.Structure):
     """rwkv7_slot_state (include/rwkv7_hip.h)."""
     _fields_ = [("step", ctypes.c_void_p), ("limit", ctypes.c_void_p), ("min_until", ctypes.c_void_p), ("seed", ctypes.c_void_p),
@@ -144,14 +204,25 @@ class ContinuousDecoder:
     through prefill.PackedPrefill on the engine's cache: graphs captured once per size class and replayed, the rows reset inside the
     kernels, no device read-back.  In "graph" mode a request's ids do not depend on its slot or on when it is admitted FOR THE SAME PACK
     COMPOSITION (the prompts admitted together, in order): the composition decides the bucket and with it the GEMM shapes, whose
-    library kernels may round differently from bucket to bucket.  prefill_max_seqs / prefill_buckets: PackedPrefill's."""
+    library kernels may round differently from bucket to bucket.  prefill_max_seqs / prefill_buckets: PackedPrefill's.
+
+    admission="overlap": the same PackedPrefill, on a staging cache of prefill_max_seqs rows and on a side stream.  step() reserves
+    the lowest free slots for up to prefill_max_seqs pending requests and starts their prefill; `overlap_replays` replays later (or
+    as soon as nothing is busy) the decode stream waits for it on the device, commits the staged rows into the slots' rows and draws
+    the first ids.  Until then a reserved slot is an idle slot: the step overwrites its rows with stale values and the commit
+    replaces all of them.  Only one group is in flight at a time; every decision reads host counters, never the device, so a
+    submission sequence gives the same schedule on every run.  Every bucket is captured at construction.  Ids equal
+    admission="graph"'s for the same pack composition; admission_log lists per group (replays at launch, replays at commit, [handles])."""
 
     def __init__(self, model, slots: int = 32, max_new_tokens_cap: int = 3000, eos_token_id: Optional[int] = None,
                  pad_token_id: Optional[int] = None, suppress_tokens: Optional[Sequence[int]] = None, check_every: int = 16,
-                 admission: str = "eager", prefill_max_seqs: int = 8, prefill_buckets: Sequence[int] = (256, 512, 1024, 2048, 4096)):
-        if admission not in ("eager", "graph"):
-            raise ValueError(f"admission = {admission!r}: 'eager' or 'graph'")
-        self.admission = admission
+                 admission: str = "eager", prefill_max_seqs: int = 8, prefill_buckets: Sequence[int] = (256, 512, 1024, 2048, 4096),
+                 overlap_replays: int = 8):
+        if admission not in ("eager", "graph", "overlap"):
+            raise ValueError(f"admission = {admission!r}: 'eager', 'graph' or 'overlap'")
+        if overlap_replays < 0:
+            raise ValueError("overlap_replays must be >= 0")
+        self.admission, self.overlap_replays = admission, int(overlap_replays)
         check_slots(slots)   # 1..32, or 64 / 96 / 128: ValueError before anything touches the device
         if max_new_tokens_cap < 1 or check_every < 1:
             raise ValueError("max_new_tokens_cap and check_every must be >= 1")
@@ -211,7 +282,7 @@ class ContinuousDecoder:
         st.eos = -1 if self.eos is None else self.eos
         self.st = st
 
-        self.sched = SlotScheduler(slots)
+        self.sched = OverlapScheduler(slots) if admission == "overlap" else SlotScheduler(slots)
         self.dstep = step_for(m.model, m.lm_head, self.cache)
         # capture the step.  Every slot is idle (live = 0): the draw writes nothing, and the warm-up's change to the state of idle
         # rows does not matter (admission resets a row before it is used)
@@ -228,6 +299,9 @@ class ContinuousDecoder:
         if admission == "graph":
             from .prefill import PackedPrefill
             self.prefill = PackedPrefill(m.model, self.cache, max_seqs=prefill_max_seqs, buckets=prefill_buckets)
+        self.admission_log: List[Tuple[int, int, List[int]]] = []   # overlap: (replays at launch, replays at commit, [handles]) per group
+        if admission == "overlap":
+            self._init_overlap(int(prefill_max_seqs), prefill_buckets)
 
     def _step(self):
         sample_slots(self.dstep(self.x), self.st, None, self.allow_lo, self.allow_hi, self.suppress, self.max_domain)
@@ -259,6 +333,8 @@ class ContinuousDecoder:
     @torch.no_grad()
     def step(self) -> List[Tuple[int, torch.Tensor]]:
         """Admit what fits, run up to check_every replays, retire what finished: [(handle, ids)] of the requests that finished."""
+        if self.admission == "overlap":
+            return self._step_overlap()
         done = []
         if self.eos is None:
             done += self._retire(self.sched.due(), None)
@@ -332,6 +408,107 @@ class ContinuousDecoder:
         logits = self.model.lm_head(h_last).float()
         row_slot = torch.tensor(slots, dtype=torch.int32).pin_memory().to(self.device, non_blocking=True)
         self._admit_draw(took, logits, row_slot.long(), row_slot)
+
+    # ---- admission="overlap" -------------------------------------------------------------------------------------------------
+    def _init_overlap(self, max_seqs, buckets):
+        """Everything overlapped work touches is allocated HERE, once: the staging cache and its PackedPrefill with every bucket
+        captured (no capture may happen while the other stream has work in flight), the staged logits, the row indices, the two
+        pointer tables, the pinned index blocks, the side stream and the events."""
+        from .prefill import PackedPrefill, cache_field_table
+        m, dev = self.model, self.device
+        P = self.stage_rows = max_seqs
+        self.stage_cache = Cache.zeros(m.config, P, dev, m.dtype)
+        self.prefill = PackedPrefill(m.model, self.stage_cache, max_seqs=max_seqs, buckets=buckets).warm()
+        self.logits_stage = torch.zeros(P, self.V, dtype=torch.float32, device=dev)
+        self._src_row = torch.arange(P, dtype=torch.int32, device=dev)        # stage row of entry i: always i
+        self._dst_row = torch.full((P,), -1, dtype=torch.int32, device=dev)   # its slot; -1 past the group
+        self._rows64 = torch.zeros(P, dtype=torch.int64, device=dev)
+        self._src_tbl, self._dst_tbl = cache_field_table(self.stage_cache), cache_field_table(self.cache)
+        # the slots of a group cross in one of two pinned blocks, alternately; a block is rewritten only after the copy that read it
+        self._pin = [torch.full((P,), -1, dtype=torch.int32).pin_memory() for _ in range(2)]
+        self._pin_ev = [torch.cuda.Event(), torch.cuda.Event()]
+        self._pin_used = [False, False]
+        self._ready = torch.cuda.Event()
+        self._side = torch.cuda.Stream(device=dev)
+        self._launched_at = 0
+        self._groups = 0
+        torch.cuda.current_stream(dev).synchronize()   # the tables and the warm-up are complete before any side-stream work
+
+    def _step_overlap(self) -> List[Tuple[int, torch.Tensor]]:
+        """step() with the prefill of the next group on the side stream.  Every decision reads host counters only (never whether the
+        prefill has finished), so a submission sequence gives the same schedule on every run."""
+        s, lag, done = self.sched, self.overlap_replays, []
+        if self.eos is None:
+            done += self._retire(s.due(), None)
+        if s.commit_due(lag):
+            self._commit()
+        if s.can_launch():
+            self._launch()
+            if s.commit_due(lag):
+                self._commit()
+        if self.eos is None:
+            done += self._retire(s.due(), None)   # max_new_tokens = 1: finished with its first id
+        if not s.busy:
+            return done
+        n = s.next_replays(self.check_every, lag, self.eos is None)
+        for _ in range(n):
+            self.graph.replay()
+        self.replays += n
+        s.advance(n)
+        if self.eos is None:
+            done += self._retire(s.due(), None)
+        else:
+            both = torch.stack([self.live.to(torch.int64), self.step_t]).cpu()   # one small read-back
+            done += self._retire([b for b in sorted(s.busy) if not both[0, b]], both[1])
+        if self.dstep.barrier_timed_out():
+            raise _lib.Rwkv7HipError("rwkv7_decode_step_bf16: a grid barrier timed out; the generated ids are invalid")
+        return done
+
+    def _launch(self):
+        """Reserve a group (host) and start its prefill (device)."""
+        took = self.sched.reserve(self.stage_rows)
+        self._launched_at = self.replays
+        self._launch_device(took)
+
+    def _commit(self):
+        """The staged group becomes busy (host) and its rows and first ids reach the slots (device)."""
+        took = self.sched.commit()
+        self._commit_device(took)
+        self.admission_log.append((self._launched_at, self.replays, [r.handle for _, r in took]))
+
+    def _launch_device(self, took):
+        """The group's prefill into stage rows 0 .. n - 1 on the side stream.  The side stream first waits for the decode stream: for
+        the prompts' embeddings, and for the previous commit's read of the stage rows and of logits_stage."""
+        main, side = torch.cuda.current_stream(self.device), self._side
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            for _, r in took:
+                r.embeds.record_stream(side)
+            h_last = self.prefill.run([r.embeds for _, r in took], list(range(len(took))), fresh=True)
+            self.logits_stage[:len(took)].copy_(self.model.lm_head(h_last).float())
+            self._ready.record(side)
+
+    def _commit_device(self, took):
+        """On the decode stream: wait (on the device, the host never blocks on it) for the staged prefill, copy the stage rows into the
+        slots' rows in one launch, then the parameter block, step = 0, live = 1 and the first draw, as the other admission modes do."""
+        from .prefill import cache_rows_commit, check_commit_rows
+        n, k = len(took), self._groups % 2
+        main = torch.cuda.current_stream(self.device)
+        _, slots = check_commit_rows(range(n), [sl for sl, _ in took], self.stage_rows, self.slots)
+        if self._pin_used[k]:
+            self._pin_ev[k].synchronize()   # the copy that read this block two groups ago (long complete)
+        self._pin[k].fill_(-1)
+        self._pin[k][:n] = torch.tensor(slots, dtype=torch.int32)
+        self._dst_row.copy_(self._pin[k], non_blocking=True)
+        self._pin_ev[k].record(main)
+        self._pin_used[k] = True
+        self._groups += 1
+        main.wait_event(self._ready)
+        cfg = self.model.config
+        cache_rows_commit(self._src_tbl, self._dst_tbl, self._src_row, self._dst_row, n, len(self.cache), cfg.hidden_size, cfg.num_heads)
+        row_slot = self._dst_row[:n]
+        self._rows64[:n].copy_(row_slot)
+        self._admit_draw(took, self.logits_stage[:n], self._rows64[:n], row_slot)
 
     def _admit_draw(self, took, logits, rows64, row_slot):
         # the slots' parameters: host mirror -> one copy per field; step = 0 and live = 1 for the admitted slots only (the device

@@ -1,0 +1,66 @@
+// rwkvtts_amd/csrc/cache_rows.hip -- commit staged cache rows (rwkvtts_amd/continuous.py, admission="overlap"): for every entry i
+// with dst_row[i] >= 0, row src_row[i] of a source cache is copied to row dst_row[i] of a destination cache, all three fields
+// (att_x_prev bf16 [S,D], att_kv fp32 [S,H,64,64], ffn_x_prev bf16 [S,D]) of all layers, in ONE launch: what 3 L index_copy_ calls do.
+//
+// A row of the three fields of one layer is one virtual array of 16-byte vectors: D/8 | 1024 H | D/8 (D = 64 H, so 1040 H in all).
+// Grid (piece of that array, entry, layer); a thread moves kCommitVecs vectors, all loads issued before the first store.  The field
+// pointers come from two device tables, the rows from two device index arrays, so nothing about a particular admission reaches the
+// launch.  Pure copy: plain 16-byte vector loads and stores, no LDS, no atomics, bits preserved whatever they encode.
+//
+// Neither row index is range-checked against the caches' row counts (device data; the caller's guarantee, include/rwkv7_hip.h); a
+// negative index of either kind skips the entry.  Destination rows must be distinct among the active entries.
+#include <hip/hip_runtime.h>
+
+namespace rwkv7 {
+
+constexpr int kCommitThreads = 256, kCommitVecs = 4;
+
+__global__ __launch_bounds__(kCommitThreads) void cache_rows_commit_kernel(const uint4 *const *__restrict__ src_tbl,
+                                                                           uint4 *const *__restrict__ dst_tbl,
+                                                                           const int *__restrict__ src_row,
+                                                                           const int *__restrict__ dst_row, int xv, int kvv) {
+    const int e = blockIdx.y, l = blockIdx.z;
+    const long sr = src_row[e], dr = dst_row[e];
+    if (sr < 0 || dr < 0) return;   // uniform over the workgroup
+    const uint4 *const s0 = src_tbl[3 * l], *const s1 = src_tbl[3 * l + 1], *const s2 = src_tbl[3 * l + 2];
+    uint4 *const d0 = dst_tbl[3 * l], *const d1 = dst_tbl[3 * l + 1], *const d2 = dst_tbl[3 * l + 2];
+    const int nv = 2 * xv + kvv;
+    const int base = blockIdx.x * (kCommitThreads * kCommitVecs) + threadIdx.x;
+    uint4 v[kCommitVecs];
+    uint4 *to[kCommitVecs];
+#pragma unroll
+    for (int j = 0; j < kCommitVecs; j++) {
+        const int i = base + j * kCommitThreads;
+        to[j] = nullptr;
+        if (i < nv) {
+            const uint4 *from;
+            if (i < xv) {
+                from = s0 + sr * xv + i;
+                to[j] = d0 + dr * xv + i;
+            } else if (i < xv + kvv) {
+                from = s1 + sr * kvv + (i - xv);
+                to[j] = d1 + dr * kvv + (i - xv);
+            } else {
+                from = s2 + sr * xv + (i - xv - kvv);
+                to[j] = d2 + dr * xv + (i - xv - kvv);
+            }
+            v[j] = *from;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < kCommitVecs; j++)
+        if (to[j]) *to[j] = v[j];
+}
+
+int cache_rows_commit_bf16(int layers, int n, const void *const *src_tbl, void *const *dst_tbl, const int *src_row, const int *dst_row,
+                           int D, int H, hipStream_t st) {
+    (void)hipGetLastError();
+    const int xv = D / 8, kvv = H * 1024, nv = 2 * xv + kvv;
+    const int per = kCommitThreads * kCommitVecs;
+    const dim3 grid((nv + per - 1) / per, n, layers), block(kCommitThreads);
+    hipLaunchKernelGGL(cache_rows_commit_kernel, grid, block, 0, st, (const uint4 *const *)src_tbl, (uint4 *const *)dst_tbl, src_row,
+                       dst_row, xv, kvv);
+    return (int)hipGetLastError();
+}
+
+}  // namespace rwkv7

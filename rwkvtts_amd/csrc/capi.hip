@@ -106,6 +106,7 @@ template <typename T> int add_ln_mix_fwd(int, int, int, int, void *, const void 
 template <typename T> int mix_add_ln_bwd(int, int, int, int, const void *const *, const void *, const void *, const float *, const float *, const void *, const void *, const void *, const void *, void *, float *, int, int, hipStream_t);
 int add_ln_mix_rows_fwd_bf16(int, int, int, const void *, const void *, const void *, const void *, float, const void *, const void *, const int *, const int *, const void *, void *, void *, void *, int, int, hipStream_t);
 int chunk_fwd9_state_rows_bf16(int, int, const void *, const void *, const void *, const void *, const void *, const void *, const float *, void *, const int *, int, float *, const int *, hipStream_t);
+int cache_rows_commit_bf16(int, int, const void *const *, void *const *, const int *, const int *, int, int, hipStream_t);
 template <typename T> int relusq_fwd(long, const void *, void *, hipStream_t);
 template <typename T> int relusq_bwd(long, const void *, const void *, void *, hipStream_t);
 template <typename T> int relusq_bwd_s(long, const void *, const void *, void *, hipStream_t);
@@ -516,6 +517,16 @@ int rwkv7_add_ln_mix_rows_fwd_bf16(int T, int D, int nmix, const void *x, const 
     if (!SHAPE_OK(D) || (nmix != 1 && nmix != 6) || T % 32 != 0) return RWKV7_ESHAPE;
     return rwkv7::add_ln_mix_rows_fwd_bf16(T, D, nmix, x, branch, gamma, beta, eps, mask, params, prev_src, last_dst,
                                            x_prev_rd ? x_prev_rd : x_prev, x_prev, x_out, out, nblocks, run_len, (hipStream_t)stream);
+}
+// staged cache rows -> slot rows in one launch (rwkvtts_amd/continuous.py, admission="overlap"): tables and row indices are device data
+int rwkv7_cache_rows_commit_bf16(int layers, int n, const void *const *src_tbl, void *const *dst_tbl, const int *src_row,
+                                 const int *dst_row, int D, int H, rwkv7_stream_t stream) {
+    if (layers < 1 || layers > 65535 || n < 0 || n > 65535 || D <= 0 || H <= 0 || !src_tbl || !dst_tbl) return RWKV7_EINVAL;
+    if (D % 8 != 0 || D > 4096) return RWKV7_ESHAPE;
+    if (D != 64 * H) return RWKV7_EHEAD;
+    if (n == 0) return RWKV7_OK;   // nothing to commit: no launch
+    if (!src_row || !dst_row) return RWKV7_EINVAL;
+    return rwkv7::cache_rows_commit_bf16(layers, n, src_tbl, dst_tbl, src_row, dst_row, D, H, (hipStream_t)stream);
 }
 // plain rows (one state per row, [B,H,64,64]): the packed entries with seq_chunk_off = NULL, nseq = 0
 int rwkv7_wkv_chunk_fwd_state_bf16(int B, int T, int H, const void *w, const void *q, const void *k, const void *v,

@@ -166,6 +166,47 @@ def wkv_state_rows(state, r, w, k, v, a, b, seq_off, state_row):
     return y
 
 
+def cache_field_table(cache: Cache) -> torch.Tensor:
+    """The device table rwkv7_cache_rows_commit_bf16 takes for `cache`: int64 [3 L], per layer the addresses of att_x_prev, att_kv,
+    ffn_x_prev.  The cache's tensors must outlive the table; ValueError for fields the entry does not cover."""
+    if cache is None or len(cache) == 0:
+        raise ValueError("rwkv7_cache_rows_commit_bf16: no per-layer cache")
+    S, D = cache[0].att_x_prev.shape
+    H = cache[0].att_kv.shape[1]
+    ptrs = []
+    for st in cache.states:
+        for t, dt, shape in ((st.att_x_prev, torch.bfloat16, (S, D)), (st.att_kv, torch.float32, (S, H, 64, 64)), (st.ffn_x_prev, torch.bfloat16, (S, D))):
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda or t.data_ptr() % 16:
+                raise ValueError(f"rwkv7_cache_rows_commit_bf16: cache field {tuple(t.shape)} / {t.dtype}: expected a contiguous, 16-byte "
+                                 f"aligned {dt} {shape} on the HIP device")
+            ptrs.append(t.data_ptr())
+    return torch.tensor(ptrs, dtype=torch.int64).to(cache[0].att_kv.device)
+
+
+def check_commit_rows(src_row: Sequence[int], dst_row: Sequence[int], src_rows: int, dst_rows: int):
+    """Host check of the row lists before they go to the device (the kernel does not check them): as many sources as destinations,
+    active sources in [0, src_rows), active destinations distinct and in [0, dst_rows); a negative destination marks a skipped entry."""
+    src_row, dst_row = [int(r) for r in src_row], [int(r) for r in dst_row]
+    if len(src_row) != len(dst_row):
+        raise ValueError(f"{len(src_row)} source rows for {len(dst_row)} destination rows")
+    act = [(s, d) for s, d in zip(src_row, dst_row) if d >= 0]
+    if any(not 0 <= s < src_rows for s, _ in act) or any(d >= dst_rows for _, d in act) or len({d for _, d in act}) != len(act):
+        raise ValueError(f"rows {src_row} -> {dst_row}: sources must lie in [0, {src_rows}), destinations distinct in [0, {dst_rows})")
+    return src_row, dst_row
+
+
+def cache_rows_commit(src_tbl, dst_tbl, src_row, dst_row, n: int, layers: int, D: int, H: int):
+    """rwkv7_cache_rows_commit_bf16 on the current stream: src_tbl / dst_tbl from cache_field_table, src_row / dst_row int32 device
+    tensors of at least n entries whose values the caller has checked (check_commit_rows)."""
+    for t in (src_row, dst_row):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.is_cuda and t.numel() >= n
+    assert src_tbl.dtype == torch.int64 and dst_tbl.dtype == torch.int64 and src_tbl.numel() == dst_tbl.numel() == 3 * layers
+    with torch.cuda.device_of(dst_tbl):
+        rc = _lib.lib().rwkv7_cache_rows_commit_bf16(int(layers), int(n), _p(src_tbl), _p(dst_tbl), _p(src_row), _p(dst_row), int(D), int(H),
+                                                     ctypes.c_void_p(torch.cuda.current_stream(dst_tbl.device).cuda_stream))
+    _lib.check(rc, "rwkv7_cache_rows_commit_bf16")
+
+
 class _Bucket:
     def __init__(self, t_al, max_seqs, D, dev):
         self.t_al = t_al
