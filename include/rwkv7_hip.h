@@ -470,6 +470,30 @@ int rwkv7_adamw_bf16(long n, float *p32, const void *g16, float *m, float *v, vo
 int rwkv7_adamw_groups_bf16(long n, float *p32, const void *g16, float *m, float *v, void *p16, const unsigned char *slab_group,
                             const float *group_tab, int ngroups, const float *skip_flag, float lr, float beta1, float beta2,
                             float eps, int step, rwkv7_stream_t stream);
+/*      The same step with gradient clipping by global norm (the reference hands `gradient_clipping` to DeepSpeed,
+ *      train_scripts/train_rwkv_tts.py:133,405; third_party/cosyvoice/utils/train_utils.py:283-291 calls clip_grad_norm_):
+ *      coef = min(1, max_norm / (sqrt(*sumsq) + 1e-6)), computed per launch from the DEVICE scalar sumsq (the sum of squares of
+ *      the whole gradient, rwkv7_grad_sumsq_bf16 -- not only of the n elements of this call); the gradient is multiplied by coef
+ *      in fp32 right after the bf16 load, and only when coef < 1: with coef == 1 the arithmetic is that of
+ *      rwkv7_adamw_groups_bf16.  A non-finite *sumsq acts like skip_flag != 0 (zero-gradient step, nothing becomes NaN).
+ *      max_norm >= 0; +inf = measure only.  The host reads neither sumsq nor skip_flag. */
+int rwkv7_adamw_groups_clip_bf16(long n, float *p32, const void *g16, float *m, float *v, void *p16, const unsigned char *slab_group,
+                                 const float *group_tab, int ngroups, const float *skip_flag, const float *sumsq, float max_norm,
+                                 float lr, float beta1, float beta2, float eps, int step, rwkv7_stream_t stream);
+
+/* ---- passes over a flat bf16 gradient buffer (n % 128 == 0, pointers 16-byte aligned; the trainer's slices are 256-byte
+ *      aligned).  No atomics anywhere: two calls on the same data give the same bits.
+ *      rwkv7_grad_sumsq_bf16: out[0] = (accumulate ? out[0] : 0) + sum g16[i]^2.  Two launches: one workgroup per FIXED tile of
+ *      8192 elements (fp32, one partial per tile into `partials`, rwkv7_grad_sumsq_workspace_bytes(n) bytes), then one
+ *      workgroup that adds the partials in double in a fixed order.  A NaN or Inf in g16 gives a non-finite out[0]. */
+long rwkv7_grad_sumsq_workspace_bytes(long n);
+int rwkv7_grad_sumsq_bf16(long n, const void *g16, float *partials, float *out, int accumulate, rwkv7_stream_t stream);
+/*      Micro-batch accumulation in fp32 (`accum_grad`, train_utils.py:87-89; DeepSpeed's bf16 engine accumulates in fp32):
+ *      rwkv7_grad_accum_bf16: acc32 = (first ? 0 : acc32) + float(g16)   (first: acc32 is not read, float(g16) is stored as it is);
+ *      rwkv7_grad_fold_bf16:  g16 = bf16_rne((acc32 + float(g16)) * inv_count) in place -- the last micro-batch's gradient joins
+ *      the sum here, and the only rounding to bf16 is this one. */
+int rwkv7_grad_accum_bf16(long n, float *acc32, const void *g16, int first, rwkv7_stream_t stream);
+int rwkv7_grad_fold_bf16(long n, const float *acc32, void *g16, float inv_count, rwkv7_stream_t stream);
 
 /* ---- last step of a split weight gradient (the dW of nn.Linear under autograd, e.g. rwkv_s2s_single_ffn.py:171-174,195,
  *      228-229, reduced over B*T in S row slabs with fp32 partials): out[n] (bf16) = (accumulate ? out[n] : 0) +

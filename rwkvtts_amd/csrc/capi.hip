@@ -36,6 +36,11 @@ int gemv32_bf16(int, int, int, const void *, const void *, const void *, void *,
 int ce_fwd_bwd(long, int, long, void *, const long *, long, float, float *, float, hipStream_t);
 int adamw_step(long, float *, const void *, float *, float *, void *, const uint8_t *, const float *, const float *, float, float, float, float,
                float, float, float, hipStream_t);
+int adamw_clip_step(long, float *, const void *, float *, float *, void *, const uint8_t *, const float *, const float *, const float *,
+                    float, float, float, float, float, float, float, float, hipStream_t);
+int grad_sumsq_bf16(long, const void *, float *, float *, int, hipStream_t);
+int grad_accum_bf16(long, float *, const void *, int, hipStream_t);
+int grad_fold_bf16(long, const float *, void *, float, hipStream_t);
 int lora32_bf16(int, int, int, int, int, const void *, const void *, const void *, const void *, void *, hipStream_t);
 int chunk_bseq_bf16(int, int, int, const void *, const void *, const void *, const void *, const void *, const float *, void *,
                     float *, const int *, int, hipStream_t);
@@ -717,6 +722,34 @@ int rwkv7_adamw_groups_bf16(long n, float *p32, const void *g16, float *m, float
     const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
     return rwkv7::adamw_step(n, p32, g16, m, v, p16, slab_group, group_tab, skip_flag, lr, beta1, beta2, eps, 0.f, (float)(1.0 / bc1),
                              (float)(1.0 / sqrt(bc2)), (hipStream_t)stream);
+}
+int rwkv7_adamw_groups_clip_bf16(long n, float *p32, const void *g16, float *m, float *v, void *p16, const unsigned char *slab_group,
+                                 const float *group_tab, int ngroups, const float *skip_flag, const float *sumsq, float max_norm,
+                                 float lr, float beta1, float beta2, float eps, int step, rwkv7_stream_t stream) {
+    if (n <= 0 || step <= 0 || any_null({(const void *)p32, g16, (const void *)m, (const void *)v, p16, (const void *)sumsq}))
+        return RWKV7_EINVAL;
+    if ((slab_group == nullptr) != (group_tab == nullptr) || (slab_group && (ngroups <= 0 || ngroups > 256))) return RWKV7_EINVAL;
+    if (!(max_norm >= 0.f)) return RWKV7_EINVAL;   // NaN or negative; +inf = measure only
+    if (n % 4 != 0 || (slab_group && n % 128 != 0)) return RWKV7_ESHAPE;
+    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+    return rwkv7::adamw_clip_step(n, p32, g16, m, v, p16, slab_group, group_tab, skip_flag, sumsq, max_norm, lr, beta1, beta2, eps, 0.f,
+                                  (float)(1.0 / bc1), (float)(1.0 / sqrt(bc2)), (hipStream_t)stream);
+}
+long rwkv7_grad_sumsq_workspace_bytes(long n) { return n <= 0 ? 0 : (n + 8191) / 8192 * (long)sizeof(float); }
+int rwkv7_grad_sumsq_bf16(long n, const void *g16, float *partials, float *out, int accumulate, rwkv7_stream_t stream) {
+    if (n <= 0 || any_null({g16, (const void *)partials, (const void *)out})) return RWKV7_EINVAL;
+    if (n % 128 != 0 || ((uintptr_t)g16 & 15) != 0) return RWKV7_ESHAPE;
+    return rwkv7::grad_sumsq_bf16(n, g16, partials, out, accumulate != 0, (hipStream_t)stream);
+}
+int rwkv7_grad_accum_bf16(long n, float *acc32, const void *g16, int first, rwkv7_stream_t stream) {
+    if (n <= 0 || any_null({(const void *)acc32, g16})) return RWKV7_EINVAL;
+    if (n % 128 != 0 || (((uintptr_t)g16 | (uintptr_t)acc32) & 15) != 0) return RWKV7_ESHAPE;
+    return rwkv7::grad_accum_bf16(n, acc32, g16, first != 0, (hipStream_t)stream);
+}
+int rwkv7_grad_fold_bf16(long n, const float *acc32, void *g16, float inv_count, rwkv7_stream_t stream) {
+    if (n <= 0 || any_null({(const void *)acc32, (const void *)g16})) return RWKV7_EINVAL;
+    if (n % 128 != 0 || (((uintptr_t)g16 | (uintptr_t)acc32) & 15) != 0) return RWKV7_ESHAPE;
+    return rwkv7::grad_fold_bf16(n, acc32, g16, inv_count, (hipStream_t)stream);
 }
 int rwkv7_adamw_bf16(long n, float *p32, const void *g16, float *m, float *v, void *p16, float lr, float beta1, float beta2,
                      float eps, float weight_decay, int step, rwkv7_stream_t stream) {

@@ -12,6 +12,7 @@
 // per-head reductions (l2 norm, GroupNorm moments, bonus dot product) are 8-lane DPP sums, no LDS.
 // Parameter gradients are accumulated per thread over the rows a workgroup walks and written as per-workgroup
 // partials [nblocks, P, D] (fp32); the host sums the partials (deterministic, no atomics).
+#include "adamw_body.h"
 #include "ln_row.h"
 
 namespace rwkv7 {
@@ -1089,6 +1090,7 @@ __global__ __launch_bounds__(kEwMaxThreads) void mix_add_ln_bwd_kernel(int B, in
 // optimizer keeps fp32 masters the same way).  Update rule = torch.optim.AdamW (decoupled weight decay):
 //   p *= 1 - lr wd ;  m = b1 m + (1-b1) g ;  v = b2 v + (1-b2) g^2 ;  p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
 // 4 floats per thread and iteration: 2 + 3*4 bytes read, 3*4 + 2 written per parameter (28 B) -- nothing else touches HBM.
+// The loop is adamw_body (adamw_body.h), shared with the clipping kernel of grad_ops.hip.
 // ------------------------------------------------------------------------------------------------------
 // GROUPS: per-slab parameter groups (train_cosy_rwkv7speech_multiple_dataset.py:162-202): slab_group[e / 128] indexes
 // group_tab[g] = {lr scale, weight decay}; the trainer's flat buffer aligns every parameter to 128 elements, so a float4 never
@@ -1101,29 +1103,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(long n4, float *__restrict__
                                                     const float *__restrict__ skip_flag, float lr, float beta1, float beta2,
                                                     float eps, float wd, float inv_bc1, float inv_sqrt_bc2) {
     const bool skip = skip_flag != nullptr && *skip_flag != 0.f;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-        float lr_i = lr, wd_i = wd;
-        if (GROUPS) {
-            const float2 g = group_tab[slab_group[i >> 5]];
-            lr_i = lr * g.x;
-            wd_i = g.y;
-        }
-        const float decay = 1.f - lr_i * wd_i, step = lr_i * inv_bc1;
-        float4 p = reinterpret_cast<float4 *>(p32)[i], mm = reinterpret_cast<float4 *>(m)[i], vv = reinterpret_cast<float4 *>(v)[i];
-        float4 g = cvt4(ld4<bf16_t>(g16 + 4 * i, true));
-        if (skip) g = make_float4(0.f, 0.f, 0.f, 0.f);
-        auto upd = [&](float &pp, float &m1, float &v1, float gg) {
-            pp *= decay;
-            m1 = fmaf(beta1, m1, (1.f - beta1) * gg);
-            v1 = fmaf(beta2, v1, (1.f - beta2) * gg * gg);
-            pp -= step * m1 / (sqrtf(v1) * inv_sqrt_bc2 + eps);
-        };
-        upd(p.x, mm.x, vv.x, g.x); upd(p.y, mm.y, vv.y, g.y); upd(p.z, mm.z, vv.z, g.z); upd(p.w, mm.w, vv.w, g.w);
-        reinterpret_cast<float4 *>(p32)[i] = p;
-        reinterpret_cast<float4 *>(m)[i] = mm;
-        reinterpret_cast<float4 *>(v)[i] = vv;
-        st4(p16 + 4 * i, p);
-    }
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x)
+        adamw_body<GROUPS, false>(i, p32, g16, m, v, p16, slab_group, group_tab, skip, 1.f, lr, beta1, beta2, eps, wd, inv_bc1, inv_sqrt_bc2);
 }
 
 int adamw_step(long n, float *p32, const void *g16, float *m, float *v, void *p16, const uint8_t *slab_group, const float *group_tab,

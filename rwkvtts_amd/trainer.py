@@ -16,6 +16,7 @@ MI355X-first choices:
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import os
 from typing import List, Optional
@@ -181,6 +182,8 @@ class BucketedAllReduce:
         self.use_avg, self.summed = True, []
         self.measure, self.wait_events = False, []
         self.defer_reattach = False   # DataParallelTrainer sets it: it calls flat.reattach() itself, behind the optimizer launch
+        self.pre_exchange = None      # callable(s, e): runs on [s, e) of the flat gradient right before that run goes on the wire
+        #                               (DataParallelTrainer: the fold of the accumulated micro-batch gradients, bucket by bucket)
         self.enabled = self.world > 1 or (force and dist.is_initialized())
         if self.enabled:
             flat.on_ready = self._ready
@@ -265,6 +268,8 @@ class BucketedAllReduce:
         self.flat.flush()   # the bucket's slices must hold the final gradients
         self.launched.append(b)
         for s, e in self.runs[b]:
+            if self.pre_exchange is not None:
+                self.pre_exchange(s, e)
             self._exchange(s, e, b)
 
     def _exchange(self, s, e, b=-1):
@@ -409,7 +414,7 @@ class DataParallelTrainer:
     def __init__(self, model: torch.nn.Module, lr=1e-4, lr_final=1e-5, warmup_steps=100, total_steps=100000,
                  weight_decay=0.0, betas=(0.9, 0.95), eps=1e-18, bucket_bytes=32 << 20, nan_guard=True,
                  master_fp32=True, param_groups=None, schedule="linear", force_allreduce=False, shard_optimizer=False,
-                 bucket_optimizer=True):
+                 bucket_optimizer=True, max_grad_norm=None):
         """shard_optimizer: every rank reduces the gradient pieces of ITS 1/N slab only, steps AdamW on that slab and broadcasts
         the slab's new bf16 parameters (reduce-scatter + sharded optimizer + all-gather, ZeRO-1 style: the reference's DeepSpeed
         ZeRO-2 engine does the same exchange, train_spark_rwkv7speech.py:483-516).  Same parameters after every step as the
@@ -420,7 +425,17 @@ class DataParallelTrainer:
         clipping must all-reduce its own partial over the own slab, `reducer.slab(rank)`).
         bucket_optimizer (default, all-reduce mode with > 1 rank): AdamW runs bucket by bucket, each as soon as its own
         all-reduce has completed, so the optimizer pass (2.1-2.4 ms for the 0.4B model) overlaps the buckets still on the wire
-        instead of sitting behind the last one.  Element-wise the same update: identical parameters to the one-pass mode."""
+        instead of sitting behind the last one.  Element-wise the same update: identical parameters to the one-pass mode.
+        max_grad_norm: clip the (reduced) gradient by its global L2 norm, torch.nn.utils.clip_grad_norm_'s rule (the reference
+        hands `gradient_clipping` to DeepSpeed, train_scripts/train_rwkv_tts.py:133,405): coef = min(1, max_grad_norm / (norm +
+        1e-6)).  One sum-of-squares pass over the reduced gradient (rwkv7_grad_sumsq_bf16: the whole buffer, or the own slab plus a
+        one-element all_reduce(SUM) in shard mode), then ONE AdamW pass that reads the sum from device memory and scales the
+        gradient as it loads it (rwkv7_adamw_groups_clip_bf16); the gradient buffer itself is left unscaled.  The norm is not known
+        before the last bucket has landed, so clipping GIVES UP the per-bucket optimizer overlap of `bucket_optimizer`: the optimizer
+        pass sits behind the last all-reduce.  Every rank computes the factor from identical data: replicas stay bit-identical.
+        A non-finite norm makes the step a zero-gradient step, like a NaN loss.  float('inf') = measure only.
+        `last_grad_norm` (None without max_grad_norm): device fp32 scalar, the pre-clip norm of the last step; step() never
+        reads it on the host."""
         self.model = model
         self.bucket_optimizer = bool(bucket_optimizer)
         self.flat = FlatBuffers(model)
@@ -480,6 +495,23 @@ class DataParallelTrainer:
         self.lr, self.lr_final, self.warmup_steps, self.total_steps = lr, lr_final, warmup_steps, total_steps
         self.nan_guard = nan_guard
         self.nan_flag = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.last_grad_norm = None
+        if self.max_grad_norm is not None:
+            assert self.max_grad_norm >= 0.0, "max_grad_norm must be >= 0 (float('inf'): measure only)"
+            self.last_grad_norm = torch.zeros((), dtype=torch.float32, device=dev)
+            # the sum of squares stays on the device: fp32 + per-tile partials for the HIP pass, float64 in the torch fallback
+            self._sumsq = torch.zeros(1, dtype=torch.float32 if self.hip_adamw else torch.float64, device=dev)
+            if self.hip_adamw:
+                from . import _lib
+                nbytes = _lib.lib().rwkv7_grad_sumsq_workspace_bytes
+                nbytes.restype, nbytes.argtypes = ctypes.c_long, [ctypes.c_long]
+                self._sumsq_partials = torch.empty(nbytes(self.flat.numel) // 4, dtype=torch.float32, device=dev)
+        # micro-batch accumulation (accumulate()): fp32 sum of the gradients of the micro-batches before the one step() runs,
+        # allocated on first use; their count; the running max of their NaN flags
+        self._acc32 = None
+        self._acc_count = 0
+        self._acc_flag = torch.zeros(1, dtype=torch.float32, device=dev)
         self.step_idx = 0
         self.last_lr = None
         # modules that cache tensors derived from parameters (RWKV7Attention._stacked_mix): the optimizer kernel rewrites
@@ -494,7 +526,7 @@ class DataParallelTrainer:
         base = self.current_lr()
         return {g[0]: base * g[1] for g in self.group_defs}
 
-    def _torch_adamw(self, lr, skip, lo_s=None, hi_s=None):
+    def _torch_adamw(self, lr, skip, lo_s=None, hi_s=None, coef=None):
         g_all = self.flat.flat_grad
         b1, b2 = self.betas
         t = self.step_idx + 1
@@ -508,6 +540,8 @@ class DataParallelTrainer:
             _, scale, wd = self.group_defs[gi]
             p, m, v = self.master[s:e], self.exp_avg[s:e], self.exp_avg_sq[s:e]
             g = g_all[s:e].to(p.dtype)
+            if coef is not None:
+                g = g * coef
             g = torch.where(skip.to(torch.bool), torch.zeros_like(g), g)
             lr_g = lr * scale
             p.mul_(1.0 - lr_g * wd)
@@ -538,6 +572,100 @@ class DataParallelTrainer:
         for w in works:
             w.wait()
 
+    def _grad_sumsq(self, lo, hi):
+        """self._sumsq = sum of squares of flat_grad[lo:hi] (0 for an empty slab), on the device."""
+        if hi <= lo:
+            self._sumsq.zero_()
+        elif self.hip_adamw:
+            from . import _lib
+            P = lambda t: ctypes.c_void_p(t.data_ptr())
+            with torch.cuda.device_of(self.master):
+                rc = _lib.lib().rwkv7_grad_sumsq_bf16(
+                    ctypes.c_long(hi - lo), P(self.flat.flat_grad[lo:hi]), P(self._sumsq_partials), P(self._sumsq), 0,
+                    ctypes.c_void_p(torch.cuda.current_stream(self.master.device).cuda_stream))
+            _lib.check(rc, "grad_sumsq")
+        else:
+            self._sumsq.copy_(self.flat.flat_grad[lo:hi].double().pow(2).sum().reshape(1))
+
+    def _adamw_clip(self, lo, hi, lr):
+        """AdamW on [lo, hi) with the gradient scaled by min(1, max_grad_norm / (sqrt(self._sumsq) + 1e-6)); a non-finite sum
+        makes it a zero-gradient step.  Neither value is read on the host."""
+        if hi <= lo:
+            return
+        if self.hip_adamw:
+            from . import _lib
+            P = lambda t: ctypes.c_void_p(t.data_ptr())
+            f = ctypes.c_float
+            with torch.cuda.device_of(self.master):
+                rc = _lib.lib().rwkv7_adamw_groups_clip_bf16(
+                    ctypes.c_long(hi - lo), P(self.master[lo:hi]), P(self.flat.flat_grad[lo:hi]), P(self.exp_avg[lo:hi]),
+                    P(self.exp_avg_sq[lo:hi]), P(self.flat.flat_param[lo:hi]), P(self.slab_group[lo // 128:hi // 128]), P(self.group_tab),
+                    len(self.group_defs), P(self.nan_flag), P(self._sumsq), f(self.max_grad_norm),
+                    f(lr), f(self.betas[0]), f(self.betas[1]), f(self.eps), self.step_idx + 1,
+                    ctypes.c_void_p(torch.cuda.current_stream(self.master.device).cuda_stream))
+            _lib.check(rc, "adamw_clip")
+        else:
+            ss = self._sumsq[0]
+            coef = torch.clamp(self.max_grad_norm / (ss.sqrt() + 1e-6), max=1.0).to(self.master.dtype)
+            skip = torch.maximum(self.nan_flag, (~torch.isfinite(ss)).to(self.nan_flag.dtype).reshape(1))
+            self._torch_adamw(lr, skip, lo, hi, coef=coef)
+
+    def _fold(self, lo, hi, inv_count):
+        """flat_grad[lo:hi] = round((fp32 sum of the earlier micro-batches + flat_grad[lo:hi]) * inv_count), in place."""
+        if hi <= lo:
+            return
+        g = self.flat.flat_grad[lo:hi]
+        if self.hip_adamw:
+            from . import _lib
+            with torch.cuda.device_of(self.master):
+                rc = _lib.lib().rwkv7_grad_fold_bf16(
+                    ctypes.c_long(hi - lo), ctypes.c_void_p(self._acc32[lo:hi].data_ptr()), ctypes.c_void_p(g.data_ptr()),
+                    ctypes.c_float(inv_count), ctypes.c_void_p(torch.cuda.current_stream(self.master.device).cuda_stream))
+            _lib.check(rc, "grad_fold")
+        else:
+            g.copy_(((self._acc32[lo:hi] + g.float()) * inv_count).to(g.dtype))
+
+    def accumulate(self, **batch):
+        """One micro-batch of gradient accumulation (`accum_grad` / `gradient_accumulation_steps` of the reference recipes,
+        third_party/cosyvoice/utils/train_utils.py:87-89): forward and backward into the flat bf16 buffer, then that gradient is
+        added to an fp32 buffer of flat.numel elements (allocated on first use; DeepSpeed's bf16 engine accumulates in fp32 too).
+        No collective is issued and the reducer's bucket bookkeeping is left as if the pass had not happened; the NaN flag of the
+        micro-batch joins a running max.  k - 1 calls followed by step() make one optimizer step on the mean gradient of the k
+        micro-batches.  Returns the (detached) loss tensor."""
+        if self._acc32 is None:
+            self._acc32 = torch.empty(self.flat.numel, dtype=torch.float32, device=self.flat.flat_grad.device)
+        first = self._acc_count == 0
+        self.flat.arm()
+        on_ready, self.flat.on_ready = self.flat.on_ready, None   # the reducer does not see this pass
+        try:
+            loss = self.model(**batch).loss
+            if self.nan_guard:
+                bad = (~torch.isfinite(loss.detach())).reshape(1).to(self._acc_flag.dtype)
+                if first:
+                    self._acc_flag.copy_(bad)
+                else:
+                    torch.maximum(self._acc_flag, bad, out=self._acc_flag)
+            else:
+                self._acc_flag.zero_()
+            loss.backward()
+            self.flat.finish_backward(reattach=True)
+        finally:
+            self.flat.on_ready = on_ready
+        if self.hip_adamw:
+            from . import _lib
+            with torch.cuda.device_of(self.master):
+                rc = _lib.lib().rwkv7_grad_accum_bf16(
+                    ctypes.c_long(self.flat.numel), ctypes.c_void_p(self._acc32.data_ptr()),
+                    ctypes.c_void_p(self.flat.flat_grad.data_ptr()), int(first),
+                    ctypes.c_void_p(torch.cuda.current_stream(self.master.device).cuda_stream))
+            _lib.check(rc, "grad_accum")
+        elif first:
+            self._acc32.copy_(self.flat.flat_grad)
+        else:
+            self._acc32.add_(self.flat.flat_grad.float())
+        self._acc_count += 1
+        return loss.detach()
+
     def step(self, **batch):
         """One optimisation step on this rank's shard of the batch.  Returns the (detached) loss tensor.
 
@@ -545,13 +673,23 @@ class DataParallelTrainer:
         `isnan(loss)` -> every rank backpropagates loss * 0 and steps on a zero gradient, train_spark_rwkv7speech.py:
         664-687) keeps its flag on the device -- the all-reduce is enqueued before backward, backward runs regardless,
         and the optimizer kernel reads the flag and substitutes a zero gradient.  Nothing waits for `flag.item()`, so
-        the gradient buckets start as soon as backward reaches them."""
+        the gradient buckets start as soon as backward reaches them.
+
+        After k - 1 accumulate() calls this batch is the k-th micro-batch: every bucket is folded with the fp32 sum of the earlier
+        gradients (rwkv7_grad_fold_bf16, mean over k, one rounding to bf16) right before it goes on the wire, so the exchange still
+        overlaps this backward pass; the NaN flag that is all-reduced is the max over the k micro-batches.  Without a preceding
+        accumulate() nothing of that runs."""
+        k = self._acc_count + 1
+        if k > 1:
+            self.reducer.pre_exchange = lambda s_, e_: self._fold(s_, e_, 1.0 / k)
         self.flat.arm()
         out = self.model(**batch)
         loss = out.loss
         flag_work = None
         if self.nan_guard:
             self.nan_flag.copy_((~torch.isfinite(loss.detach())).reshape(1))
+            if k > 1:
+                torch.maximum(self.nan_flag, self._acc_flag, out=self.nan_flag)
             if self.world > 1:
                 flag_work = dist.all_reduce(self.nan_flag, op=dist.ReduceOp.MAX, async_op=True)  # :664-670
         else:
@@ -585,8 +723,21 @@ class DataParallelTrainer:
             for s_, e_ in runs:
                 adamw(s_, e_)
 
-        stepped = self.reducer.finish(on_bucket if self.bucket_optimizer and not self.shard_optimizer else None)
-        if not stepped:
+        clip = self.max_grad_norm is not None
+        stepped = self.reducer.finish(on_bucket if self.bucket_optimizer and not self.shard_optimizer and not clip else None)
+        if k > 1:
+            self.reducer.pre_exchange = None
+            if not self.reducer.enabled:
+                self._fold(0, self.flat.numel, 1.0 / k)   # no exchange to overlap: one pass
+            self._acc_count = 0
+        if clip:   # the norm needs every bucket: one sum-of-squares pass, then one optimizer pass behind it
+            lo, hi = self.reducer.slab(self.reducer.rank) if self.shard_optimizer else (0, self.flat.numel)
+            self._grad_sumsq(lo, hi)
+            if self.shard_optimizer:
+                dist.all_reduce(self._sumsq, op=dist.ReduceOp.SUM, group=self.reducer.group)
+            torch.sqrt(self._sumsq[0], out=self.last_grad_norm)
+            self._adamw_clip(lo, hi, lr)
+        elif not stepped:
             adamw(*(self.reducer.slab(self.reducer.rank) if self.shard_optimizer else (0, self.flat.numel)))
         if self.shard_optimizer:
             self._broadcast_slabs()
