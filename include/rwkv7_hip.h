@@ -455,6 +455,24 @@ int rwkv7_ce_fwd_bwd_ls_bf16(long rows, int V, void *logits, const long *labels,
  *      neither read nor written). */
 int rwkv7_ce_fwd_bwd_ld_bf16(long rows, int V, long ld, void *logits, const long *labels, long ignore_index, float scale, float *loss_rows,
                              float label_smoothing, rwkv7_stream_t stream);
+/* ---- Cosy head loss: label-smoothing KL loss (cosyvoice/transformer/label_smoothing_loss.py:68-96), its gradient and the accuracy
+ *      flag (cosyvoice/utils/common.py:76-95) of a chunk of bf16 logits [rows, ld] in one pass.  Columns V .. ld - 1 are neither read
+ *      nor written.  dlogits (bf16 [rows, ld]) MAY be the same pointer as logits (in place); otherwise the logits are left intact.
+ *      Target distribution of a row with label y: t_y = 1 - s, t_j = s / (V - 1) for j != y, s = smoothing in [0, 1).  With lse the
+ *      log-sum-exp of the row's V logits:
+ *        loss_rows[row]    = C - (1 - s)(x_y - lse) - s/(V-1) ((sum_j x_j - x_y) - (V-1) lse),
+ *                            C = (1-s) ln(1-s) + s ln(s/(V-1)) with 0 ln 0 = 0, computed by this entry on the HOST in double and handed
+ *                            to the kernel as a float
+ *        dlogits[row][j]   = (softmax_j - t_j) * scale, rounded to bf16 once from the fp32 value
+ *        correct_rows[row] = 1 if the LOWEST index among the row's maxima equals y, else 0 (torch.argmax's rule on the CPU; exact ties
+ *                            are common in bf16 logits)
+ *      Rows with label == ignore_index give loss_rows = 0, correct_rows = 0 and dlogits = 0.  Reductions run in fp32 from the bf16
+ *      logits with the running maximum subtracted before exp.  Labels must be ignore_index or lie in [0, V): they are NOT checked on the
+ *      device (the kernel indexes x[label]).  RWKV7_EINVAL, before any launch: a NULL pointer, rows <= 0, V < 2, ld < V, smoothing
+ *      outside [0, 1).  Fastest when logits and dlogits agree modulo 16 bytes (always true in place) and V <= 8192 (the row stays in
+ *      registers: one read, one write); any V, ld >= V and alignment is correct. ---- */
+int rwkv7_kl_acc_fwd_bwd_bf16(long rows, int V, long ld, const void *logits, void *dlogits, const long *labels, long ignore_index,
+                              float smoothing, float scale, float *loss_rows, int *correct_rows, rwkv7_stream_t stream);
 
 /* ---- optimizer step (train_spark_rwkv7speech.py:178-197; torch.optim.AdamW update rule, decoupled weight decay) on a
  *      flat parameter buffer: fp32 master weights p32 and moments m, v updated in place from bf16 gradients g16; the

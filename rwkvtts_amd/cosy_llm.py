@@ -18,15 +18,16 @@ from torch.nn.utils.rnn import pad_sequence
 
 from .backbone import Cache, ModelOutput, RWKV7Config, RWKV7Model
 from .hf_api import HFModelMixin
-from .losses import label_smoothing_kl, th_accuracy
+from .losses import fused_linear_kl_accuracy, label_smoothing_kl, label_smoothing_kl_fused, th_accuracy
 
 IGNORE_ID = -1  # cosyvoice/utils/common.py:24
 
 
 class RWKV7CosyConfig(RWKV7Config):
-    """cosy_llm.py:13-22."""
+    """cosy_llm.py:13-22.  fused_loss (not in the reference, default off): the training loss through rwkv7_kl_acc_fwd_bwd_bf16 instead
+    of the fp32 tensor chain of label_smoothing_kl (losses.label_smoothing_kl_fused); the returned logits are the same bits."""
     _EXTRA = dict(llm_input_size=None, llm_output_size=None, speech_token_size=6561, length_normalized_loss=True,
-                  lsm_weight=0.0, mix_ratio=(5, 15), drop_ratio=0.0)
+                  lsm_weight=0.0, mix_ratio=(5, 15), drop_ratio=0.0, fused_loss=False)
 
     def __init__(self, **kw):
         base = {k: v for k, v in kw.items() if k in RWKV7Config.__dataclass_fields__ and k != "extra"}
@@ -122,8 +123,8 @@ class RWKV7CosyLM(HFModelMixin, nn.Module):
         self.speech_token_size = config.speech_token_size
 
     def criterion_ce(self, logits, target):
-        return label_smoothing_kl(logits, target, self.speech_token_size + 1, IGNORE_ID, self.config.lsm_weight,
-                                  self.config.length_normalized_loss)
+        kl = label_smoothing_kl_fused if self.config.fused_loss else label_smoothing_kl
+        return kl(logits, target, self.speech_token_size + 1, IGNORE_ID, self.config.lsm_weight, self.config.length_normalized_loss)
 
     def pad_unpad_sequence(self, sos_eos_emb, text_token, text_token_len, task_id_emb, speech_token, speech_token_len):
         """Per sample [sos, text[:n_t], task_id, speech[:n_s]], right-padded to the longest sample.  Behaviour of
@@ -325,8 +326,11 @@ class RWKV7LM(nn.Module):
     causal LM (here: backbone + lm_head); text embeddings come from llm.get_input_embeddings()."""
 
     def __init__(self, llm_input_size, llm_output_size, speech_token_size, llm: RWKV7CosyLM, sampling: Callable = None,
-                 length_normalized_loss=True, lsm_weight=0.0, mix_ratio=(5, 15), drop_ratio=0.0):
+                 length_normalized_loss=True, lsm_weight=0.0, mix_ratio=(5, 15), drop_ratio=0.0, fused_loss=False):
         super().__init__()
+        # fused_loss (not in the reference): loss and accuracy from the backbone's hidden states through losses.fused_linear_kl_accuracy
+        # -- the [B, L, V] logits never exist.  Needs an llm that exposes .model and .lm_head (RWKV7CosyLM does).
+        self.fused_loss = fused_loss
         self.llm_input_size, self.llm_output_size, self.speech_token_size = llm_input_size, llm_output_size, speech_token_size
         self.sos_eos, self.task_id, self.fill_token = 0, 1, 2
         self.llm_embedding = nn.Embedding(2, llm_input_size)
@@ -355,8 +359,14 @@ class RWKV7LM(nn.Module):
                                                            speech_token_len)
         if self.dropout is not None:
             lm_input = self.dropout(lm_input)
-        logits = self.llm(inputs_embeds=lm_input, attention_mask=attention_mask).logits
         lm_target = lm_target[:, 1:].contiguous()
+        if self.fused_loss and hasattr(self.llm, "model") and hasattr(self.llm, "lm_head"):
+            hidden = self.llm.model(inputs_embeds=lm_input, attention_mask=attention_mask)[0]
+            loss, acc = fused_linear_kl_accuracy(hidden, lm_target, self.llm.lm_head.weight, self.llm.lm_head.bias, lm_target.shape[0],
+                                                 self.lsm_weight, self.length_normalized_loss, ignore_index=IGNORE_ID,
+                                                 n_valid=sum(int(n) + 1 for n in speech_token_len))   # speech ids + EOS per sample
+            return {"loss": loss, "acc": acc}
+        logits = self.llm(inputs_embeds=lm_input, attention_mask=attention_mask).logits
         loss = label_smoothing_kl(logits, lm_target, self.speech_token_size + 1, IGNORE_ID, self.lsm_weight,
                                   self.length_normalized_loss)
         acc = th_accuracy(logits.view(-1, self.speech_token_size + 1), lm_target, ignore_label=IGNORE_ID)

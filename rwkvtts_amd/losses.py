@@ -6,6 +6,8 @@ fused_linear_cross_entropy : stands in for rwkvfla's FusedLinearCrossEntropyLoss
     same pass and scaled by the incoming grad in backward.
 label_smoothing_kl         : third_party/cosyvoice/transformer/label_smoothing_loss.py:21-96 (Cosy layout).
 th_accuracy                : third_party/cosyvoice/utils/common.py:76-95.
+fused_linear_kl_accuracy   : the two above on the head GEMM's bf16 logits chunk by chunk through rwkv7_kl_acc_fwd_bwd_bf16 (opt-in:
+    RWKV7LM(fused_loss=True)); label_smoothing_kl_fused: the loss alone on logits the caller keeps (RWKV7CosyConfig(fused_loss=True)).
 """
 import os
 
@@ -193,3 +195,140 @@ def th_accuracy(pad_outputs, pad_targets, ignore_label):
     mask = pad_targets != ignore_label
     num = torch.sum(pred.masked_select(mask) == pad_targets.masked_select(mask))
     return (num / torch.sum(mask)).detach()
+
+
+KL_ACC_HITS = [0]   # launches of rwkv7_kl_acc_fwd_bwd_bf16 (one per chunk): how a test sees which route a call took
+
+
+def _kl_acc_gate(x, labels, *more):
+    return (HIP_CE and x.is_cuda and x.dtype == torch.bfloat16 and labels.dtype == torch.int64
+            and all(m is None or (m.is_cuda and m.dtype == torch.bfloat16) for m in more))
+
+
+def _kl_acc_rows(logits, dlogits, labels, V, ignore_index, smoothing, scale=1.0):
+    """rwkv7_kl_acc_fwd_bwd_bf16 on 2-D bf16 logits [rows, ld] (unit column stride; columns V.. untouched): writes
+    (softmax - true_dist) * scale into dlogits (which may BE logits) and returns (loss_rows fp32 [rows], correct_rows int32 [rows])."""
+    import ctypes
+    from . import _lib
+    rows, ld = logits.shape[0], logits.stride(0)
+    assert logits.stride(1) == 1 and dlogits.stride() == logits.stride() and dlogits.shape == logits.shape
+    if CHECK_LABELS:
+        bad = (labels != ignore_index) & ((labels < 0) | (labels >= V))
+        assert not bool(bad.any()), f"labels outside [0, {V}) that are not ignore_index={ignore_index}"
+    lab = labels.contiguous()
+    loss_rows = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    correct = torch.empty(rows, dtype=torch.int32, device=logits.device)
+    with torch.cuda.device_of(logits):
+        rc = _lib.lib().rwkv7_kl_acc_fwd_bwd_bf16(
+            ctypes.c_long(rows), ctypes.c_int(V), ctypes.c_long(ld), ctypes.c_void_p(logits.data_ptr()), ctypes.c_void_p(dlogits.data_ptr()),
+            ctypes.c_void_p(lab.data_ptr()), ctypes.c_long(ignore_index), ctypes.c_float(float(smoothing)), ctypes.c_float(scale),
+            ctypes.c_void_p(loss_rows.data_ptr()), ctypes.c_void_p(correct.data_ptr()),
+            ctypes.c_void_p(torch.cuda.current_stream(logits.device).cuda_stream))
+    _lib.check(rc, "kl_acc_fwd_bwd")
+    KL_ACC_HITS[0] += 1
+    return loss_rows, correct
+
+
+class _FusedLinearKLAcc(torch.autograd.Function):
+    """_FusedLinearCE's shape for the Cosy head: per chunk of rows the bf16 logits of F.linear, the KL/accuracy kernel IN PLACE, then
+    dh, dw and db from the overwritten buffer.  A denominator the HOST knows (the batch size, or n_valid when the caller counted the
+    valid tokens while it built the targets) goes into the kernel's `scale`: d loss / d logits is then rounded to bf16 from the same
+    fp32 value as in the torch chain, and backward multiplies by the incoming gradient alone (exact for the usual 1.0).  A valid-token
+    count that exists on the device only stays there -- no host synchronisation -- and is folded into the incoming gradient in
+    backward: d loss / d logits is then rounded before the division instead of after it (the same relative precision, other values).
+    Either way dh [N, D], dw and db are kept in fp32 until backward (the GEMMs write fp32): each is scaled and rounded to bf16 ONCE,
+    like the output of the parent's bf16 GEMMs."""
+
+    @staticmethod
+    def forward(ctx, hidden, weight, bias, labels, batch_size, smoothing, normalize_length, ignore_index, chunk, n_valid):
+        N, V = hidden.shape[0], weight.shape[0]
+        total = (labels != ignore_index).sum()
+        host_denom = (n_valid or None) if normalize_length else batch_size   # nothing valid: the device route gives the pair's nan
+        scale = 1.0 / host_denom if host_denom is not None else 1.0
+        need = ctx.needs_input_grad
+        loss = torch.zeros((), dtype=torch.float32, device=hidden.device)
+        ncorrect = torch.zeros((), dtype=torch.int64, device=hidden.device)
+        dh = torch.empty_like(hidden, dtype=torch.float32) if need[0] else None   # 4 N D bytes: small next to a chunk's [rows, V]
+        dw = torch.zeros_like(weight, dtype=torch.float32) if need[1] else None
+        db = torch.zeros_like(bias, dtype=torch.float32) if (bias is not None and need[2]) else None
+        for s in range(0, N, chunk):
+            h = hidden[s:s + chunk]
+            pd = F.linear(h, weight, bias)   # bf16 logits as nn.Linear gives them
+            loss_rows, correct = _kl_acc_rows(pd, pd, labels[s:s + chunk], V, ignore_index, smoothing, scale)
+            loss += loss_rows.sum()
+            ncorrect += correct.sum()
+            if need[0]:
+                dh[s:s + chunk] = torch.mm(pd, weight, out_dtype=torch.float32)   # fp32 out of the GEMM: rounded after the scale
+            if need[1]:
+                dw += torch.mm(pd.t(), h, out_dtype=torch.float32)   # ... and no bf16 rounding of a chunk's partial sum
+            if db is not None:
+                db += pd.sum(0, dtype=torch.float32)
+        denom = total if normalize_length else batch_size
+        ctx.save_for_backward(dh, dw, db, total)
+        ctx.on_device, ctx.wdtype, ctx.hdtype = host_denom is None, weight.dtype, hidden.dtype
+        acc = ncorrect / total
+        ctx.mark_non_differentiable(acc)
+        return loss / denom, acc
+
+    @staticmethod
+    def backward(ctx, g, _gacc):
+        dh, dw, db, total = ctx.saved_tensors
+        g = g.float() / total if ctx.on_device else g.float()
+        return ((dh * g).to(ctx.hdtype) if dh is not None else None,   # fp32 buffers: scaled in fp32, rounded once
+                (dw * g).to(ctx.wdtype) if dw is not None else None,
+                (db * g).to(ctx.wdtype) if db is not None else None, None, None, None, None, None, None, None)
+
+
+def fused_linear_kl_accuracy(hidden, labels, weight, bias, batch_size, smoothing, normalize_length, ignore_index=-1, chunk=None,
+                             n_valid=None):
+    """hidden [..., D], labels [...] -> (loss, acc) of the Cosy head: label_smoothing_kl and th_accuracy of F.linear(hidden, weight, bias)
+    without the [rows, V] logits or any fp32 tensor of that size (bf16 CUDA hidden / weight / bias, int64 labels: the HIP kernel on one
+    chunk of bf16 logits at a time).  Anything else computes the same two values from materialised logits.  batch_size: the denominator
+    when normalize_length is false.  chunk: rows per round of head GEMMs (None: auto_chunk).  n_valid (optional, a Python int): the
+    number of labels != ignore_index when the caller knows it on the host; it only moves the division in front of the gradient's bf16
+    rounding (see _FusedLinearKLAcc) and must be the true count."""
+    D, V = hidden.shape[-1], weight.shape[0]
+    h2, lab = hidden.reshape(-1, D), labels.reshape(-1)
+    if not (_kl_acc_gate(h2, lab, weight, bias) and 0 <= smoothing < 1):
+        logits = F.linear(h2, weight, bias)
+        loss = label_smoothing_kl(logits.unsqueeze(0), lab.unsqueeze(0), V, ignore_index, smoothing, normalize_length)   # "batch" of 1
+        return loss if normalize_length else loss / batch_size, th_accuracy(logits, lab.unsqueeze(0), ignore_index)
+    if chunk is None:
+        chunk = auto_chunk(h2.shape[0], V, h2.element_size())
+    return _FusedLinearKLAcc.apply(h2, weight, bias, lab, batch_size, float(smoothing), normalize_length, ignore_index, chunk, n_valid)
+
+
+class _KLFromLogits(torch.autograd.Function):
+    """The loss alone on logits the caller keeps: the kernel out of place (d loss / d logits into its own bf16 buffer, scale = 1).
+    backward multiplies that buffer by the incoming gradient / denominator in fp32, a slab of rows at a time (the fp32 temporary is
+    at most 256 MiB, never [rows, V]): unless that factor is a power of two, d loss / d logits is rounded to bf16 twice -- within one
+    bf16 ulp of the fp32 value instead of half of one, an RMS rounding error of at most sqrt(2) times the single rounding's.  (One rounding would need the factor
+    at launch time: a host read of a device scalar in every backward.)"""
+
+    @staticmethod
+    def forward(ctx, logits2, labels, batch_size, smoothing, normalize_length, ignore_index):
+        total = (labels != ignore_index).sum()
+        dlogits = torch.empty_like(logits2)
+        loss_rows, _ = _kl_acc_rows(logits2, dlogits, labels, logits2.shape[1], ignore_index, smoothing)
+        ctx.save_for_backward(dlogits, total)
+        ctx.by_tokens, ctx.batch_size = bool(normalize_length), batch_size
+        return loss_rows.sum() / (total if normalize_length else batch_size)
+
+    @staticmethod
+    def backward(ctx, g):
+        dlogits, total = ctx.saved_tensors
+        g = g.float() / (total if ctx.by_tokens else ctx.batch_size)
+        out = torch.empty_like(dlogits)
+        step = max(1, (1 << 26) // dlogits.shape[1])   # 2^26 fp32 elements per slab
+        for r in range(0, dlogits.shape[0], step):
+            out[r:r + step] = dlogits[r:r + step].float() * g
+        return out, None, None, None, None, None
+
+
+def label_smoothing_kl_fused(logits, target, size, padding_idx, smoothing, normalize_length=False):
+    """label_smoothing_kl with the fp32 chain replaced by the HIP kernel where it applies (bf16 CUDA logits, int64 target); the logits
+    are left as they are."""
+    x, t = logits.reshape(-1, size), target.reshape(-1)
+    if not (_kl_acc_gate(x, t) and 0 <= smoothing < 1 and x.is_contiguous()):
+        return label_smoothing_kl(logits, target, size, padding_idx, smoothing, normalize_length)
+    return _KLFromLogits.apply(x, t, logits.shape[0], float(smoothing), normalize_length, padding_idx)
