@@ -184,13 +184,8 @@ def sample_slots(logits: torch.Tensor, st: SlotState, row_slot: Optional[torch.T
     assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
     if row_slot is not None:
         assert row_slot.dtype == torch.int32 and row_slot.is_contiguous() and row_slot.numel() == logits.shape[0]
-    p = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)
-    with torch.cuda.device_of(logits):
-        rc = _lib.lib().rwkv7_sample_slots_f32(logits.shape[0], p(logits), ctypes.c_long(logits.stride(0)), p(row_slot), p(allow_lo),
-                                               p(allow_hi), p(suppress), 0 if suppress is None else suppress.numel(),
-                                               int(logits.shape[1] if max_domain is None else max_domain), ctypes.byref(st),
-                                               ctypes.c_void_p(torch.cuda.current_stream(logits.device).cuda_stream))
-    _lib.check(rc, "rwkv7_sample_slots_f32")
+    _lib.call("rwkv7_sample_slots_f32", logits, logits.shape[0], logits, logits.stride(0), row_slot, allow_lo, allow_hi, suppress,
+              0 if suppress is None else suppress.numel(), int(logits.shape[1] if max_domain is None else max_domain), ctypes.byref(st))
 
 
 class ContinuousDecoder:

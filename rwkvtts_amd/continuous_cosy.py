@@ -50,12 +50,7 @@ def ras_slots(logits: torch.Tensor, st: RasSlotState, row_slot: Optional[torch.T
     assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
     if row_slot is not None:
         assert row_slot.dtype == torch.int32 and row_slot.is_contiguous() and row_slot.numel() == logits.shape[0]
-    with torch.cuda.device_of(logits):
-        rc = _lib.lib().rwkv7_ras_slots_f32(logits.shape[0], logits.shape[1], ctypes.c_void_p(logits.data_ptr()),
-                                            ctypes.c_long(logits.stride(0)),
-                                            ctypes.c_void_p(row_slot.data_ptr() if row_slot is not None else None), ctypes.byref(st),
-                                            ctypes.c_void_p(torch.cuda.current_stream(logits.device).cuda_stream))
-    _lib.check(rc, "rwkv7_ras_slots_f32")
+    _lib.call("rwkv7_ras_slots_f32", logits, logits.shape[0], logits.shape[1], logits, logits.stride(0), row_slot, ctypes.byref(st))
 
 
 @dataclass

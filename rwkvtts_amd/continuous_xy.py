@@ -79,10 +79,6 @@ class XYSlotState(ctypes.Structure):
                 ("n_eos", ctypes.c_int), ("reference_termination", ctypes.c_int)]
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else None)
-
-
 def xy_slots_draw(logits: torch.Tensor, st: XYSlotState, seg_off, seg_len, allow_lo, allow_hi, max_domain: int,
                   row_slot: Optional[torch.Tensor] = None):
     """rwkv7_xy_slots_draw_f32 on the current stream: logits fp32 [rows, width] (unit column stride); seg_off / seg_len / allow_lo /
@@ -90,21 +86,15 @@ def xy_slots_draw(logits: torch.Tensor, st: XYSlotState, seg_off, seg_len, allow
     assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
     if row_slot is not None:
         assert row_slot.dtype == torch.int32 and row_slot.is_contiguous() and row_slot.numel() == logits.shape[0]
-    with torch.cuda.device_of(logits):
-        rc = _lib.lib().rwkv7_xy_slots_draw_f32(logits.shape[0], _p(logits), ctypes.c_long(logits.stride(0)), _p(row_slot), _p(seg_off),
-                                                _p(seg_len), _p(allow_lo), _p(allow_hi), int(max_domain), ctypes.byref(st),
-                                                ctypes.c_void_p(torch.cuda.current_stream(logits.device).cuda_stream))
-    _lib.check(rc, "rwkv7_xy_slots_draw_f32")
+    _lib.call("rwkv7_xy_slots_draw_f32", logits, logits.shape[0], logits, logits.stride(0), row_slot, seg_off, seg_len, allow_lo, allow_hi,
+              int(max_domain), ctypes.byref(st))
 
 
 def xy_slots_frame(rows: int, st: XYSlotState, device, row_slot: Optional[torch.Tensor] = None):
     """rwkv7_xy_slots_frame_bf16 on the current stream of `device`, for `rows` rows (row_slot as in xy_slots_draw)."""
     if row_slot is not None:
         assert row_slot.dtype == torch.int32 and row_slot.is_contiguous() and row_slot.numel() == rows
-    with torch.cuda.device(device):
-        rc = _lib.lib().rwkv7_xy_slots_frame_bf16(int(rows), _p(row_slot), ctypes.byref(st),
-                                                  ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream))
-    _lib.check(rc, "rwkv7_xy_slots_frame_bf16")
+    _lib.call("rwkv7_xy_slots_frame_bf16", device, int(rows), row_slot, ctypes.byref(st))
 
 
 class ContinuousXYDecoder:

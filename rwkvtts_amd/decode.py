@@ -61,9 +61,7 @@ class DecodeStep:
         self.dims = _Dims(self.B, cfg.hidden_size, cfg.num_heads, len(backbone.layers), backbone.layers[0].ffn.key.weight.shape[0],
                           lm_head.weight.shape[0], a0.w_lora.rank, a0.a_lora.rank, backbone.layers[1].attn.v_lora.rank
                           if len(backbone.layers) > 1 else 32, a0.g_lora.rank, cfg.norm_eps, a0.g_norm.eps)
-        query = getattr(lib, self.WORKSPACE)
-        query.restype = ctypes.c_size_t
-        nbytes = query(ctypes.byref(self.dims))
+        nbytes = getattr(lib, self.WORKSPACE)(ctypes.byref(self.dims))
         if nbytes == 0:
             raise ValueError(self.ENTRY + ": unsupported shape")
         dev = lm_head.weight.device
@@ -128,19 +126,11 @@ class DecodeStep:
 
     def __call__(self, x_in: torch.Tensor) -> torch.Tensor:
         assert x_in.shape == (self.B, self.dims.D) and x_in.dtype == torch.bfloat16 and x_in.is_contiguous()
-        hb = self.head.bias
-        with torch.cuda.device_of(x_in):
-            tail = (ctypes.c_void_p(x_in.data_ptr()),
-                    ctypes.c_void_p(self.norm.weight.data_ptr()), ctypes.c_void_p(self.norm.bias.data_ptr()),
-                    ctypes.c_void_p(self.head.weight.data_ptr()), ctypes.c_void_p(hb.data_ptr() if hb is not None else None),
-                    ctypes.c_void_p(self.logits.data_ptr()), ctypes.c_void_p(self.workspace.data_ptr()), int(self.persistent),
-                    ctypes.c_void_p(torch.cuda.current_stream(x_in.device).cuda_stream))
-            if self.host_table:
-                rc = _lib.lib().rwkv7_decode_step_tbl_bf16(ctypes.byref(self.dims), ctypes.c_void_p(self.table.data_ptr()),
-                                                           ctypes.c_void_p(self.table_host.data_ptr()), *tail)
-            else:
-                rc = _lib.lib().rwkv7_decode_step_bf16(ctypes.byref(self.dims), ctypes.c_void_p(self.table.data_ptr()), *tail)
-        _lib.check(rc, "rwkv7_decode_step_tbl_bf16" if self.host_table else "rwkv7_decode_step_bf16")
+        tail = (x_in, self.norm.weight, self.norm.bias, self.head.weight, self.head.bias, self.logits, self.workspace, self.persistent)
+        if self.host_table:
+            _lib.call("rwkv7_decode_step_tbl_bf16", x_in, ctypes.byref(self.dims), self.table, self.table_host, *tail)
+        else:
+            _lib.call("rwkv7_decode_step_bf16", x_in, ctypes.byref(self.dims), self.table, *tail)
         return self.logits
 
     def barrier_timed_out(self) -> bool:
@@ -164,15 +154,8 @@ class WideDecodeStep(DecodeStep):
 
     def __call__(self, x_in: torch.Tensor) -> torch.Tensor:
         assert x_in.shape == (self.B, self.dims.D) and x_in.dtype == torch.bfloat16 and x_in.is_contiguous()
-        hb = self.head.bias
-        p = ctypes.c_void_p
-        with torch.cuda.device_of(x_in):
-            rc = _lib.lib().rwkv7_decode_step_wide_bf16(
-                ctypes.byref(self.dims), p(self.table.data_ptr()), p(self.table_host.data_ptr() if self.host_table else None),
-                p(x_in.data_ptr()), p(self.norm.weight.data_ptr()), p(self.norm.bias.data_ptr()), p(self.head.weight.data_ptr()),
-                p(hb.data_ptr() if hb is not None else None), p(self.logits.data_ptr()), p(self.workspace.data_ptr()),
-                p(torch.cuda.current_stream(x_in.device).cuda_stream))
-        _lib.check(rc, self.ENTRY)
+        _lib.call(self.ENTRY, x_in, ctypes.byref(self.dims), self.table, self.table_host if self.host_table else None, x_in,
+                  self.norm.weight, self.norm.bias, self.head.weight, self.head.bias, self.logits, self.workspace)
         return self.logits
 
     def barrier_timed_out(self) -> bool:

@@ -21,14 +21,6 @@ _MIX_BWD_ROWS = 4     # rows per run in mix_bwd (neighbours carried in registers
 _MIX_BWD_BLOCKS = 1024
 
 
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _stream(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
 def _sfx(t):
     if not t.is_cuda:
         raise NotImplementedError("fused RWKV-7 stages run on the HIP device only (no CPU path)")
@@ -44,9 +36,13 @@ def _c(t):
 
 
 def _call(name, ref, *args):
-    with torch.cuda.device_of(ref):
-        rc = getattr(_lib.lib(), f"rwkv7_{name}_{_sfx(ref)}")(*args, _stream(ref))
-    _lib.check(rc, name)
+    _lib.call(f"rwkv7_{name}_{_sfx(ref)}", ref, *args)
+
+
+def _p(t):
+    """A tensor's address (None: NULL) for code that hands _call raw pointers (tests/test_fused_rows_gpu.py drives the C entries of the
+    time-mix backward pair that way); _call itself takes the tensors as they are."""
+    return None if t is None else t.data_ptr()
 
 
 COLSUM_KERNEL = os.environ.get("RWKV7_COLSUM_KERNEL", "1") == "1"
@@ -59,9 +55,7 @@ def _colsum(part, dtype):
         n = part[0].numel()
         if n % 4 == 0 and n <= 32768:
             out = torch.empty(part.shape[1:], dtype=dtype, device=part.device)
-            with torch.cuda.device_of(part):
-                rc = _lib.lib().rwkv7_sum_slabs_bf16(ctypes.c_long(n), part.shape[0], _p(part), _p(out), 0, _stream(part))
-            _lib.check(rc, "sum_slabs(colsum)")
+            _lib.call("rwkv7_sum_slabs_bf16", part, n, part.shape[0], part, out, 0)
             return out
     return part.sum(0).to(dtype)
 
@@ -84,7 +78,7 @@ class _Mix(torch.autograd.Function):
         nmix = params.shape[0]
         out = torch.empty(nmix, B, T, D, dtype=x.dtype, device=x.device)
         xp = None if x_prev is None else _c(x_prev.to(x.dtype))
-        _call("mix_fwd", x, B, T, D, nmix, _p(x), _p(xp), _p(mask), _p(params), _p(out), min(B * T, _MIX_FWD_BLOCKS))
+        _call("mix_fwd", x, B, T, D, nmix, x, xp, mask, params, out, min(B * T, _MIX_FWD_BLOCKS))
         ctx.save_for_backward(x, xp, mask, params)
         ctx.xp_dtype = None if x_prev is None else x_prev.dtype
         return tuple(out[i] for i in range(nmix))
@@ -99,8 +93,8 @@ class _Mix(torch.autograd.Function):
         nb = max(1, min(-(-B * T // _MIX_BWD_ROWS), _MIX_BWD_BLOCKS))
         dx = torch.empty_like(x)
         part = torch.empty(nb, nmix, D, dtype=torch.float32, device=x.device)
-        ptrs = (ctypes.c_void_p * nmix)(*[g.data_ptr() for g in gs])
-        _call("mix_bwd", x, B, T, D, nmix, ptrs, _p(x), _p(xp), _p(mask), _p(params), _p(dx), _p(part), nb, _MIX_BWD_ROWS)
+        ptrs = _lib.ptr_array(gs)
+        _call("mix_bwd", x, B, T, D, nmix, ptrs, x, xp, mask, params, dx, part, nb, _MIX_BWD_ROWS)
         dxp = None
         if ctx.needs_input_grad[1]:
             # mix_fwd takes the carried row x_prev UNMASKED as the step before t = 0: d out_i[:, 0] / d x_prev = params[i]
@@ -132,7 +126,7 @@ class _MixLora(torch.autograd.Function):
         x, params, wcat = _c(x), _c(params), _c(wcat)
         nmix = params.shape[0]
         out = torch.empty(nmix, B, T, D, dtype=x.dtype, device=x.device)
-        _call("mix_fwd", x, B, T, D, nmix, _p(x), _p(None), _p(mask), _p(params), _p(out), min(B * T, _MIX_FWD_BLOCKS))
+        _call("mix_fwd", x, B, T, D, nmix, x, None, mask, params, out, min(B * T, _MIX_FWD_BLOCKS))
         G = torch.mm(x.view(-1, D), wcat.t())
         ctx.save_for_backward(x, mask, params, wcat)
         FUSED_MIX_LORA_HITS[0] += 1
@@ -148,8 +142,8 @@ class _MixLora(torch.autograd.Function):
         nb = max(1, min(-(-B * T // _MIX_BWD_ROWS), _MIX_BWD_BLOCKS))
         dx = torch.empty_like(x)
         part = torch.empty(nb, nmix, D, dtype=torch.float32, device=x.device)
-        ptrs = (ctypes.c_void_p * nmix)(*[g.data_ptr() for g in gs])
-        _call("mix_bwd", x, B, T, D, nmix, ptrs, _p(x), _p(None), _p(mask), _p(params), _p(dx), _p(part), nb, _MIX_BWD_ROWS)
+        ptrs = _lib.ptr_array(gs)
+        _call("mix_bwd", x, B, T, D, nmix, ptrs, x, None, mask, params, dx, part, nb, _MIX_BWD_ROWS)
         dwcat = None
         if dG is not None:
             dG2 = _c(dG).view(-1, dG.shape[-1])
@@ -175,10 +169,6 @@ def mix_lora_supported(x, state, seq_start, w1s=None, mask=None):
     return True
 
 
-def _ptr_array(ts):
-    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-
-
 class _WcatBuild(torch.autograd.Function):
     """wcat [2 R, D] = [W1_i * (1 - mu_i) ; W1_i * mu_i] of all branches (rwkv7_mix_lora_wcat_*: one small kernel each way instead of
     a dozen tensor ops per branch)."""
@@ -190,9 +180,7 @@ class _WcatBuild(torch.autograd.Function):
         ranks = (ctypes.c_int * nb)(*[w.shape[0] for w in w1s])
         R = sum(w.shape[0] for w in w1s)
         wcat = torch.empty(2 * R, D, dtype=w1s[0].dtype, device=w1s[0].device)
-        with torch.cuda.device_of(wcat):
-            rc = _lib.lib().rwkv7_mix_lora_wcat_fwd_bf16(nb, ranks, _ptr_array(w1s), _ptr_array(mus), D, _p(wcat), _stream(wcat))
-        _lib.check(rc, "mix_lora_wcat_fwd")
+        _lib.call("rwkv7_mix_lora_wcat_fwd_bf16", wcat, nb, ranks, _lib.ptr_array(w1s), _lib.ptr_array(mus), D, wcat)
         ctx.save_for_backward(*w1s, *mus)
         ctx.nb = nb
         ctx.mu_shapes = [t.shape for t in ts[nb:]]
@@ -208,10 +196,8 @@ class _WcatBuild(torch.autograd.Function):
         dwcat = _c(dwcat)
         dw1 = [torch.empty_like(w) for w in w1s]
         dmu = [torch.empty(D, dtype=w1s[0].dtype, device=w1s[0].device) for _ in range(nb)]
-        with torch.cuda.device_of(dwcat):
-            rc = _lib.lib().rwkv7_mix_lora_wcat_bwd_bf16(nb, ranks, _ptr_array(w1s), _ptr_array(mus), D, _p(dwcat), _ptr_array(dw1),
-                                                         _ptr_array(dmu), _stream(dwcat))
-        _lib.check(rc, "mix_lora_wcat_bwd")
+        _lib.call("rwkv7_mix_lora_wcat_bwd_bf16", dwcat, nb, ranks, _lib.ptr_array(w1s), _lib.ptr_array(mus), D, dwcat, _lib.ptr_array(dw1),
+                  _lib.ptr_array(dmu))
         return (None, *dw1, *[g.view(sh) for g, sh in zip(dmu, ctx.mu_shapes)])
 
 
@@ -228,9 +214,7 @@ class _CombineAct(torch.autograd.Function):
         nb = len(ranks)
         outs = [torch.empty(B, T, r, dtype=G.dtype, device=G.device) for r in ranks]
         cr, ca = (ctypes.c_int * nb)(*ranks), (ctypes.c_int * nb)(*acts)
-        with torch.cuda.device_of(G):
-            rc = _lib.lib().rwkv7_mix_lora_combine_fwd_bf16(nb, cr, ca, ctypes.c_long(B * T), T, _p(G), _p(mask), _ptr_array(outs), _stream(G))
-        _lib.check(rc, "mix_lora_combine_fwd")
+        _lib.call("rwkv7_mix_lora_combine_fwd_bf16", G, nb, cr, ca, B * T, T, G, mask, _lib.ptr_array(outs))
         ctx.save_for_backward(mask, *outs)
         ctx.ranks, ctx.acts, ctx.shape = ranks, acts, (B, T, R2)
         return tuple(outs)
@@ -243,10 +227,7 @@ class _CombineAct(torch.autograd.Function):
         das = [torch.zeros_like(o) if g is None else _c(g) for g, o in zip(das, outs)]
         dG = torch.empty(B, T, R2, dtype=outs[0].dtype, device=outs[0].device)
         cr, ca = (ctypes.c_int * nb)(*ctx.ranks), (ctypes.c_int * nb)(*ctx.acts)
-        with torch.cuda.device_of(dG):
-            rc = _lib.lib().rwkv7_mix_lora_combine_bwd_bf16(nb, cr, ca, ctypes.c_long(B * T), T, _p(mask), _ptr_array(outs), _ptr_array(das),
-                                                            _p(dG), _stream(dG))
-        _lib.check(rc, "mix_lora_combine_bwd")
+        _lib.call("rwkv7_mix_lora_combine_bwd_bf16", dG, nb, cr, ca, B * T, T, mask, _lib.ptr_array(outs), _lib.ptr_array(das), dG)
         return dG, None, None, None
 
 
@@ -283,17 +264,13 @@ class _MixLoraDirect(torch.autograd.Function):
         w1s, mus = [_c(t) for t in ts[:nb]], [_c(t.reshape(-1)) for t in ts[nb:]]
         nmix = params.shape[0]
         out = torch.empty(nmix, B, T, D, dtype=x.dtype, device=x.device)
-        _call("mix_fwd", x, B, T, D, nmix, _p(x), _p(None), _p(mask), _p(params), _p(out), min(B * T, _MIX_FWD_BLOCKS))
+        _call("mix_fwd", x, B, T, D, nmix, x, None, mask, params, out, min(B * T, _MIX_FWD_BLOCKS))
         ranks = [w.shape[0] for w in w1s]
         cr, ca = (ctypes.c_int * nb)(*ranks), (ctypes.c_int * nb)(*acts)
         packed = torch.empty(sum(ranks), D, dtype=x.dtype, device=x.device)
         hs = [torch.empty(B, T, r, dtype=x.dtype, device=x.device) for r in ranks]
-        with torch.cuda.device_of(x):
-            rc = _lib.lib().rwkv7_lora_down_pack_bf16(nb, cr, _ptr_array(w1s), D, _p(packed), _stream(x))
-            _lib.check(rc, "lora_down_pack")
-            rc = _lib.lib().rwkv7_lora_down_fwd_bf16(nb, cr, ca, ctypes.c_long(B * T), T, D, _p(x), _p(mask), _ptr_array(mus), _p(packed),
-                                                     _ptr_array(hs), _stream(x))
-            _lib.check(rc, "lora_down_fwd")
+        _lib.call("rwkv7_lora_down_pack_bf16", x, nb, cr, _lib.ptr_array(w1s), D, packed)
+        _lib.call("rwkv7_lora_down_fwd_bf16", x, nb, cr, ca, B * T, T, D, x, mask, _lib.ptr_array(mus), packed, _lib.ptr_array(hs))
         ctx.save_for_backward(x, mask, params, *w1s, *mus, *hs)
         ctx.nb, ctx.acts, ctx.mu_shapes = nb, acts, [t.shape for t in ts[nb:]]
         LORA_DOWN_DIRECT_HITS[0] += 1
@@ -312,29 +289,22 @@ class _MixLoraDirect(torch.autograd.Function):
         cr, ca = (ctypes.c_int * nb)(*ranks), (ctypes.c_int * nb)(*ctx.acts)
         das = [torch.zeros_like(h) if g is None else _c(g) for g, h in zip(gs[nmix:], hs)]
         dG = torch.empty(B * T, 2 * R, dtype=x.dtype, device=x.device)
-        with torch.cuda.device_of(x):
-            rc = _lib.lib().rwkv7_mix_lora_combine_bwd_bf16(nb, cr, ca, ctypes.c_long(B * T), T, _p(mask), _ptr_array(hs), _ptr_array(das),
-                                                            _p(dG), _stream(x))
-            _lib.check(rc, "mix_lora_combine_bwd")
+        _lib.call("rwkv7_mix_lora_combine_bwd_bf16", x, nb, cr, ca, B * T, T, mask, _lib.ptr_array(hs), _lib.ptr_array(das), dG)
         g3 = [torch.zeros_like(x) if g is None else _c(g) for g in gs[:nmix]]
         nblk = max(1, min(-(-B * T // _MIX_BWD_ROWS), _MIX_BWD_BLOCKS))
         dx = torch.empty_like(x)
         part = torch.empty(nblk, nmix, D, dtype=torch.float32, device=x.device)
-        ptrs = (ctypes.c_void_p * nmix)(*[g.data_ptr() for g in g3])
-        _call("mix_bwd", x, B, T, D, nmix, ptrs, _p(x), _p(None), _p(mask), _p(params), _p(dx), _p(part), nblk, _MIX_BWD_ROWS)
+        ptrs = _lib.ptr_array(g3)
+        _call("mix_bwd", x, B, T, D, nmix, ptrs, x, None, mask, params, dx, part, nblk, _MIX_BWD_ROWS)
         wcat = torch.empty(2 * R, D, dtype=x.dtype, device=x.device)
-        with torch.cuda.device_of(x):
-            rc = _lib.lib().rwkv7_mix_lora_wcat_fwd_bf16(nb, cr, _ptr_array(w1s), _ptr_array(mus), D, _p(wcat), _stream(x))
-            _lib.check(rc, "mix_lora_wcat_fwd")
+        _lib.call("rwkv7_mix_lora_wcat_fwd_bf16", x, nb, cr, _lib.ptr_array(w1s), _lib.ptr_array(mus), D, wcat)
         # the library's addmm_ stays: an own kernel of this family did the shape in 69 us against 51.5 (profiles/r06zz_lora_dx_ab.txt)
         dx.view(-1, D).addmm_(dG, wcat)
         dwcat = _c(wgrad_splitk(dG, x.view(-1, D), slabs=WGRAD_SLABS_WCAT))
         dw1 = [torch.empty_like(w) for w in w1s]
         dmu = [torch.empty(D, dtype=x.dtype, device=x.device) for _ in range(nb)]
-        with torch.cuda.device_of(x):
-            rc = _lib.lib().rwkv7_mix_lora_wcat_bwd_bf16(nb, cr, _ptr_array(w1s), _ptr_array(mus), D, _p(dwcat), _ptr_array(dw1),
-                                                         _ptr_array(dmu), _stream(x))
-            _lib.check(rc, "mix_lora_wcat_bwd")
+        _lib.call("rwkv7_mix_lora_wcat_bwd_bf16", x, nb, cr, _lib.ptr_array(w1s), _lib.ptr_array(mus), D, dwcat, _lib.ptr_array(dw1),
+                  _lib.ptr_array(dmu))
         return (dx, None, _colsum(part, params.dtype), None, None, *dw1, *[g.view(sh) for g, sh in zip(dmu, ctx.mu_shapes)])
 
 
@@ -371,7 +341,7 @@ class _ReluSq(torch.autograd.Function):
     def forward(ctx, x):
         x = _c(x)
         y = torch.empty_like(x)
-        _call("relusq_fwd", x, ctypes.c_long(x.numel()), _p(x), _p(y))
+        _call("relusq_fwd", x, x.numel(), x, y)
         ctx.save_for_backward(x)
         return y
 
@@ -380,7 +350,7 @@ class _ReluSq(torch.autograd.Function):
         (x,) = ctx.saved_tensors
         dy = _c(dy)
         dx = torch.empty_like(x)
-        _call("relusq_bwd", x, ctypes.c_long(x.numel()), _p(x), _p(dy), _p(dx))
+        _call("relusq_bwd", x, x.numel(), x, dy, dx)
         return dx
 
 
@@ -416,9 +386,7 @@ class _KeyReluSq(torch.autograd.Function):
         M, K = x2.shape
         N = w.shape[0]
         s = torch.empty(M, N, dtype=x.dtype, device=x.device)
-        with torch.cuda.device_of(x):
-            rc = _lib.lib().rwkv7_gemm_nt_bf16(M, N, K, _p(x2), _p(w), _p(s), 1, _stream(x))
-        _lib.check(rc, "gemm_nt_relusq")
+        _lib.call("rwkv7_gemm_nt_bf16", x, M, N, K, x2, w, s, 1)
         FUSED_KEY_RELUSQ_HITS[0] += 1
         ctx.save_for_backward(x, weight, s)
         ctx.wparam = weight
@@ -429,7 +397,7 @@ class _KeyReluSq(torch.autograd.Function):
         x, weight, s = ctx.saved_tensors
         ds2 = _c(ds).view(-1, ds.shape[-1])
         dk = torch.empty_like(s)
-        _call("relusq_bwd_s", s, ctypes.c_long(s.numel()), _p(s), _p(ds2), _p(dk))
+        _call("relusq_bwd_s", s, s.numel(), s, ds2, dk)
         x2 = _c(x).view(-1, x.shape[-1])
         dx = _dgrad(dk, weight).view(x.shape) if ctx.needs_input_grad[0] else None
         dw = None
@@ -462,7 +430,7 @@ class _ReluSqValue(torch.autograd.Function):
     def forward(ctx, h, weight):
         h2 = _c(h).view(-1, h.shape[-1])
         s = torch.empty_like(h2)
-        _call("relusq_fwd", h2, ctypes.c_long(h2.numel()), _p(h2), _p(s))
+        _call("relusq_fwd", h2, h2.numel(), h2, s)
         out = torch.nn.functional.linear(s, weight)
         ctx.save_for_backward(h2, s, weight)
         ctx.wparam = weight
@@ -479,9 +447,7 @@ class _ReluSqValue(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             wt = weight.detach().t().contiguous()     # [F, D]: the NT operand (8 MiB at 0.4B, one copy per layer and step)
             dh = torch.empty_like(h2)
-            with torch.cuda.device_of(h2):
-                rc = _lib.lib().rwkv7_gemm_nt_relusq_bwd_bf16(M, F, D, _p(d2), _p(wt), _p(h2), _p(dh), _stream(h2))
-            _lib.check(rc, "gemm_nt_relusq_bwd")
+            _lib.call("rwkv7_gemm_nt_relusq_bwd_bf16", h2, M, F, D, d2, wt, h2, dh)
             dh = dh.view(ctx.shape)
         dw = _wgrad(d2, s, ctx.wparam) if ctx.needs_input_grad[1] else None
         return dh, dw
@@ -512,9 +478,7 @@ def _dgrad(dy2, weight):
     if (DGRAD_NT and dy2.is_cuda and dy2.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and dy2.shape[0] >= WGRAD_MIN_ROWS
             and N % 64 == 0 and K % 64 == 0 and N >= DGRAD_NT_MIN_N and K >= 256 and weight.is_contiguous() and dy2.is_contiguous()):
         wt = torch.empty(K, N, dtype=weight.dtype, device=weight.device)
-        with torch.cuda.device_of(dy2):
-            rc = _lib.lib().rwkv7_transpose_bf16(N, K, _p(weight), _p(wt), _stream(dy2))
-        _lib.check(rc, "transpose(dgrad)")
+        _lib.call("rwkv7_transpose_bf16", dy2, N, K, weight, wt)
         DGRAD_NT_HITS[0] += 1
         return torch.mm(dy2, wt.t())
     return torch.mm(dy2, weight)
@@ -539,9 +503,7 @@ class _ChannelMix(torch.autograd.Function):
         M, D = x2.shape
         F = wkc.shape[0]
         s = torch.empty(M, F, dtype=x.dtype, device=x.device)
-        with torch.cuda.device_of(x):
-            rc = _lib.lib().rwkv7_gemm_nt_bf16(M, F, D, _p(x2), _p(wkc), _p(s), 1, _stream(x))
-        _lib.check(rc, "gemm_nt_relusq")
+        _lib.call("rwkv7_gemm_nt_bf16", x, M, F, D, x2, wkc, s, 1)
         FUSED_CMIX_HITS[0] += 1
         out = torch.nn.functional.linear(s, wv)
         ctx.save_for_backward(x2, s, wk, wv)
@@ -557,15 +519,11 @@ class _ChannelMix(torch.autograd.Function):
         D = wv.shape[0]
         if TRANSPOSE_KERNEL and D % 64 == 0 and F % 64 == 0 and wv.is_contiguous():
             wt = torch.empty(F, D, dtype=wv.dtype, device=wv.device)      # [F, D]: the NT operand (8 MiB at 0.4B, once per layer and step)
-            with torch.cuda.device_of(s):
-                rc = _lib.lib().rwkv7_transpose_bf16(D, F, _p(wv), _p(wt), _stream(s))
-            _lib.check(rc, "transpose")
+            _lib.call("rwkv7_transpose_bf16", s, D, F, wv, wt)
         else:
             wt = wv.detach().t().contiguous()
         dk = torch.empty_like(s)
-        with torch.cuda.device_of(s):
-            rc = _lib.lib().rwkv7_gemm_nt_relusq_bwd_s_bf16(M, F, D, _p(d2), _p(wt), _p(s), _p(dk), _stream(s))
-        _lib.check(rc, "gemm_nt_relusq_bwd_s")
+        _lib.call("rwkv7_gemm_nt_relusq_bwd_s_bf16", s, M, F, D, d2, wt, s, dk)
         dx = _dgrad(dk, wk).view(ctx.shape) if ctx.needs_input_grad[0] else None
         dwk = _wgrad(dk, x2, ctx.wk) if ctx.needs_input_grad[1] else None
         dwv = _wgrad(d2, s, ctx.wv) if ctx.needs_input_grad[2] else None
@@ -604,8 +562,7 @@ class _TmixPrepare(torch.autograd.Function):
         k_k, k_a = _c(k_k.to(k.dtype)), _c(k_a.to(k.dtype))
         outs = [torch.empty_like(k) for _ in range(5)]
         rows = B * T
-        _call("tmix_prepare_fwd", k, ctypes.c_long(rows), D, _p(w_pre), _p(k), _p(v), _p(a_pre), _p(v_pre), _p(v_first), _p(mask),
-              _p(k_k), _p(k_a), *[_p(o) for o in outs], min(rows, _FWD_BLOCKS))
+        _call("tmix_prepare_fwd", k, rows, D, w_pre, k, v, a_pre, v_pre, v_first, mask, k_k, k_a, *outs, min(rows, _FWD_BLOCKS))
         ctx.save_for_backward(w_pre, k, v, a_pre, v_pre, v_first, k_k, k_a, mask)
         return tuple(outs)
 
@@ -620,9 +577,8 @@ class _TmixPrepare(torch.autograd.Function):
         d_vpre = torch.empty_like(k) if v_pre is not None else None
         d_vf = torch.empty_like(k) if v_pre is not None else None
         part = torch.empty(nb, 5, D, dtype=torch.float32, device=k.device)
-        _call("tmix_prepare_bwd", k, ctypes.c_long(rows), D, _p(w_pre), _p(k), _p(v), _p(a_pre), _p(v_pre), _p(v_first), _p(mask),
-              _p(k_k), _p(k_a), *[_p(g) for g in gs], _p(d_wpre), _p(d_k), _p(d_v), _p(d_apre), _p(d_vpre), _p(d_vf),
-              _p(part), nb)
+        _call("tmix_prepare_bwd", k, rows, D, w_pre, k, v, a_pre, v_pre, v_first, mask, k_k, k_a, *gs, d_wpre, d_k, d_v, d_apre, d_vpre,
+              d_vf, part, nb)
         dp = _colsum(part, k.dtype)
         _attach_colsums(dp, d_wpre, d_apre, d_vpre)
         return d_wpre, d_k, d_v, d_apre, d_vpre, d_vf, dp[0], dp[1], None
@@ -644,8 +600,7 @@ class _TmixPost(torch.autograd.Function):
         gn_w, gn_b, r_k = _c(gn_w.to(y.dtype)), _c(gn_b.to(y.dtype)), _c(r_k.reshape(-1).to(y.dtype))
         out = torch.empty_like(y)
         rows = B * T
-        _call("tmix_post_fwd", y, ctypes.c_long(rows), D, _p(y), _p(r), _p(k), _p(v), _p(g), _p(gn_w), _p(gn_b), _p(r_k),
-              ctypes.c_float(eps), _p(out), min(rows, _FWD_BLOCKS))
+        _call("tmix_post_fwd", y, rows, D, y, r, k, v, g, gn_w, gn_b, r_k, eps, out, min(rows, _FWD_BLOCKS))
         ctx.save_for_backward(y, r, k, v, g, gn_w, gn_b, r_k)
         ctx.eps = eps
         return out
@@ -659,8 +614,7 @@ class _TmixPost(torch.autograd.Function):
         dout = _c(dout)
         d_y, d_r, d_k, d_v, d_g = [torch.empty_like(y) for _ in range(5)]
         part = torch.empty(nb, 3, D, dtype=torch.float32, device=y.device)
-        _call("tmix_post_bwd", y, ctypes.c_long(rows), D, _p(dout), _p(y), _p(r), _p(k), _p(v), _p(g), _p(gn_w), _p(gn_b), _p(r_k),
-              ctypes.c_float(ctx.eps), _p(d_y), _p(d_r), _p(d_k), _p(d_v), _p(d_g), _p(part), nb)
+        _call("tmix_post_bwd", y, rows, D, dout, y, r, k, v, g, gn_w, gn_b, r_k, ctx.eps, d_y, d_r, d_k, d_v, d_g, part, nb)
         dp = _colsum(part, y.dtype)
         return d_y, d_r, d_k, d_v, d_g, dp[0], dp[1], dp[2], None
 
@@ -698,8 +652,8 @@ class _TmixCore(torch.autograd.Function):
         gn_w, gn_b, r_k = _c(gn_w.to(k.dtype)), _c(gn_b.to(k.dtype)), _c(r_k.reshape(-1).to(k.dtype))
         rows = B * T
         w, k2, v2, a_in, b_in = [torch.empty_like(k) for _ in range(5)]
-        _call("tmix_prepare_fwd", k, ctypes.c_long(rows), D, _p(w_pre), _p(k), _p(v), _p(a_pre), _p(v_pre), _p(v_first),
-              _p(mask), _p(k_k), _p(k_a), _p(w), _p(k2), _p(v2), _p(a_in), _p(b_in), min(rows, _FWD_BLOCKS))
+        _call("tmix_prepare_fwd", k, rows, D, w_pre, k, v, a_pre, v_pre, v_first, mask, k_k, k_a, w, k2, v2, a_in, b_in,
+              min(rows, _FWD_BLOCKS))
         v4 = lambda t: t.view(B, T, H, 64)
         via_op = VIA_REFERENCE_OP and seq_start is None
         chunked = CHUNKED_WKV_FWD and CHUNKED_WKV_BWD and k.dtype == torch.bfloat16 and T % ops.CHUNK_T == 0 and not via_op
@@ -719,8 +673,7 @@ class _TmixCore(torch.autograd.Function):
             else:
                 ops.wkv7_forward_scalar(v4(w), v4(r), v4(k2), v4(v2), v4(a_in), v4(b_in), v4(y), s, sa)
         out = torch.empty_like(k)
-        _call("tmix_post_fwd", k, ctypes.c_long(rows), D, _p(y), _p(r), _p(k2), _p(v2), _p(g), _p(gn_w), _p(gn_b), _p(r_k),
-              ctypes.c_float(eps), _p(out), min(rows, _FWD_BLOCKS))
+        _call("tmix_post_fwd", k, rows, D, y, r, k2, v2, g, gn_w, gn_b, r_k, eps, out, min(rows, _FWD_BLOCKS))
         ctx.save_for_backward(r, w_pre, k, v, a_pre, g, v_pre, v_first, k_k, k_a, gn_w, gn_b, r_k, mask,
                               w, k2, v2, a_in, b_in, y, s, sa, tinv)
         ctx.H, ctx.eps, ctx.chunked_fwd, ctx.seq_start, ctx.via_op = H, eps, chunked, seq_start, via_op
@@ -751,13 +704,12 @@ class _TmixCore(torch.autograd.Function):
             d_y, dt_post, d_g = [torch.empty_like(k) for _ in range(3)]
             hscal = torch.empty(rows, H, 2, dtype=torch.float32, device=k.device)
             d_r_post = d_k2_post = d_v2_post = None
-            _call("tmix_post_bwd_compact", k, ctypes.c_long(rows), D, _p(dout), _p(y), _p(r), _p(k2), _p(v2), _p(g), _p(gn_w),
-                  _p(gn_b), _p(r_k), ctypes.c_float(ctx.eps), _p(d_y), _p(dt_post), _p(d_g), _p(hscal), _p(part_post), nb)
+            _call("tmix_post_bwd_compact", k, rows, D, dout, y, r, k2, v2, g, gn_w, gn_b, r_k, ctx.eps, d_y, dt_post, d_g, hscal, part_post,
+                  nb)
         else:
             d_y, d_r_post, d_k2_post, d_v2_post, d_g = [torch.empty_like(k) for _ in range(5)]
-            _call("tmix_post_bwd", k, ctypes.c_long(rows), D, _p(dout), _p(y), _p(r), _p(k2), _p(v2), _p(g), _p(gn_w), _p(gn_b),
-                  _p(r_k), ctypes.c_float(ctx.eps), _p(d_y), _p(d_r_post), _p(d_k2_post), _p(d_v2_post), _p(d_g),
-                  _p(part_post), nb)
+            _call("tmix_post_bwd", k, rows, D, dout, y, r, k2, v2, g, gn_w, gn_b, r_k, ctx.eps, d_y, d_r_post, d_k2_post, d_v2_post, d_g,
+                  part_post, nb)
         # 2. scan: chunked MFMA backward (bf16, T % 32 == 0) or the scalar kernel with two workgroups per head
         if WGRAD_SYNC_BEFORE_SCAN:
             wgrad_side_sync(k.device)
@@ -783,10 +735,9 @@ class _TmixCore(torch.autograd.Function):
                 dq2[0], dq2[1], d_r_post, d_vf_next]
         if compact:
             gsum += [dt_post, r, r_k, hscal]
-        ptrs = (ctypes.c_void_p * len(gsum))(*[None if t is None else t.data_ptr() for t in gsum])
-        _call("tmix_prepare_bwd_sum_compact" if compact else "tmix_prepare_bwd_sum", k, ctypes.c_long(rows), D, _p(w_pre), _p(k), _p(v), _p(a_pre), _p(v_pre), _p(v_first),
-              _p(mask), _p(k_k), _p(k_a), ptrs, _p(d_wpre), _p(d_k), _p(d_v), _p(d_apre), _p(d_vpre), _p(d_vf),
-              _p(d_r), _p(part), nb)
+        ptrs = _lib.ptr_array(gsum)
+        _call("tmix_prepare_bwd_sum_compact" if compact else "tmix_prepare_bwd_sum", k, rows, D, w_pre, k, v, a_pre, v_pre, v_first, mask,
+              k_k, k_a, ptrs, d_wpre, d_k, d_v, d_apre, d_vpre, d_vf, d_r, part, nb)
         dp = _colsum(part, k.dtype)
         dpp = _colsum(part_post, k.dtype)
         _attach_colsums(dp, d_wpre, d_apre, d_vpre)
@@ -824,10 +775,7 @@ def lora_decode(x, w1, w2, bias, activation):
     x2 = _c(x).view(rows, K)
     b2 = None if bias is None else _c(bias)
     y = torch.empty(rows, N, dtype=torch.bfloat16, device=x.device)
-    with torch.cuda.device_of(x):
-        rc = _lib.lib().rwkv7_lora32_bf16(rows, N, K, R, _ACT_ID[activation], _p(x2), _p(_c(w1)), _p(_c(w2)), _p(b2), _p(y),
-                                          _stream(x))
-    _lib.check(rc, "lora32")
+    _lib.call("rwkv7_lora32_bf16", x, rows, N, K, R, _ACT_ID[activation], x2, _c(w1), _c(w2), b2, y)
     return y.view(*x.shape[:-1], N)
 
 
@@ -864,11 +812,8 @@ def wgrad_splitk(dy2, x2, out=None, slabs=None):
         part = torch.empty(S, N, K, dtype=torch.float32, device=dy2.device)
         if out is None:
             out = torch.empty(N, K, dtype=torch.bfloat16, device=dy2.device)
-        with torch.cuda.device_of(part):
-            rc = _lib.lib().rwkv7_wgrad_skinny_bf16(ctypes.c_long(M), N, K, S, _p(dy2), _p(x2), _p(part), _stream(part))
-            _lib.check(rc, "wgrad_skinny")
-            rc = _lib.lib().rwkv7_sum_slabs_bf16(ctypes.c_long(N * K), S, _p(part), _p(out), 0, _stream(part))
-        _lib.check(rc, "sum_slabs")
+        _lib.call("rwkv7_wgrad_skinny_bf16", part, M, N, K, S, dy2, x2, part)
+        _lib.call("rwkv7_sum_slabs_bf16", part, N * K, S, part, out, 0)
         return out
     if (MID_WGRAD and dy2.dtype == torch.bfloat16 and x2.dtype == torch.bfloat16 and N in (512, 576) and K % 256 == 0 and M >= WGRAD_MIN_ROWS
             and M % (MID_WGRAD_SLABS * 64) == 0 and dy2.is_contiguous() and x2.is_contiguous()):
@@ -877,11 +822,8 @@ def wgrad_splitk(dy2, x2, out=None, slabs=None):
         part = torch.empty(S, N, K, dtype=torch.float32, device=dy2.device)
         if out is None:
             out = torch.empty(N, K, dtype=torch.bfloat16, device=dy2.device)
-        with torch.cuda.device_of(part):
-            rc = _lib.lib().rwkv7_wgrad_mid_bf16(ctypes.c_long(M), N, K, S, _p(dy2), _p(x2), _p(part), _stream(part))
-            _lib.check(rc, "wgrad_mid")
-            rc = _lib.lib().rwkv7_sum_slabs_bf16(ctypes.c_long(N * K), S, _p(part), _p(out), 0, _stream(part))
-        _lib.check(rc, "sum_slabs")
+        _lib.call("rwkv7_wgrad_mid_bf16", part, M, N, K, S, dy2, x2, part)
+        _lib.call("rwkv7_sum_slabs_bf16", part, N * K, S, part, out, 0)
         MID_WGRAD_HITS[0] += 1
         return out
     S = slabs if slabs else (WGRAD_SLABS_SMALL if N * K <= 1024 * 1024 else WGRAD_SLABS_BIG)
@@ -900,9 +842,7 @@ def wgrad_splitk(dy2, x2, out=None, slabs=None):
         return res
     if out is None:
         out = torch.empty(N, K, dtype=torch.bfloat16, device=dy2.device)
-    with torch.cuda.device_of(part):
-        rc = _lib.lib().rwkv7_sum_slabs_bf16(ctypes.c_long(N * K), S, _p(part), _p(out), 0, _stream(part))
-    _lib.check(rc, "sum_slabs")
+    _lib.call("rwkv7_sum_slabs_bf16", part, N * K, S, part, out, 0)
     return out
 
 
@@ -917,9 +857,7 @@ class _GatherRows(torch.autograd.Function):
     def forward(ctx, src, idx, inv):
         src = _c(src)
         out = torch.empty(idx.numel(), src.shape[1], dtype=src.dtype, device=src.device)
-        with torch.cuda.device_of(src):
-            rc = _lib.lib().rwkv7_gather_rows_bf16(ctypes.c_long(idx.numel()), src.shape[1], _p(src), _p(idx), _p(out), _stream(src))
-        _lib.check(rc, "gather_rows")
+        _lib.call("rwkv7_gather_rows_bf16", src, idx.numel(), src.shape[1], src, idx, out)
         ctx.save_for_backward(idx, inv)
         return out
 
@@ -928,9 +866,7 @@ class _GatherRows(torch.autograd.Function):
         idx, inv = ctx.saved_tensors
         g = _c(g)
         dsrc = torch.empty(inv.numel(), g.shape[1], dtype=g.dtype, device=g.device)
-        with torch.cuda.device_of(g):
-            rc = _lib.lib().rwkv7_gather_rows_bf16(ctypes.c_long(inv.numel()), g.shape[1], _p(g), _p(inv), _p(dsrc), _stream(g))
-        _lib.check(rc, "gather_rows(bwd)")
+        _lib.call("rwkv7_gather_rows_bf16", g, inv.numel(), g.shape[1], g, inv, dsrc)
         return dsrc, None, None
 
 
@@ -1106,9 +1042,7 @@ def linear(x, weight, bias=None):
         x2, w2 = _c(x).view(rows, K), _c(weight)
         b2 = None if bias is None else _c(bias.to(torch.bfloat16))
         y = torch.empty(rows, N, dtype=torch.bfloat16, device=x.device)
-        with torch.cuda.device_of(x):
-            rc = _lib.lib().rwkv7_gemv32_bf16(rows, N, K, _p(x2), _p(w2), _p(b2), _p(y), _stream(x))
-        _lib.check(rc, "gemv32")
+        _lib.call("rwkv7_gemv32_bf16", x, rows, N, K, x2, w2, b2, y)
         return y.view(*x.shape[:-1], N)
     if (x.is_cuda and x.dtype == torch.bfloat16 and torch.is_grad_enabled() and weight.requires_grad
             and x.numel() // x.shape[-1] >= WGRAD_MIN_ROWS):
@@ -1140,9 +1074,7 @@ class _LinearAdd(torch.autograd.Function):
         M, K = y2.shape
         N = w.shape[0]
         out = torch.empty(M, N, dtype=y.dtype, device=y.device)
-        with torch.cuda.device_of(y):
-            rc = _lib.lib().rwkv7_gemm_nt_add_bf16(M, N, K, _p(y2), _p(w), _p(r2), _p(out), _stream(y))
-        _lib.check(rc, "gemm_nt_add")
+        _lib.call("rwkv7_gemm_nt_add_bf16", y, M, N, K, y2, w, r2, out)
         ctx.save_for_backward(y2, weight)
         ctx.wparam = weight
         ctx.yshape = y.shape
@@ -1186,8 +1118,7 @@ class _AddLN(torch.autograd.Function):
             x1 = torch.empty_like(x)
         else:
             x1 = None
-        _call("add_ln_fwd", x, ctypes.c_long(rows), D, _p(x), _p(branch), _p(gamma_c), _p(beta_c), ctypes.c_float(eps),
-              _p(x1), _p(h), _p(mean), _p(rstd), min(rows, _FWD_BLOCKS))
+        _call("add_ln_fwd", x, rows, D, x, branch, gamma_c, beta_c, eps, x1, h, mean, rstd, min(rows, _FWD_BLOCKS))
         ctx.has_branch, ctx.has_beta = branch is not None, beta is not None
         ctx.save_for_backward(x1 if branch is not None else x, mean, rstd, gamma_c)
         if branch is None:
@@ -1211,8 +1142,7 @@ class _AddLN(torch.autograd.Function):
         nb = min(rows, _BWD_BLOCKS)
         dx = torch.empty_like(xs)
         part = torch.empty(nb, 2, D, dtype=torch.float32, device=xs.device)
-        _call("add_ln_bwd", xs, ctypes.c_long(rows), D, _p(dh), _p(d_x1), _p(xs), _p(mean), _p(rstd), _p(gamma), _p(dx),
-              _p(part), nb)
+        _call("add_ln_bwd", xs, rows, D, dh, d_x1, xs, mean, rstd, gamma, dx, part, nb)
         dp = _colsum(part, xs.dtype)
         return dx, (dx if ctx.has_branch else None), dp[0], (dp[1] if ctx.has_beta else None), None
 
@@ -1244,8 +1174,7 @@ class _AddLNMix(torch.autograd.Function):
         else:
             x1 = None
         nb = max(1, min(-(-rows // _ADD_LN_MIX_RUN), _ADD_LN_MIX_BLOCKS))
-        _call("add_ln_mix_fwd", x, B, T, D, nmix, _p(x), _p(branch), _p(gamma_c), _p(beta_c), ctypes.c_float(eps), _p(mask),
-              _p(params), _p(x1), _p(out), _p(mean), _p(rstd), nb, _ADD_LN_MIX_RUN)
+        _call("add_ln_mix_fwd", x, B, T, D, nmix, x, branch, gamma_c, beta_c, eps, mask, params, x1, out, mean, rstd, nb, _ADD_LN_MIX_RUN)
         ctx.has_branch, ctx.has_beta = branch is not None, beta is not None
         ctx.save_for_backward(x1 if branch is not None else x, mean, rstd, gamma_c, beta_c, mask, params)
         return (x1 if branch is not None else x,) + tuple(out[i] for i in range(nmix))
@@ -1261,9 +1190,8 @@ class _AddLNMix(torch.autograd.Function):
         nb = max(1, min(-(-rows // _ADD_LN_MIX_RUN), _ADD_LN_MIX_BWD_BLOCKS))
         dx = torch.empty_like(xs)
         part = torch.empty(nb, nmix + 2, D, dtype=torch.float32, device=xs.device)
-        ptrs = (ctypes.c_void_p * nmix)(*[g.data_ptr() for g in gs])
-        _call("mix_add_ln_bwd", xs, B, T, D, nmix, ptrs, _p(d_x1), _p(xs), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(mask),
-              _p(params), _p(dx), _p(part), nb, _ADD_LN_MIX_RUN)
+        ptrs = _lib.ptr_array(gs)
+        _call("mix_add_ln_bwd", xs, B, T, D, nmix, ptrs, d_x1, xs, mean, rstd, gamma, beta, mask, params, dx, part, nb, _ADD_LN_MIX_RUN)
         dp = _colsum(part, xs.dtype) if params.dtype == xs.dtype else part.sum(0)
         return (dx, (dx if ctx.has_branch else None), dp[nmix].to(xs.dtype), (dp[nmix + 1].to(xs.dtype) if ctx.has_beta else None),
                 None, None, dp[:nmix].to(params.dtype))
@@ -1292,8 +1220,8 @@ class _AddLNMixFwd(torch.autograd.Function):
         else:
             x1 = None
         nb = max(1, min(-(-rows // _ADD_LN_MIX_RUN), _ADD_LN_MIX_BLOCKS))
-        _call("add_ln_mix_fwd_h", x, B, T, D, nmix, _p(x), _p(branch), _p(gamma_c), _p(beta_c), ctypes.c_float(eps), _p(mask),
-              _p(params), _p(x1), _p(out), _p(h), _p(mean), _p(rstd), nb, _ADD_LN_MIX_RUN)
+        _call("add_ln_mix_fwd_h", x, B, T, D, nmix, x, branch, gamma_c, beta_c, eps, mask, params, x1, out, h, mean, rstd, nb,
+              _ADD_LN_MIX_RUN)
         ctx.has_branch, ctx.has_beta = branch is not None, beta is not None
         ctx.save_for_backward(x1 if branch is not None else x, h, mean, rstd, gamma_c, mask, params)
         return (x1 if branch is not None else x,) + tuple(out[i] for i in range(nmix))
@@ -1308,13 +1236,13 @@ class _AddLNMixFwd(torch.autograd.Function):
         nb = max(1, min(-(-rows // _MIX_BWD_ROWS), _MIX_BWD_BLOCKS))
         dh = torch.empty_like(xs)
         part_m = torch.empty(nb, nmix, D, dtype=torch.float32, device=xs.device)
-        ptrs = (ctypes.c_void_p * nmix)(*[g.data_ptr() for g in gs])
-        _call("mix_bwd", xs, B, T, D, nmix, ptrs, _p(h), _p(None), _p(mask), _p(params), _p(dh), _p(part_m), nb, _MIX_BWD_ROWS)
+        ptrs = _lib.ptr_array(gs)
+        _call("mix_bwd", xs, B, T, D, nmix, ptrs, h, None, mask, params, dh, part_m, nb, _MIX_BWD_ROWS)
         d_x1 = None if d_x1 is None else _c(d_x1)
         nb2 = min(rows, _BWD_BLOCKS)
         dx = torch.empty_like(xs)
         part = torch.empty(nb2, 2, D, dtype=torch.float32, device=xs.device)
-        _call("add_ln_bwd", xs, ctypes.c_long(rows), D, _p(dh), _p(d_x1), _p(xs), _p(mean), _p(rstd), _p(gamma), _p(dx), _p(part), nb2)
+        _call("add_ln_bwd", xs, rows, D, dh, d_x1, xs, mean, rstd, gamma, dx, part, nb2)
         dp = _colsum(part, xs.dtype)
         return (dx, (dx if ctx.has_branch else None), dp[0], (dp[1] if ctx.has_beta else None),
                 None, None, _colsum(part_m, params.dtype))
@@ -1349,8 +1277,8 @@ class _AddLNMixLora(torch.autograd.Function):
         else:
             x1 = None
         nb = max(1, min(-(-rows // _ADD_LN_MIX_RUN), _ADD_LN_MIX_BLOCKS))
-        _call("add_ln_mix_fwd_h", x, B, T, D, nmix, _p(x), _p(branch), _p(gamma_c), _p(beta_c), ctypes.c_float(eps), _p(mask),
-              _p(params), _p(x1), _p(out), _p(h), _p(mean), _p(rstd), nb, _ADD_LN_MIX_RUN)
+        _call("add_ln_mix_fwd_h", x, B, T, D, nmix, x, branch, gamma_c, beta_c, eps, mask, params, x1, out, h, mean, rstd, nb,
+              _ADD_LN_MIX_RUN)
         G = torch.mm(h.view(-1, D), wcat.t())
         ctx.has_branch, ctx.has_beta = branch is not None, beta is not None
         ctx.save_for_backward(x1 if branch is not None else x, h, mean, rstd, gamma_c, mask, params, wcat)
@@ -1368,8 +1296,8 @@ class _AddLNMixLora(torch.autograd.Function):
         nb = max(1, min(-(-rows // _MIX_BWD_ROWS), _MIX_BWD_BLOCKS))
         dh = torch.empty_like(xs)
         part_m = torch.empty(nb, nmix, D, dtype=torch.float32, device=xs.device)
-        ptrs = (ctypes.c_void_p * nmix)(*[g.data_ptr() for g in gs])
-        _call("mix_bwd", xs, B, T, D, nmix, ptrs, _p(h), _p(None), _p(mask), _p(params), _p(dh), _p(part_m), nb, _MIX_BWD_ROWS)
+        ptrs = _lib.ptr_array(gs)
+        _call("mix_bwd", xs, B, T, D, nmix, ptrs, h, None, mask, params, dh, part_m, nb, _MIX_BWD_ROWS)
         dwcat = None
         if dG is not None:
             dG2 = _c(dG).view(-1, dG.shape[-1])
@@ -1379,7 +1307,7 @@ class _AddLNMixLora(torch.autograd.Function):
         nb2 = min(rows, _BWD_BLOCKS)
         dx = torch.empty_like(xs)
         part = torch.empty(nb2, 2, D, dtype=torch.float32, device=xs.device)
-        _call("add_ln_bwd", xs, ctypes.c_long(rows), D, _p(dh), _p(d_x1), _p(xs), _p(mean), _p(rstd), _p(gamma), _p(dx), _p(part), nb2)
+        _call("add_ln_bwd", xs, rows, D, dh, d_x1, xs, mean, rstd, gamma, dx, part, nb2)
         dp = _colsum(part, xs.dtype)
         return (dx, (dx if ctx.has_branch else None), dp[0], (dp[1] if ctx.has_beta else None), None, None,
                 _colsum(part_m, params.dtype), dwcat)

@@ -14,6 +14,8 @@ import os
 import torch
 import torch.nn.functional as F
 
+from . import _lib
+
 HIP_CE = os.environ.get("RWKV7_HIP_CE", "1") == "1"   # A/B switch: 0 = the torch chain for every head
 CHECK_LABELS = os.environ.get("RWKV7_CHECK_LABELS", "0") == "1"
 PADDED_HEAD = os.environ.get("RWKV7_PADDED_HEAD", "1") == "1"   # A/B switch (see _FusedLinearCE.forward)
@@ -65,26 +67,16 @@ class _FusedLinearCE(torch.autograd.Function):
             lab = labels[s:s + chunk]
             if hip_ce:
                 # bf16 logits straight from the GEMM; one kernel turns them into per-row losses and d loss / d logits
-                import ctypes
-                from . import _lib
                 rows = h.shape[0]
-                stream = ctypes.c_void_p(torch.cuda.current_stream(h.device).cuda_stream)
                 if padded:
                     pd = torch.empty(rows, Vp, dtype=h.dtype, device=h.device)
-                    with torch.cuda.device_of(h):
-                        rc = _lib.lib().rwkv7_gemm_nt_bf16(rows, Vp, D, ctypes.c_void_p(h.data_ptr()), ctypes.c_void_p(w_pad.data_ptr()),
-                                                           ctypes.c_void_p(pd.data_ptr()), 0, stream)
-                    _lib.check(rc, "gemm_nt (head logits)")
+                    _lib.call("rwkv7_gemm_nt_bf16", h, rows, Vp, D, h, w_pad, pd, 0)
                 else:
                     pd = F.linear(h, weight, bias)   # bf16 logits as nn.Linear gives them (the bias inside the GEMM's fp32 epilogue)
                 loss_rows = torch.empty(rows, dtype=torch.float32, device=pd.device)
                 lab_c = lab.contiguous()
-                with torch.cuda.device_of(pd):
-                    rc = _lib.lib().rwkv7_ce_fwd_bwd_ld_bf16(
-                        ctypes.c_long(rows), V, ctypes.c_long(pd.shape[1]), ctypes.c_void_p(pd.data_ptr()), ctypes.c_void_p(lab_c.data_ptr()),
-                        ctypes.c_long(ignore_index), ctypes.c_float(1.0), ctypes.c_void_p(loss_rows.data_ptr()),
-                        ctypes.c_float(float(label_smoothing)), stream)
-                _lib.check(rc, "ce_fwd_bwd")
+                _lib.call("rwkv7_ce_fwd_bwd_ld_bf16", pd, rows, V, pd.shape[1], pd, lab_c, ignore_index, 1.0, loss_rows,
+                          float(label_smoothing))
                 loss += loss_rows.sum()
                 if need[0]:
                     dh[s:s + chunk] = pd @ (w_pad if padded else weight)
@@ -208,8 +200,6 @@ def _kl_acc_gate(x, labels, *more):
 def _kl_acc_rows(logits, dlogits, labels, V, ignore_index, smoothing, scale=1.0):
     """rwkv7_kl_acc_fwd_bwd_bf16 on 2-D bf16 logits [rows, ld] (unit column stride; columns V.. untouched): writes
     (softmax - true_dist) * scale into dlogits (which may BE logits) and returns (loss_rows fp32 [rows], correct_rows int32 [rows])."""
-    import ctypes
-    from . import _lib
     rows, ld = logits.shape[0], logits.stride(0)
     assert logits.stride(1) == 1 and dlogits.stride() == logits.stride() and dlogits.shape == logits.shape
     if CHECK_LABELS:
@@ -218,13 +208,8 @@ def _kl_acc_rows(logits, dlogits, labels, V, ignore_index, smoothing, scale=1.0)
     lab = labels.contiguous()
     loss_rows = torch.empty(rows, dtype=torch.float32, device=logits.device)
     correct = torch.empty(rows, dtype=torch.int32, device=logits.device)
-    with torch.cuda.device_of(logits):
-        rc = _lib.lib().rwkv7_kl_acc_fwd_bwd_bf16(
-            ctypes.c_long(rows), ctypes.c_int(V), ctypes.c_long(ld), ctypes.c_void_p(logits.data_ptr()), ctypes.c_void_p(dlogits.data_ptr()),
-            ctypes.c_void_p(lab.data_ptr()), ctypes.c_long(ignore_index), ctypes.c_float(float(smoothing)), ctypes.c_float(scale),
-            ctypes.c_void_p(loss_rows.data_ptr()), ctypes.c_void_p(correct.data_ptr()),
-            ctypes.c_void_p(torch.cuda.current_stream(logits.device).cuda_stream))
-    _lib.check(rc, "kl_acc_fwd_bwd")
+    _lib.call("rwkv7_kl_acc_fwd_bwd_bf16", logits, rows, V, ld, logits, dlogits, lab, ignore_index, float(smoothing), scale, loss_rows,
+              correct)
     KL_ACC_HITS[0] += 1
     return loss_rows, correct
 

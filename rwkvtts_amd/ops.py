@@ -15,8 +15,6 @@ running somewhere else.  PyTorch is plumbing here: it owns the device memory and
 Extension over the reference: fp32 tensors are accepted everywhere bf16 is (routed to the *_f32
 C entry points); that is what the fp32 logit-parity tests use.
 """
-import ctypes
-
 import torch
 
 from . import _lib, fused
@@ -48,12 +46,10 @@ class _timed:
             KERNEL_TIMERS.setdefault(self.name, []).append((self.s, self.e))
 
 
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _stream(t):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+def _call(timer, name, ref, *args):
+    """_lib.call as the launch that KERNEL_TIMERS lists under `timer`."""
+    with _timed(timer, ref):
+        _lib.call(name, ref, *args)
 
 
 def _sfx(ts, what):
@@ -91,20 +87,13 @@ def wkv7_forward_scalar(w, q, k, v, z, a, y, s, sa):
     B, T, H, C = w.shape
     sfx = _sfx([w, q, k, v, z, a, y], "wind_backstepping.forward")
     assert C == HEAD_SIZE and s.dtype == torch.float32 and sa.dtype == torch.float32
-    with torch.cuda.device_of(w), _timed("wkv7_fwd", w):
-        rc = getattr(_lib.lib(), "rwkv7_wkv_fwd_" + sfx)(B, T, H, _p(w), _p(q), _p(k), _p(v), _p(z), _p(a),
-                                                       _p(y), _p(s), _p(sa), _stream(w))
-    _lib.check(rc, "wind_backstepping.forward")
+    _call("wkv7_fwd", "rwkv7_wkv_fwd_" + sfx, w, B, T, H, w, q, k, v, z, a, y, s, sa)
 
 
 def wkv7_backward_scalar(w, q, k, v, z, a, dy, s, sa, dw, dq, dk, dv, dz, da):
     B, T, H, C = w.shape
     sfx = _sfx([w, q, k, v, z, a, dy, dw, dq, dk, dv, dz, da], "wind_backstepping.backward")
-    with torch.cuda.device_of(w), _timed("wkv7_bwd", w):
-        rc = getattr(_lib.lib(), "rwkv7_wkv_bwd_" + sfx)(B, T, H, _p(w), _p(q), _p(k), _p(v), _p(z), _p(a),
-                                                       _p(dy), _p(s), _p(sa), _p(dw), _p(dq), _p(dk), _p(dv),
-                                                       _p(dz), _p(da), _stream(w))
-    _lib.check(rc, "wind_backstepping.backward")
+    _call("wkv7_bwd", "rwkv7_wkv_bwd_" + sfx, w, B, T, H, w, q, k, v, z, a, dy, s, sa, dw, dq, dk, dv, dz, da)
 
 
 def _check_arena(w, s, what):
@@ -120,9 +109,7 @@ def _wb_forward(w, q, k, v, z, a, y, s, sa):
     _sfx([w, q, k, v, z, a, y], "wind_backstepping.forward")
     assert C == HEAD_SIZE and sa.dtype == torch.float32
     _check_arena(w, s, "wind_backstepping.forward")
-    with torch.cuda.device_of(w), _timed("wkv7c_op_fwd", w):
-        rc = _lib.lib().rwkv7_wkv_fwd_fast_bf16(B, T, H, _p(w), _p(q), _p(k), _p(v), _p(z), _p(a), _p(y), _p(s), _p(sa), _stream(w))
-    _lib.check(rc, "wind_backstepping.forward")
+    _call("wkv7c_op_fwd", "rwkv7_wkv_fwd_fast_bf16", w, B, T, H, w, q, k, v, z, a, y, s, sa)
 
 
 def _wb_backward(w, q, k, v, z, a, dy, s, sa, dw, dq, dk, dv, dz, da):
@@ -131,10 +118,7 @@ def _wb_backward(w, q, k, v, z, a, dy, s, sa, dw, dq, dk, dv, dz, da):
         return wkv7_backward_scalar(w, q, k, v, z, a, dy, s, sa, dw, dq, dk, dv, dz, da)
     _sfx([w, q, k, v, z, a, dy, dw, dq, dk, dv, dz, da], "wind_backstepping.backward")
     _check_arena(w, s, "wind_backstepping.backward")
-    with torch.cuda.device_of(w), _timed("wkv7c_op_bwd", w):
-        rc = _lib.lib().rwkv7_wkv_bwd_fast_bf16(B, T, H, _p(w), _p(q), _p(k), _p(v), _p(z), _p(a), _p(dy), _p(s), _p(sa),
-                                                _p(dw), _p(dq), _p(dk), _p(dv), _p(dz), _p(da), _stream(w))
-    _lib.check(rc, "wind_backstepping.backward")
+    _call("wkv7c_op_bwd", "rwkv7_wkv_bwd_fast_bf16", w, B, T, H, w, q, k, v, z, a, dy, s, sa, dw, dq, dk, dv, dz, da)
 
 
 def wkv7_backward_split(w, q, k, v, z, a, dy, s, sa, wide=None):
@@ -147,15 +131,12 @@ def wkv7_backward_split(w, q, k, v, z, a, dy, s, sa, wide=None):
     sfx = _sfx([w, q, k, v, z, a, dy], "wkv7_backward_split")
     dw2, dq2, dk2, dz2, da2 = [torch.empty((2,) + tuple(w.shape), dtype=w.dtype, device=w.device) for _ in range(5)]
     dv = torch.empty_like(v)
-    pair = lambda t: (ctypes.c_void_p * 2)(t[0].data_ptr(), t[1].data_ptr())
-    with torch.cuda.device_of(w), _timed("wkv7_bwd", w):
-        args = (B, T, H, _p(w), _p(q), _p(k), _p(v), _p(z), _p(a), _p(dy), _p(s), _p(sa), pair(dw2), pair(dq2), pair(dk2),
-                _p(dv), pair(dz2), pair(da2))
-        if wide is None:
-            rc = getattr(_lib.lib(), "rwkv7_wkv_bwd_split_" + sfx)(*args, _stream(w))
-        else:
-            rc = getattr(_lib.lib(), "rwkv7_wkv_bwd_split_variant_" + sfx)(*args, int(wide), _stream(w))
-    _lib.check(rc, "wkv7_backward_split")
+    pair = _lib.ptr_array   # a [2, ...] tensor as the two device pointers the entry takes
+    args = (B, T, H, w, q, k, v, z, a, dy, s, sa, pair(dw2), pair(dq2), pair(dk2), dv, pair(dz2), pair(da2))
+    if wide is None:
+        _call("wkv7_bwd", "rwkv7_wkv_bwd_split_" + sfx, w, *args)
+    else:
+        _call("wkv7_bwd", "rwkv7_wkv_bwd_split_variant_" + sfx, w, *args, int(wide))
     return dw2, dq2, dk2, dv, dz2, da2
 
 
@@ -163,10 +144,7 @@ def _state_forward(B, T, C, H, state, r, w, k, v, a, b, y):
     sfx = _sfx([r, w, k, v, a, b, y], "rwkv7_state_fwd.forward")
     if state.dtype != torch.float32 or not state.is_contiguous():
         raise TypeError("rwkv7_state_fwd.forward: state must be contiguous float32 [B,H,64,64]")
-    with torch.cuda.device_of(r):
-        rc = getattr(_lib.lib(), "rwkv7_wkv_state_fwd_" + sfx)(int(B), int(T), int(C), int(H), _p(state), _p(r),
-                                                             _p(w), _p(k), _p(v), _p(a), _p(b), _p(y), _stream(r))
-    _lib.check(rc, "rwkv7_state_fwd.forward")
+    _lib.call("rwkv7_wkv_state_fwd_" + sfx, r, int(B), int(T), int(C), int(H), state, r, w, k, v, a, b, y)
 
 
 def _wkv7s_forward(B, T, C, H, state, r, w, k, v, a, b, y):
@@ -250,10 +228,7 @@ def wkv7_forward_nograd(q, w, k, v, a, b):
     if T % CHUNK_LEN != 0:
         raise ValueError("T must be a multiple of 16; use the state-carrying op for ragged lengths")
     y = torch.empty_like(v)
-    with torch.cuda.device_of(w):
-        rc = getattr(_lib.lib(), "rwkv7_wkv_fwd_" + sfx)(B, T, H, _p(w), _p(q), _p(k), _p(v), _p(a), _p(b),
-                                                       _p(y), None, None, _stream(w))
-    _lib.check(rc, "wkv7_forward_nograd")
+    _lib.call("rwkv7_wkv_fwd_" + sfx, w, B, T, H, w, q, k, v, a, b, y, None, None)
     return y
 
 
@@ -306,9 +281,7 @@ def wkv7_chunk_prep(w, a, b):
     B, T, H, C = w.shape
     sfx = _sfx([w, a, b], "wkv7_chunk_prep")
     tinv = torch.empty(B, H, T // CHUNK_T, CHUNK_T, CHUNK_T, dtype=torch.float32, device=w.device)
-    with torch.cuda.device_of(w), _timed("wkv7c_prep", w):
-        rc = getattr(_lib.lib(), "rwkv7_wkv_chunk_prep_" + sfx)(B, T, H, _p(w), _p(a), _p(b), _p(tinv), _stream(w))
-    _lib.check(rc, "wkv7_chunk_prep")
+    _call("wkv7c_prep", "rwkv7_wkv_chunk_prep_" + sfx, w, B, T, H, w, a, b, tinv)
     return tinv
 
 
@@ -333,13 +306,11 @@ def _chunk_fwd(w, q, k, v, a, b, save, seq_off, nseq, h0=None):
     sa = torch.empty(B, T, H, C, dtype=torch.float32, device=w.device) if save else None
     hs = torch.empty(B, H, T // CHUNK_T, Q15_REC, dtype=torch.int16, device=w.device) if save else None
     hT = None if h0 is None else torch.empty(nseq if seq_off is not None else B, H, C, C, dtype=torch.float32, device=w.device)
-    args = (B, T, H, _p(w), _p(q), _p(k), _p(v), _p(a), _p(b), _p(tinv), _p(y), _p(sa), _p(hs), _p(seq_off), nseq)
-    with torch.cuda.device_of(w), _timed("wkv7c_fwd" if h0 is None else "wkv7c_fwd_state", w):
-        if h0 is None:
-            rc = getattr(_lib.lib(), "rwkv7_wkv_chunk_fwd_seq_" + sfx)(*args, _stream(w))
-        else:
-            rc = _lib.lib().rwkv7_wkv_chunk_fwd_state_seq_bf16(*args, _p(h0), _p(hT), _stream(w))
-    _lib.check(rc, "wkv7_chunk_forward")
+    args = (B, T, H, w, q, k, v, a, b, tinv, y, sa, hs, seq_off, nseq)
+    if h0 is None:
+        _call("wkv7c_fwd", "rwkv7_wkv_chunk_fwd_seq_" + sfx, w, *args)
+    else:
+        _call("wkv7c_fwd_state", "rwkv7_wkv_chunk_fwd_state_seq_bf16", w, *args, h0, hT)
     return y, tinv, sa, hs, hT
 
 
@@ -365,13 +336,11 @@ def _bseq(w, q, a, b, dy, tinv, seq_off, nseq, want_z, state=None):
     # chunk).  The carried-state layouts give every chunk of the row to a sequence.
     zeroed = seq_off is not None and state is None
     z = (torch.zeros if zeroed else torch.empty)(B, T, H, C, dtype=torch.float32, device=w.device) if want_z else None
-    args = (B, T, H, _p(w), _p(q), _p(a), _p(b), _p(dy), _p(tinv), _p(e_vk), _p(z), _p(seq_off), nseq)
-    with torch.cuda.device_of(w), _timed("wkv7c_bseq" if state is None else "wkv7c_bseq_state", w):
-        if state is None:
-            rc = _lib.lib().rwkv7_wkv_chunk_bseq_bf16(*args, _stream(w))
-        else:
-            rc = _lib.lib().rwkv7_wkv_chunk_bseq_state_seq_bf16(*args, *[_p(t) for t in state], _stream(w))
-    _lib.check(rc, "wkv7_chunk_bseq")
+    args = (B, T, H, w, q, a, b, dy, tinv, e_vk, z, seq_off, nseq)
+    if state is None:
+        _call("wkv7c_bseq", "rwkv7_wkv_chunk_bseq_bf16", w, *args)
+    else:
+        _call("wkv7c_bseq_state", "rwkv7_wkv_chunk_bseq_state_seq_bf16", w, *args, *state)
     return e_vk, z
 
 
@@ -390,10 +359,7 @@ def _chunk_bwd(w, q, k, v, a, b, dy, hs, sa, tinv, seq_off, nseq, state=None):
     B, T, H, C = w.shape
     e_vk, z = _bseq(w, q, a, b, dy, tinv, seq_off, nseq, True, state)
     grads = [torch.empty_like(w) for _ in range(6)]
-    with torch.cuda.device_of(w), _timed("wkv7c_bwd_out", w):
-        rc = _lib.lib().rwkv7_wkv_chunk_bwd_out_z_bf16(B, T, H, _p(w), _p(q), _p(k), _p(v), _p(a), _p(b), _p(dy), _p(hs), _p(sa),
-                                                       _p(z), _p(e_vk), *[_p(g) for g in grads], _stream(w))
-    _lib.check(rc, "wkv7_chunk_bwd_out")
+    _call("wkv7c_bwd_out", "rwkv7_wkv_chunk_bwd_out_z_bf16", w, B, T, H, w, q, k, v, a, b, dy, hs, sa, z, e_vk, *grads)
     return grads
 
 
@@ -411,8 +377,7 @@ def debug_mma32(X, Y):
     """GPU unit-test hook: D = X Y^T for X,Y fp32 [32,64] through the bf16-split MFMA primitive; returns (D, DT)."""
     D = torch.empty(32, 32, device=X.device)
     DT = torch.empty(32, 32, device=X.device)
-    rc = _lib.lib().rwkv7_debug_mma32(_p(X.contiguous()), _p(Y.contiguous()), _p(D), _p(DT), _stream(X))
-    _lib.check(rc, "debug_mma32")
+    _lib.call("rwkv7_debug_mma32", X, X.contiguous(), Y.contiguous(), D, DT)
     return D, DT
 
 

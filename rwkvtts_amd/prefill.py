@@ -17,7 +17,6 @@ Nothing on the run() path reads the device back (.tolist() / .item() / .cpu() / 
 """
 from __future__ import annotations
 
-import ctypes
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple
 
@@ -128,10 +127,6 @@ def plan(lens: Sequence[int], rows: Sequence[int], fresh: bool, n_rows: int, max
     return out
 
 
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
 def add_ln_mix_rows(x, branch, norm, mask, params, prev_src, last_dst, x_prev_rd, x_prev):
     """rwkv7_add_ln_mix_rows_fwd_bf16 on the current stream: x, branch [T, D] bf16 (branch may be None), mask [T] bf16 or None,
     params [nmix, D], prev_src / last_dst int32 [T] on the device, x_prev (and x_prev_rd, the snapshot carried predecessors are read
@@ -140,12 +135,8 @@ def add_ln_mix_rows(x, branch, norm, mask, params, prev_src, last_dst, x_prev_rd
     nmix = params.shape[0]
     out = torch.empty(nmix, T, D, dtype=x.dtype, device=x.device)
     x1 = torch.empty_like(x) if branch is not None else None
-    with torch.cuda.device_of(x):
-        rc = _lib.lib().rwkv7_add_ln_mix_rows_fwd_bf16(
-            T, D, nmix, _p(x), _p(branch), _p(norm.weight), _p(norm.bias), ctypes.c_float(norm.eps), _p(mask), _p(params), _p(prev_src),
-            _p(last_dst), _p(x_prev_rd), _p(x_prev), _p(x1), _p(out), max(1, min(-(-T // _RUN), _BLOCKS)), _RUN,
-            ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-    _lib.check(rc, "rwkv7_add_ln_mix_rows_fwd_bf16")
+    _lib.call("rwkv7_add_ln_mix_rows_fwd_bf16", x, T, D, nmix, x, branch, norm.weight, norm.bias, norm.eps, mask, params, prev_src,
+              last_dst, x_prev_rd, x_prev, x1, out, max(1, min(-(-T // _RUN), _BLOCKS)), _RUN)
     return (x if branch is None else x1), out
 
 
@@ -158,11 +149,7 @@ def wkv_state_rows(state, r, w, k, v, a, b, seq_off, state_row):
     w4, a4, b4 = (t.view(1, T, H, 64) for t in (w, a, b))
     tinv = ops.wkv7_chunk_prep(w4, a4, b4)
     y = torch.empty_like(v)
-    with torch.cuda.device_of(r):
-        rc = _lib.lib().rwkv7_wkv_chunk_fwd_state_rows_bf16(
-            T, H, _p(w), _p(r), _p(k), _p(v), _p(a), _p(b), _p(tinv), _p(y), _p(seq_off), state_row.numel(), _p(state), _p(state_row),
-            ctypes.c_void_p(torch.cuda.current_stream(r.device).cuda_stream))
-    _lib.check(rc, "rwkv7_wkv_chunk_fwd_state_rows_bf16")
+    _lib.call("rwkv7_wkv_chunk_fwd_state_rows_bf16", r, T, H, w, r, k, v, a, b, tinv, y, seq_off, state_row.numel(), state, state_row)
     return y
 
 
@@ -201,10 +188,7 @@ def cache_rows_commit(src_tbl, dst_tbl, src_row, dst_row, n: int, layers: int, D
     for t in (src_row, dst_row):
         assert t.dtype == torch.int32 and t.is_contiguous() and t.is_cuda and t.numel() >= n
     assert src_tbl.dtype == torch.int64 and dst_tbl.dtype == torch.int64 and src_tbl.numel() == dst_tbl.numel() == 3 * layers
-    with torch.cuda.device_of(dst_tbl):
-        rc = _lib.lib().rwkv7_cache_rows_commit_bf16(int(layers), int(n), _p(src_tbl), _p(dst_tbl), _p(src_row), _p(dst_row), int(D), int(H),
-                                                     ctypes.c_void_p(torch.cuda.current_stream(dst_tbl.device).cuda_stream))
-    _lib.check(rc, "rwkv7_cache_rows_commit_bf16")
+    _lib.call("rwkv7_cache_rows_commit_bf16", dst_tbl, int(layers), int(n), src_tbl, dst_tbl, src_row, dst_row, int(D), int(H))
 
 
 class _Bucket:

@@ -129,20 +129,15 @@ class RowSampler:
         rows = logits.shape[0]
         if out is None:
             out = torch.empty(rows, self.nseg, dtype=torch.int64, device=logits.device)
-        p = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)
-        common = (p(self.seg_off), p(self.seg_len), p(self.allow_lo), p(self.allow_hi), p(self.suppress),
+        common = (logits, logits.stride(0), self.seg_off, self.seg_len, self.allow_lo, self.allow_hi, self.suppress,
                   0 if self.suppress is None else self.suppress.numel(), self.max_domain, self.do_sample, self.top_k,
-                  ctypes.c_float(self.top_p), ctypes.c_float(self.temperature), ctypes.c_ulonglong(self.seed), p(step), p(out))
-        stream = ctypes.c_void_p(torch.cuda.current_stream(logits.device).cuda_stream)
-        with torch.cuda.device_of(logits):
-            if tail is None and self.min_id < 0:
-                rc = _lib.lib().rwkv7_sample_rows_f32(rows, self.nseg, p(logits), ctypes.c_long(logits.stride(0)), *common, stream)
-            else:
-                assert self.nseg == 1
-                rc = _lib.lib().rwkv7_sample_rows_tail_f32(rows, p(logits), ctypes.c_long(logits.stride(0)), *common,
-                                                           ctypes.byref(tail) if tail is not None else None, self.min_id,
-                                                           ctypes.c_long(self.min_until), stream)
-        _lib.check(rc, "rwkv7_sample_rows_f32")
+                  self.top_p, self.temperature, self.seed, step, out)
+        if tail is None and self.min_id < 0:
+            _lib.call("rwkv7_sample_rows_f32", logits, rows, self.nseg, *common)
+        else:
+            assert self.nseg == 1
+            _lib.call("rwkv7_sample_rows_tail_f32", logits, rows, *common, ctypes.byref(tail) if tail is not None else None,
+                      self.min_id, self.min_until)
         return out
 
 
@@ -155,12 +150,8 @@ def ras_step(logits: torch.Tensor, tok: torch.Tensor, recent: torch.Tensor, ptr:
         assert t.dtype == torch.int64 and t.is_cuda and t.is_contiguous()
     assert recent.numel() == win_size
     seed = int(fresh_seed() if seed is None else seed) & ((1 << 64) - 1)   # (callers in a loop pass one seed per generation)
-    p = lambda t: ctypes.c_void_p(t.data_ptr())
-    with torch.cuda.device_of(logits):
-        rc = _lib.lib().rwkv7_ras_step_f32(logits.numel(), p(logits), p(tok), p(recent), p(ptr), p(step_i), ctypes.c_long(int(n_ignore)),
-                                           int(eos), ctypes.c_float(top_p), int(top_k), int(win_size), ctypes.c_float(tau_r),
-                                           ctypes.c_ulonglong(seed), ctypes.c_void_p(torch.cuda.current_stream(logits.device).cuda_stream))
-    _lib.check(rc, "rwkv7_ras_step_f32")
+    _lib.call("rwkv7_ras_step_f32", logits, logits.numel(), logits, tok, recent, ptr, step_i, int(n_ignore), int(eos), top_p, int(top_k),
+              int(win_size), tau_r, seed)
 
 
 def xy_frame_step(nt, out, row, pos, unfinished, needs, all_done, n_rows, text_shift, speech_vocab, pad, eos0, total, eos_list,
@@ -171,14 +162,9 @@ def xy_frame_step(nt, out, row, pos, unfinished, needs, all_done, n_rows, text_s
     for t in (nt, out, row, pos, unfinished, needs, n_rows):
         assert t.dtype == torch.int64 and t.is_cuda and t.is_contiguous()
     assert all_done.dtype == torch.bool and out.shape[0] == B and out.shape[2] == C
-    p = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)
-    L = ctypes.c_long
-    with torch.cuda.device_of(nt):
-        rc = _lib.lib().rwkv7_xy_frame_step(B, C, out.shape[1], L(text_shift), L(speech_vocab), L(pad), L(-1 if eos0 is None else eos0),
-                                            L(-1 if total is None else total), p(eos_list), 0 if eos_list is None else eos_list.numel(),
-                                            int(bool(reference_termination)), p(nt), p(out), p(row), p(pos), p(unfinished), p(needs),
-                                            p(all_done), p(n_rows), ctypes.c_void_p(torch.cuda.current_stream(nt.device).cuda_stream))
-    _lib.check(rc, "rwkv7_xy_frame_step")
+    _lib.call("rwkv7_xy_frame_step", nt, B, C, out.shape[1], text_shift, speech_vocab, pad, -1 if eos0 is None else eos0,
+              -1 if total is None else total, eos_list, 0 if eos_list is None else eos_list.numel(), int(bool(reference_termination)),
+              nt, out, row, pos, unfinished, needs, all_done, n_rows)
 
 
 class XYEmbed:
@@ -193,14 +179,10 @@ class XYEmbed:
     def __init__(self, tables, B):
         self.tables = [t.detach() for t in tables]
         self.C, self.D = len(tables), tables[0].shape[1]
-        self.ptrs = (ctypes.c_void_p * self.C)(*[t.data_ptr() for t in self.tables])
+        self.ptrs = _lib.ptr_array(self.tables)
         self.x = torch.empty(B, self.D, dtype=torch.bfloat16, device=tables[0].device)
 
     def __call__(self, row: torch.Tensor) -> torch.Tensor:
         assert row.dtype == torch.int64 and row.is_contiguous() and row.shape == (self.x.shape[0], self.C)
-        with torch.cuda.device_of(row):
-            rc = _lib.lib().rwkv7_xy_embed_bf16(row.shape[0], self.C, self.D, self.ptrs, ctypes.c_void_p(row.data_ptr()),
-                                                ctypes.c_void_p(self.x.data_ptr()),
-                                                ctypes.c_void_p(torch.cuda.current_stream(row.device).cuda_stream))
-        _lib.check(rc, "rwkv7_xy_embed_bf16")
+        _lib.call("rwkv7_xy_embed_bf16", row, row.shape[0], self.C, self.D, self.ptrs, row, self.x)
         return self.x

@@ -16,7 +16,6 @@ MI355X-first choices:
 """
 from __future__ import annotations
 
-import ctypes
 import math
 import os
 from typing import List, Optional
@@ -24,6 +23,7 @@ from typing import List, Optional
 import torch
 import torch.distributed as dist
 
+from . import _lib
 
 FLUSH_EVERY = int(os.environ.get("RWKV7_FLUSH_EVERY", "48"))   # adopted gradients per in-backward flush (0: one flush at the end)
 
@@ -503,10 +503,8 @@ class DataParallelTrainer:
             # the sum of squares stays on the device: fp32 + per-tile partials for the HIP pass, float64 in the torch fallback
             self._sumsq = torch.zeros(1, dtype=torch.float32 if self.hip_adamw else torch.float64, device=dev)
             if self.hip_adamw:
-                from . import _lib
-                nbytes = _lib.lib().rwkv7_grad_sumsq_workspace_bytes
-                nbytes.restype, nbytes.argtypes = ctypes.c_long, [ctypes.c_long]
-                self._sumsq_partials = torch.empty(nbytes(self.flat.numel) // 4, dtype=torch.float32, device=dev)
+                nbytes = _lib.lib().rwkv7_grad_sumsq_workspace_bytes(self.flat.numel)
+                self._sumsq_partials = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
         # micro-batch accumulation (accumulate()): fp32 sum of the gradients of the micro-batches before the one step() runs,
         # allocated on first use; their count; the running max of their NaN flags
         self._acc32 = None
@@ -577,13 +575,7 @@ class DataParallelTrainer:
         if hi <= lo:
             self._sumsq.zero_()
         elif self.hip_adamw:
-            from . import _lib
-            P = lambda t: ctypes.c_void_p(t.data_ptr())
-            with torch.cuda.device_of(self.master):
-                rc = _lib.lib().rwkv7_grad_sumsq_bf16(
-                    ctypes.c_long(hi - lo), P(self.flat.flat_grad[lo:hi]), P(self._sumsq_partials), P(self._sumsq), 0,
-                    ctypes.c_void_p(torch.cuda.current_stream(self.master.device).cuda_stream))
-            _lib.check(rc, "grad_sumsq")
+            _lib.call("rwkv7_grad_sumsq_bf16", self.master, hi - lo, self.flat.flat_grad[lo:hi], self._sumsq_partials, self._sumsq, 0)
         else:
             self._sumsq.copy_(self.flat.flat_grad[lo:hi].double().pow(2).sum().reshape(1))
 
@@ -593,17 +585,10 @@ class DataParallelTrainer:
         if hi <= lo:
             return
         if self.hip_adamw:
-            from . import _lib
-            P = lambda t: ctypes.c_void_p(t.data_ptr())
-            f = ctypes.c_float
-            with torch.cuda.device_of(self.master):
-                rc = _lib.lib().rwkv7_adamw_groups_clip_bf16(
-                    ctypes.c_long(hi - lo), P(self.master[lo:hi]), P(self.flat.flat_grad[lo:hi]), P(self.exp_avg[lo:hi]),
-                    P(self.exp_avg_sq[lo:hi]), P(self.flat.flat_param[lo:hi]), P(self.slab_group[lo // 128:hi // 128]), P(self.group_tab),
-                    len(self.group_defs), P(self.nan_flag), P(self._sumsq), f(self.max_grad_norm),
-                    f(lr), f(self.betas[0]), f(self.betas[1]), f(self.eps), self.step_idx + 1,
-                    ctypes.c_void_p(torch.cuda.current_stream(self.master.device).cuda_stream))
-            _lib.check(rc, "adamw_clip")
+            _lib.call("rwkv7_adamw_groups_clip_bf16", self.master,
+                      hi - lo, self.master[lo:hi], self.flat.flat_grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi],
+                      self.flat.flat_param[lo:hi], self.slab_group[lo // 128:hi // 128], self.group_tab, len(self.group_defs),
+                      self.nan_flag, self._sumsq, self.max_grad_norm, lr, self.betas[0], self.betas[1], self.eps, self.step_idx + 1)
         else:
             ss = self._sumsq[0]
             coef = torch.clamp(self.max_grad_norm / (ss.sqrt() + 1e-6), max=1.0).to(self.master.dtype)
@@ -616,12 +601,7 @@ class DataParallelTrainer:
             return
         g = self.flat.flat_grad[lo:hi]
         if self.hip_adamw:
-            from . import _lib
-            with torch.cuda.device_of(self.master):
-                rc = _lib.lib().rwkv7_grad_fold_bf16(
-                    ctypes.c_long(hi - lo), ctypes.c_void_p(self._acc32[lo:hi].data_ptr()), ctypes.c_void_p(g.data_ptr()),
-                    ctypes.c_float(inv_count), ctypes.c_void_p(torch.cuda.current_stream(self.master.device).cuda_stream))
-            _lib.check(rc, "grad_fold")
+            _lib.call("rwkv7_grad_fold_bf16", self.master, hi - lo, self._acc32[lo:hi], g, inv_count)
         else:
             g.copy_(((self._acc32[lo:hi] + g.float()) * inv_count).to(g.dtype))
 
@@ -652,13 +632,7 @@ class DataParallelTrainer:
         finally:
             self.flat.on_ready = on_ready
         if self.hip_adamw:
-            from . import _lib
-            with torch.cuda.device_of(self.master):
-                rc = _lib.lib().rwkv7_grad_accum_bf16(
-                    ctypes.c_long(self.flat.numel), ctypes.c_void_p(self._acc32.data_ptr()),
-                    ctypes.c_void_p(self.flat.flat_grad.data_ptr()), int(first),
-                    ctypes.c_void_p(torch.cuda.current_stream(self.master.device).cuda_stream))
-            _lib.check(rc, "grad_accum")
+            _lib.call("rwkv7_grad_accum_bf16", self.master, self.flat.numel, self._acc32, self.flat.flat_grad, int(first))
         elif first:
             self._acc32.copy_(self.flat.flat_grad)
         else:
@@ -704,18 +678,10 @@ class DataParallelTrainer:
             if hi <= lo:
                 return
             if self.hip_adamw:
-                import ctypes
-                from . import _lib
-                P = lambda t: ctypes.c_void_p(t.data_ptr())
-                f = ctypes.c_float
-                with torch.cuda.device_of(self.master):
-                    rc = _lib.lib().rwkv7_adamw_groups_bf16(
-                        ctypes.c_long(hi - lo), P(self.master[lo:hi]), P(self.flat.flat_grad[lo:hi]), P(self.exp_avg[lo:hi]),
-                        P(self.exp_avg_sq[lo:hi]), P(self.flat.flat_param[lo:hi]), P(self.slab_group[lo // 128:hi // 128]), P(self.group_tab),
-                        len(self.group_defs), P(self.nan_flag),
-                        f(lr), f(self.betas[0]), f(self.betas[1]), f(self.eps), self.step_idx + 1,
-                        ctypes.c_void_p(torch.cuda.current_stream(self.master.device).cuda_stream))
-                _lib.check(rc, "adamw")
+                _lib.call("rwkv7_adamw_groups_bf16", self.master,
+                          hi - lo, self.master[lo:hi], self.flat.flat_grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi],
+                          self.flat.flat_param[lo:hi], self.slab_group[lo // 128:hi // 128], self.group_tab, len(self.group_defs),
+                          self.nan_flag, lr, self.betas[0], self.betas[1], self.eps, self.step_idx + 1)
             else:
                 self._torch_adamw(lr, self.nan_flag, lo, hi)
 

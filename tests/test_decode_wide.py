@@ -16,7 +16,6 @@ def _dims(B=64, D=128, H=None, L=2, F=None, V=77, ranks=(32, 32, 32, 32)):
 
 
 def _bytes(lib, dm):
-    lib.rwkv7_decode_wide_workspace_bytes.restype = ctypes.c_size_t
     return lib.rwkv7_decode_wide_workspace_bytes(ctypes.byref(dm))
 
 
@@ -62,7 +61,6 @@ def test_wide_workspace_grows_by_row_tile(hip_lib, D, ranks, V):
     assert size[65] == size[96]
     assert size[97] == size[127] == size[128]
     assert size[64] < size[96] < size[128]
-    hip_lib.rwkv7_decode_workspace_bytes.restype = ctypes.c_size_t
     narrow = hip_lib.rwkv7_decode_workspace_bytes(ctypes.byref(_dims(B=32, D=D, V=V, ranks=ranks)))
     assert 0 < narrow < size[64]
     # every plane doubles from one tile to two; only the 256-byte barrier block does not
@@ -73,7 +71,6 @@ def test_wide_workspace_is_zero_outside_its_range(hip_lib):
     for dm in (_dims(B=1), _dims(B=32), _dims(B=129), _dims(B=0), _dims(D=96, H=1), _dims(ranks=(32, 32, 16, 32)), _dims(F=100)):
         assert _bytes(hip_lib, dm) == 0
     assert hip_lib.rwkv7_decode_wide_workspace_bytes(None) == 0
-    hip_lib.rwkv7_decode_workspace_bytes.restype = ctypes.c_size_t
     assert hip_lib.rwkv7_decode_workspace_bytes(ctypes.byref(_dims(B=33))) == 0
 
 

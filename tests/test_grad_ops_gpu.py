@@ -15,10 +15,7 @@ f = ctypes.c_float
 
 def _lib():
     from rwkvtts_amd import _lib as L
-    lib = L.lib()
-    lib.rwkv7_grad_sumsq_workspace_bytes.restype = ctypes.c_long
-    lib.rwkv7_grad_sumsq_workspace_bytes.argtypes = [ctypes.c_long]
-    return lib
+    return L.lib()
 
 
 def _grad(n, seed, sign_seed=None):

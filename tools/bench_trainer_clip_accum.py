@@ -83,7 +83,6 @@ def main():
     f = ctypes.c_float
     n = tr.flat.numel
     st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    lib.rwkv7_grad_sumsq_workspace_bytes.restype, lib.rwkv7_grad_sumsq_workspace_bytes.argtypes = ctypes.c_long, [ctypes.c_long]
     ws = torch.empty(lib.rwkv7_grad_sumsq_workspace_bytes(n) // 4, dtype=torch.float32, device=dev)
     ss = torch.zeros(1, device=dev)
     acc = torch.zeros(n, dtype=torch.float32, device=dev)
