@@ -513,6 +513,21 @@ int rwkv7_grad_sumsq_bf16(long n, const void *g16, float *partials, float *out, 
 int rwkv7_grad_accum_bf16(long n, float *acc32, const void *g16, int first, rwkv7_stream_t stream);
 int rwkv7_grad_fold_bf16(long n, const float *acc32, void *g16, float inv_count, rwkv7_stream_t stream);
 
+/* ---- position-sensitive 64-bit digest of a device buffer of n_words 32-bit words whose first word has the GLOBAL index
+ *      first_index (trainer checkpoints: the buffers in memory after a load are the buffers that were saved; replica check):
+ *          x_i  = (uint64)w[i] + (first_index + i + 1) * 0x9E3779B97F4A7C15
+ *          x_i ^= x_i >> 30;  x_i *= 0xBF58476D1CE4E5B9;  x_i ^= x_i >> 27;  x_i *= 0x94D049BB133111EB;  x_i ^= x_i >> 31
+ *          out[0] = (accumulate ? out[0] : 0) + sum_i x_i                               (all of it mod 2^64)
+ *      Exact integer arithmetic: the same 64 bits on every call and in a numpy uint64 restatement.  Additive over disjoint index
+ *      ranges: the digest of a buffer is the wrapping sum of the digests of its slabs, each with its own first_index.  The digest
+ *      of all-zero words is not zero, and exchanging two unequal words changes it.  Two launches, no atomics: one workgroup per
+ *      FIXED tile of 8192 words (16-byte loads, one uint64 partial per tile into `partials`, the workspace query's byte count),
+ *      then one workgroup that adds the partials.  buf is only read.  n_words % 4 == 0, buf 16-byte aligned (RWKV7_ESHAPE
+ *      otherwise, nothing launched); n_words == 0 is allowed (buf and partials may then be NULL).  64-bit indices throughout. ---- */
+long rwkv7_buf_digest_workspace_bytes(long n_words);
+int rwkv7_buf_digest_u32(long n_words, long first_index, const void *buf, unsigned long long *partials, unsigned long long *out,
+                         int accumulate, rwkv7_stream_t stream);
+
 /* ---- last step of a split weight gradient (the dW of nn.Linear under autograd, e.g. rwkv_s2s_single_ffn.py:171-174,195,
  *      228-229, reduced over B*T in S row slabs with fp32 partials): out[n] (bf16) = (accumulate ? out[n] : 0) +
  *      sum_s parts[s][n].  out may be the parameter's slice of the flat gradient buffer.  n % 4 == 0. ---- */

@@ -16,14 +16,17 @@ MI355X-first choices:
 """
 from __future__ import annotations
 
+import json
 import math
 import os
+import shutil
+import warnings
 from typing import List, Optional
 
 import torch
 import torch.distributed as dist
 
-from . import _lib
+from . import _lib, digest as _digest
 
 FLUSH_EVERY = int(os.environ.get("RWKV7_FLUSH_EVERY", "48"))   # adopted gradients per in-backward flush (0: one flush at the end)
 
@@ -383,6 +386,50 @@ def cosine_warmup_decay(step, total_steps, warmup_steps, lr, lr_final):
 
 SCHEDULES = {"linear": linear_warmup_decay, "cosine": cosine_warmup_decay}
 
+CHECKPOINT_FORMAT = 1
+DIGEST_NAMES = ("master", "exp_avg", "exp_avg_sq", "param")
+
+
+def _write_synced(path, data):
+    """data (bytes, or a uint8 numpy array) to `path`, flushed to the disk before the call returns."""
+    with open(path, "wb") as f:
+        if isinstance(data, (bytes, bytearray)):
+            f.write(data)
+        else:
+            data.tofile(f)
+        f.flush()
+        os.fsync(f.fileno())
+
+
+def _sync_dir(path):
+    fd = os.open(path, os.O_RDONLY)
+    try:
+        os.fsync(fd)
+    finally:
+        os.close(fd)
+
+
+def _read_json(path):
+    with open(path) as f:
+        return json.load(f)
+
+
+def complete_checkpoints(dir):
+    """[(step_idx, tag)] of the complete checkpoints under `dir`, oldest first.  A `<tag>.tmp` directory (a save that did not
+    finish) is never one."""
+    out = []
+    for tag in os.listdir(dir) if os.path.isdir(dir) else ():
+        meta = os.path.join(dir, tag, "meta.json")
+        if tag.endswith(".tmp") or not os.path.isfile(meta):
+            continue
+        try:
+            m = _read_json(meta)
+        except ValueError:
+            continue
+        if m.get("format") == CHECKPOINT_FORMAT:
+            out.append((int(m["step_idx"]), os.path.getmtime(meta), tag))
+    return [(s_, t) for s_, _, t in sorted(out)]
+
 
 def reference_param_groups(model: torch.nn.Module, weight_decay: float):
     """The parameter groups of configure_optimizer (train_cosy_rwkv7speech_multiple_dataset.py:162-190), one entry per
@@ -712,3 +759,237 @@ class DataParallelTrainer:
             m._mix_key = None
         self.step_idx += 1
         return loss.detach()
+
+    # ---- state digest and checkpoints (DESIGN.md section 6.2) ------------------------------------------------------------------
+    def _own_range(self):
+        """[lo, hi) of the flat buffers this rank is the authority on: its slab in shard mode, everything otherwise."""
+        return self.reducer.slab(self.reducer.rank) if self.shard_optimizer else (0, self.flat.numel)
+
+    def _range_digests(self, ranges):
+        """[[master, exp_avg, exp_avg_sq, param digests as Python ints] for [lo, hi) in ranges], with global word indices (an
+        fp32 element is a word, two bf16 elements are one).  HIP path: rwkv7_buf_digest_u32 per buffer and range, then ONE read-back;
+        otherwise the numpy restatement.  With an fp32 model master IS flat_param: the two values are the same."""
+        bufs = (self.master, self.exp_avg, self.exp_avg_sq, self.flat.flat_param)
+        per_word = [4 // b.element_size() for b in bufs]
+        if not self.hip_adamw:
+            return [[_digest.fallback_digest(b[lo:hi], lo // k) for b, k in zip(bufs, per_word)] for lo, hi in ranges]
+        if getattr(self, "_digest_ws", None) is None:
+            self._digest_ws = _digest.workspace(self.flat.numel, self.master.device)
+        out = torch.zeros(max(1, 4 * len(ranges)), dtype=torch.int64, device=self.master.device)
+        for r, (lo, hi) in enumerate(ranges):
+            for j, (b, k) in enumerate(zip(bufs, per_word)):
+                _digest.launch(b[lo:hi], lo // k, out[4 * r + j:4 * r + j + 1], self._digest_ws)
+        vals = [v & _digest.MASK64 for v in out.tolist()]
+        return [vals[4 * r:4 * r + 4] for r in range(len(ranges))]
+
+    def _combine_digests(self, own):
+        """The four whole-buffer digests from every rank's `own` ones.  Replicated mode: they must be equal on all ranks (MIN and MAX
+        of the 32-bit halves agree), RuntimeError naming the first buffer that differs otherwise.  Shard mode: the wrapping sum of
+        the slab digests (the digest is additive over disjoint index ranges)."""
+        r_ = self.reducer
+        dev = self.master.device if r_.backend == "nccl" else torch.device("cpu")
+        if self.shard_optimizer:
+            mine = torch.tensor([v - (1 << 64) if v >> 63 else v for v in own], dtype=torch.int64, device=dev)
+            everyone = [torch.zeros_like(mine) for _ in range(r_.world)]
+            dist.all_gather(everyone, mine, group=r_.group)
+            return [sum(int(t[j]) for t in everyone) & _digest.MASK64 for j in range(4)]
+        halves = torch.tensor([h for v in own for h in (v & 0xffffffff, v >> 32)], dtype=torch.int64, device=dev)
+        lo_, hi_ = halves.clone(), halves.clone()
+        dist.all_reduce(lo_, op=dist.ReduceOp.MIN, group=r_.group)
+        dist.all_reduce(hi_, op=dist.ReduceOp.MAX, group=r_.group)
+        differ = (lo_ != hi_).reshape(4, 2).any(dim=1).tolist()
+        if any(differ):
+            name = DIGEST_NAMES[differ.index(True)]
+            raise RuntimeError(f"replicas differ: the digest of `{name}` is not the same on all {r_.world} ranks (step {self.step_idx})")
+        return list(own)
+
+    def digest(self, all_ranks=False):
+        """{"master", "exp_avg", "exp_avg_sq", "param"}: 64-bit digests (rwkvtts_amd/digest.py) of this rank's authoritative range of
+        the fp32 masters, the two moments and the model-dtype parameters, with global indices; one host read-back.
+        all_ranks=True (a collective when world > 1): replicated mode checks that every rank holds the same four words and raises
+        RuntimeError naming the buffer if not; shard mode returns the digests of the WHOLE buffers, summed from the slabs."""
+        own = self._range_digests([self._own_range()])[0]
+        if all_ranks and self.world > 1:
+            own = self._combine_digests(own)
+        return dict(zip(DIGEST_NAMES, own))
+
+    def _layout(self):
+        names = {id(p): n for n, p in self.model.named_parameters()}
+        return [dict(name=names.get(id(p), f"<parameter {i}>"), shape=list(p.shape), offset=o, numel=p.numel())
+                for i, (p, o) in enumerate(zip(self.flat.params, self.flat.offsets))]
+
+    def _barrier(self):
+        if self.world > 1:
+            dist.barrier(group=self.reducer.group)
+
+    def save_checkpoint(self, dir, tag=None, extra=None, keep_last=3):
+        """Write the training state to <dir>/<tag>/ (tag: "step_<step_idx>" by default) and return that path; what the reference
+        scripts ask of `model_engine.save_checkpoint(output_dir)` (train_scripts/train_spark_rwkv7speech.py:199-217, 695, 734).
+        A collective when world > 1: every rank calls it with the same arguments, on a directory all ranks can see.
+
+        Written: the fp32 masters and both moments, the model-dtype flat parameters (so that no rounding has to be reproduced),
+        step_idx and last_lr, the layout (names, shapes, offsets), group_defs and the hyper-parameters (for information), one digest
+        per buffer and written range, `extra` (JSON: epoch, batch index, data cursor) and every rank's host and device RNG state.
+        Not written: gradients, the fp32 micro-batch accumulator -- saving inside an accumulation window is a RuntimeError.
+        Replicated mode: rank 0 writes the tensors, after the digests have shown the replicas to be identical; shard mode: every
+        rank writes its own slab (foreign slabs of the masters and moments are stale on a rank).
+        Everything goes to <dir>/<tag>.tmp/, every file is fsynced by its writer; after a barrier rank 0 renames the directory,
+        rewrites <dir>/latest and deletes the oldest complete checkpoints beyond keep_last (None: keep all) and stale .tmp directories.
+        One device synchronisation and device-to-host copies on the calling thread; nothing of step() changes."""
+        if self._acc_count != 0:
+            raise RuntimeError(f"save_checkpoint inside an accumulation window ({self._acc_count} micro-batches pending): "
+                               "checkpoints are taken at step boundaries, the fp32 accumulator is not serialised")
+        extra_json = json.dumps(extra)   # not JSON-serialisable: TypeError before anything is written
+        tag = f"step_{self.step_idx}" if tag is None else str(tag)
+        if not tag or tag.endswith(".tmp") or tag == "latest" or os.path.basename(tag) != tag:
+            raise ValueError(f"bad checkpoint tag {tag!r}")
+        rank, world = self.reducer.rank, self.world
+        tmp, final = os.path.join(dir, tag + ".tmp"), os.path.join(dir, tag)
+        lo, hi = self._own_range()
+        own = self._range_digests([(lo, hi)])[0]
+        whole = self._combine_digests(own) if world > 1 else own   # replicated mode: raises if the replicas have diverged
+        if rank == 0:
+            os.makedirs(dir, exist_ok=True)
+            if os.path.isdir(tmp):
+                shutil.rmtree(tmp)
+            os.makedirs(tmp)
+        self._barrier()
+        hexd = lambda vals: {n: "%016x" % v for n, v in zip(DIGEST_NAMES, vals)}
+        same = self.master is self.flat.flat_param
+        if (rank == 0 or self.shard_optimizer) and hi > lo:
+            stem = f"range_{lo:012d}_{hi:012d}"
+            files = {}
+            for name, buf in zip(DIGEST_NAMES, (self.master, self.exp_avg, self.exp_avg_sq, self.flat.flat_param)):
+                if name == "param" and same:
+                    continue
+                files[name] = f"{stem}.{name}.bin"
+                _write_synced(os.path.join(tmp, files[name]), buf[lo:hi].detach().cpu().view(torch.uint8).numpy())
+            _write_synced(os.path.join(tmp, stem + ".json"),
+                          json.dumps(dict(lo=lo, hi=hi, rank=rank, files=files, digest=hexd(own)), indent=1).encode())
+        rng = {"cpu": torch.get_rng_state()}
+        if self.master.is_cuda:
+            rng["cuda"] = torch.cuda.get_rng_state(self.master.device)
+        torch.save(rng, os.path.join(tmp, f"rng_rank{rank}.pt"))
+        with open(os.path.join(tmp, f"rng_rank{rank}.pt"), "rb") as f:
+            os.fsync(f.fileno())
+        if rank == 0:
+            ranges = [self.reducer.slab(r) for r in range(world)] if self.shard_optimizer else [(0, self.flat.numel)]
+            sched = [k for k, v in SCHEDULES.items() if v is self.schedule]
+            meta = dict(format=CHECKPOINT_FORMAT, step_idx=self.step_idx, last_lr=self.last_lr, world=world,
+                        shard_optimizer=self.shard_optimizer, numel=self.flat.numel,
+                        param_dtype=str(self.flat.flat_param.dtype), master_dtype=str(self.master.dtype),
+                        ranges=[list(r) for r in ranges if r[1] > r[0]], digest=hexd(whole), layout=self._layout(),
+                        group_defs=[list(g) for g in self.group_defs],
+                        hyper=dict(lr=self.lr, lr_final=self.lr_final, warmup_steps=self.warmup_steps, total_steps=self.total_steps,
+                                   weight_decay=self.weight_decay, betas=list(self.betas), eps=self.eps,
+                                   max_grad_norm=self.max_grad_norm, nan_guard=self.nan_guard,
+                                   schedule=sched[0] if sched else repr(self.schedule)),
+                        extra=json.loads(extra_json))
+            _write_synced(os.path.join(tmp, "meta.json"), json.dumps(meta, indent=1).encode())
+        self._barrier()
+        if rank == 0:
+            _sync_dir(tmp)
+            if os.path.isdir(final):
+                shutil.rmtree(final)
+            os.rename(tmp, final)
+            _write_synced(os.path.join(dir, "latest.new"), tag.encode())
+            os.replace(os.path.join(dir, "latest.new"), os.path.join(dir, "latest"))
+            _sync_dir(dir)
+            for d in os.listdir(dir):   # saves that never finished
+                if d.endswith(".tmp") and os.path.isdir(os.path.join(dir, d)):
+                    shutil.rmtree(os.path.join(dir, d), ignore_errors=True)
+            if keep_last:
+                old = [t for _, t in complete_checkpoints(dir) if t != tag]
+                for t in old[:max(0, len(old) - (int(keep_last) - 1))]:
+                    shutil.rmtree(os.path.join(dir, t), ignore_errors=True)
+        self._barrier()
+        return final
+
+    def load_checkpoint(self, dir, tag=None):
+        """Restore what save_checkpoint wrote into this FRESHLY constructed trainer (a model of the same architecture) and return
+        the saved `extra`.  tag=None: the tag named by <dir>/latest.  Every rank reads the whole checkpoint (a collective only in
+        that all ranks are expected to call it).
+
+        The stored layout (names, shapes, offsets, numel, dtypes) must be this trainer's: ValueError naming the first parameter that
+        differs, with model and trainer untouched.  The full buffers are assembled from whatever range files the checkpoint has --
+        a sharded 2-rank checkpoint loads into one rank and the other way round -- and copied INTO the existing flat buffers: the
+        parameters stay views of flat_param.  step_idx and last_lr are set, the modules' parameter-derived caches invalidated.  Then
+        the digest of every stored range is recomputed from the buffers (the kernel on the HIP path) and compared with the stored
+        one: RuntimeError naming the buffer on a mismatch -- a truncated or corrupted file and a bad copy alike.
+        RNG: this rank's host and device states are restored if the checkpoint has them for this rank and the world size is
+        unchanged; otherwise they are left alone, with a warning.  Schedule, parameter groups and the clip threshold are the new
+        trainer's own (a differing stored group table is a warning); the reducer discovers its buckets again as on any fresh trainer."""
+        if tag is None:
+            try:
+                with open(os.path.join(dir, "latest")) as f:
+                    tag = f.read().strip()
+            except OSError:
+                raise FileNotFoundError(f"{dir}: no `latest` file, no checkpoint to resume from") from None
+        path = os.path.join(dir, tag)
+        if tag.endswith(".tmp") or not os.path.isfile(os.path.join(path, "meta.json")):
+            raise FileNotFoundError(f"{path} is not a complete checkpoint")
+        meta = _read_json(os.path.join(path, "meta.json"))
+        if meta.get("format") != CHECKPOINT_FORMAT:
+            raise ValueError(f"{path}: checkpoint format {meta.get('format')!r}, this trainer reads {CHECKPOINT_FORMAT}")
+        mine = self._layout()
+        for a, b in zip(meta["layout"], mine):
+            if a != b:
+                raise ValueError(f"{path}: parameter `{b['name']}` is {b['shape']} at offset {b['offset']} here, the checkpoint has "
+                                 f"`{a['name']}` {a['shape']} at offset {a['offset']}")
+        if len(meta["layout"]) != len(mine) or meta["numel"] != self.flat.numel:
+            longer = meta["layout"] if len(meta["layout"]) > len(mine) else mine
+            raise ValueError(f"{path}: {len(meta['layout'])} parameters in the checkpoint, {len(mine)} here (first without a partner: "
+                             f"`{longer[min(len(meta['layout']), len(mine))]['name']}`)")
+        if meta["param_dtype"] != str(self.flat.flat_param.dtype) or meta["master_dtype"] != str(self.master.dtype):
+            raise ValueError(f"{path}: stored as {meta['param_dtype']} parameters with {meta['master_dtype']} masters, this trainer "
+                             f"holds {self.flat.flat_param.dtype} with {self.master.dtype}")
+        ranges = sorted(tuple(r) for r in meta["ranges"])
+        if not ranges or ranges[0][0] != 0 or ranges[-1][1] != self.flat.numel or any(a[1] != b[0] for a, b in zip(ranges, ranges[1:])):
+            raise RuntimeError(f"{path}: the stored ranges {ranges} do not tile [0, {self.flat.numel})")
+        same = self.master is self.flat.flat_param
+        bufs = dict(zip(DIGEST_NAMES, (self.master, self.exp_avg, self.exp_avg_sq, self.flat.flat_param)))
+        todo, stored = [], []
+        for lo, hi in ranges:   # everything that can be checked on the host before a buffer is touched
+            rj = os.path.join(path, f"range_{lo:012d}_{hi:012d}.json")
+            if not os.path.isfile(rj):
+                raise RuntimeError(f"{path}: the file of range [{lo}, {hi}) is missing")
+            info = _read_json(rj)
+            if (info["lo"], info["hi"]) != (lo, hi):
+                raise RuntimeError(f"{rj} describes [{info['lo']}, {info['hi']})")
+            stored.append([int(info["digest"][n], 16) for n in DIGEST_NAMES])
+            for name, buf in bufs.items():
+                if name == "param" and same:
+                    continue
+                f = os.path.join(path, info["files"][name])
+                want = (hi - lo) * buf.element_size()
+                if not os.path.isfile(f) or os.path.getsize(f) != want:
+                    raise RuntimeError(f"{path}: `{name}` of range [{lo}, {hi}) is missing or truncated "
+                                       f"({os.path.getsize(f) if os.path.isfile(f) else 0} bytes, {want} expected)")
+                todo.append((f, buf, lo, hi))
+        import numpy as np
+        with torch.no_grad():
+            for f, buf, lo, hi in todo:
+                buf[lo:hi].copy_(torch.from_numpy(np.fromfile(f, dtype=np.uint8)).view(buf.dtype))
+        self.step_idx, self.last_lr = int(meta["step_idx"]), meta["last_lr"]
+        self._acc_count = 0
+        for m in self._param_caches:
+            m._mix_key = None
+        for (lo, hi), want, got in zip(ranges, stored, self._range_digests(ranges)):
+            for name, w, g in zip(DIGEST_NAMES, want, got):
+                if w != g:
+                    raise RuntimeError(f"{path}: digest mismatch in `{name}`, range [{lo}, {hi}): stored {w:016x}, in memory after "
+                                       f"the load {g:016x} -- a corrupted file or a bad copy")
+        rng_file = os.path.join(path, f"rng_rank{self.reducer.rank}.pt")
+        if meta["world"] == self.world and os.path.isfile(rng_file):
+            rng = torch.load(rng_file, map_location="cpu", weights_only=True)
+            torch.set_rng_state(rng["cpu"])
+            if "cuda" in rng and self.master.is_cuda:
+                torch.cuda.set_rng_state(rng["cuda"], self.master.device)
+            elif self.master.is_cuda:
+                warnings.warn(f"{path}: no device RNG state for rank {self.reducer.rank}; the device generator is left as it is")
+        else:
+            warnings.warn(f"{path}: saved by {meta['world']} rank(s), loaded by {self.world}: the RNG states are left as they are")
+        if [list(g) for g in self.group_defs] != meta["group_defs"]:
+            warnings.warn(f"{path}: the stored parameter groups {meta['group_defs']} differ from this trainer's "
+                          f"{[list(g) for g in self.group_defs]}; this trainer's are used")
+        return meta["extra"]
