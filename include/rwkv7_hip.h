@@ -527,6 +527,18 @@ int rwkv7_grad_fold_bf16(long n, const float *acc32, void *g16, float inv_count,
 long rwkv7_buf_digest_workspace_bytes(long n_words);
 int rwkv7_buf_digest_u32(long n_words, long first_index, const void *buf, unsigned long long *partials, unsigned long long *out,
                          int accumulate, rwkv7_stream_t stream);
+/*      Snapshot and digest in one pass (the trainer's non-blocking checkpoints: a consistent copy of a state buffer that the next
+ *      step will overwrite, and the proof of what was copied): dst[0..n_words) = src[0..n_words) bit for bit, and out[0] is exactly
+ *      the word rwkv7_buf_digest_u32(n_words, first_index, src, ...) gives, `accumulate` included.  Same two launches, same tiles
+ *      and the same workspace (rwkv7_buf_digest_workspace_bytes) as that entry; each 16-byte piece is stored to dst with a plain
+ *      vector store from the registers it is then mixed from, so the digest is of the words that were written.  Words of dst at
+ *      and behind n_words are never written, src is only read.  Bytes moved: one read and one write of the buffer (a copy followed
+ *      by the digest entry reads it twice and writes it once).  Checked here, nothing launched otherwise: n_words % 4 == 0, src and
+ *      dst 16-byte aligned (RWKV7_ESHAPE); src, dst, partials non-NULL when n_words > 0, out non-NULL, nothing negative, and
+ *      [src, src + 4 n_words) must not overlap [dst, dst + 4 n_words) (RWKV7_EINVAL).  n_words == 0 stores nothing and sets out[0]
+ *      as the digest entry does.  The caller keeps both buffers alive and orders other writers of dst by the stream. */
+int rwkv7_buf_snapshot_digest_u32(long n_words, long first_index, const void *src, void *dst, unsigned long long *partials,
+                                  unsigned long long *out, int accumulate, rwkv7_stream_t stream);
 
 /* ---- last step of a split weight gradient (the dW of nn.Linear under autograd, e.g. rwkv_s2s_single_ffn.py:171-174,195,
  *      228-229, reduced over B*T in S row slabs with fp32 partials): out[n] (bf16) = (accumulate ? out[n] : 0) +

@@ -8,6 +8,9 @@
 // wrapping sum of the digests of its slabs, each taken with its own `first` (sharded checkpoints, the cross-rank check).
 // The buffer is only read.  4 bytes read per word against two 64-bit multiplies and three shift-xors: about as much integer VALU
 // work as the load delivers bytes for (DESIGN.md section 6.2 has the measured rate).
+// The snapshot form (rwkv7_buf_snapshot_digest_u32, the non-blocking checkpoints) is the same pass with one more instruction per
+// piece: the 16 bytes a thread holds are stored to a second buffer before they are mixed, so the copy and the digest of the copy
+// cost one read and one write of the data, and the digest is of the words that were written.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -29,8 +32,11 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
 // t + 7 * 256 of the tile (a wave reads 1 KiB contiguous per load), all eight loads in flight before the first multiply.
 // n % 4 == 0, so a piece is inside the buffer or outside it as a whole; a piece outside contributes NOTHING (the digest of a
 // zero word is not zero).  The key of a piece's first word costs one 64-bit multiply, the next three are one add each.
+// kSnapshot: every piece inside the buffer is also stored to dst + (its offset in w), from the registers it is mixed from; a
+// piece outside is not stored, so dst is never written at or behind word n.  dst does not overlap w (checked by the C entry).
+template <bool kSnapshot>
 __global__ __launch_bounds__(256) void buf_digest_tiles_kernel(long n, uint64_t first, const uint32_t *__restrict__ w,
-                                                               uint64_t *__restrict__ partials) {
+                                                               uint32_t *__restrict__ dst, uint64_t *__restrict__ partials) {
     __shared__ uint64_t sh[4];
     constexpr uint64_t G = 0x9E3779B97F4A7C15ull;
     const long base = (long)blockIdx.x * kDigestTile;
@@ -45,6 +51,7 @@ __global__ __launch_bounds__(256) void buf_digest_tiles_kernel(long n, uint64_t 
     for (int j = 0; j < kDigestPieces; j++) {
         const long e = base + (long)(j * 256 + (int)threadIdx.x) * 4;
         if (e < n) {
+            if constexpr (kSnapshot) *reinterpret_cast<uint4 *>(dst + e) = r[j];
             const uint64_t k0 = (first + (uint64_t)e + 1ull) * G;
             s += mix64((uint64_t)r[j].x + k0);
             s += mix64((uint64_t)r[j].y + (k0 + G));
@@ -81,13 +88,19 @@ __global__ __launch_bounds__(256) void buf_digest_final_kernel(long ntiles, cons
 
 long buf_digest_tiles(long n_words) { return (n_words + kDigestTile - 1) / kDigestTile; }
 
-int buf_digest_u32(long n_words, long first_index, const void *buf, unsigned long long *partials, unsigned long long *out,
+// dst == nullptr: digest only; otherwise dst[0..n_words) = buf[0..n_words) as well.  Same grid, same partials, same stage 2.
+int buf_digest_u32(long n_words, long first_index, const void *buf, void *dst, unsigned long long *partials, unsigned long long *out,
                    int accumulate, hipStream_t st) {
     (void)hipGetLastError();
     const long ntiles = buf_digest_tiles(n_words);
-    if (ntiles > 0)
-        hipLaunchKernelGGL(buf_digest_tiles_kernel, dim3((unsigned)ntiles), dim3(256), 0, st, n_words, (uint64_t)first_index,
-                           (const uint32_t *)buf, (uint64_t *)partials);
+    if (ntiles > 0) {
+        if (dst != nullptr)
+            hipLaunchKernelGGL(buf_digest_tiles_kernel<true>, dim3((unsigned)ntiles), dim3(256), 0, st, n_words, (uint64_t)first_index,
+                               (const uint32_t *)buf, (uint32_t *)dst, (uint64_t *)partials);
+        else
+            hipLaunchKernelGGL(buf_digest_tiles_kernel<false>, dim3((unsigned)ntiles), dim3(256), 0, st, n_words, (uint64_t)first_index,
+                               (const uint32_t *)buf, (uint32_t *)nullptr, (uint64_t *)partials);
+    }
     hipLaunchKernelGGL(buf_digest_final_kernel, dim3(1), dim3(256), 0, st, ntiles, (const uint64_t *)partials, (uint64_t *)out, accumulate);
     return (int)hipGetLastError();
 }

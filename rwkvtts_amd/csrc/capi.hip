@@ -43,7 +43,7 @@ int grad_sumsq_bf16(long, const void *, float *, float *, int, hipStream_t);
 int grad_accum_bf16(long, float *, const void *, int, hipStream_t);
 int grad_fold_bf16(long, const float *, void *, float, hipStream_t);
 long buf_digest_tiles(long);
-int buf_digest_u32(long, long, const void *, unsigned long long *, unsigned long long *, int, hipStream_t);
+int buf_digest_u32(long, long, const void *, void *, unsigned long long *, unsigned long long *, int, hipStream_t);
 int lora32_bf16(int, int, int, int, int, const void *, const void *, const void *, const void *, void *, hipStream_t);
 int chunk_bseq_bf16(int, int, int, const void *, const void *, const void *, const void *, const void *, const float *, void *,
                     float *, const int *, int, hipStream_t);
@@ -763,7 +763,19 @@ int rwkv7_buf_digest_u32(long n_words, long first_index, const void *buf, unsign
     if (n_words > 0 && any_null({buf, (const void *)partials})) return RWKV7_EINVAL;
     if (n_words % 4 != 0 || ((uintptr_t)buf & 15) != 0 || (((uintptr_t)partials | (uintptr_t)out) & 7) != 0) return RWKV7_ESHAPE;
     if (rwkv7::buf_digest_tiles(n_words) > 0x7fffffffL) return RWKV7_ESHAPE;   // one workgroup per tile: 2^44 words
-    return rwkv7::buf_digest_u32(n_words, first_index, buf, partials, out, accumulate != 0, (hipStream_t)stream);
+    return rwkv7::buf_digest_u32(n_words, first_index, buf, nullptr, partials, out, accumulate != 0, (hipStream_t)stream);
+}
+int rwkv7_buf_snapshot_digest_u32(long n_words, long first_index, const void *src, void *dst, unsigned long long *partials,
+                                  unsigned long long *out, int accumulate, rwkv7_stream_t stream) {
+    if (n_words < 0 || first_index < 0 || out == nullptr) return RWKV7_EINVAL;
+    if (n_words > 0 && any_null({src, (const void *)dst, (const void *)partials})) return RWKV7_EINVAL;
+    if (n_words % 4 != 0 || (((uintptr_t)src | (uintptr_t)dst) & 15) != 0 || (((uintptr_t)partials | (uintptr_t)out) & 7) != 0)
+        return RWKV7_ESHAPE;
+    if (rwkv7::buf_digest_tiles(n_words) > 0x7fffffffL) return RWKV7_ESHAPE;
+    const uintptr_t s = (uintptr_t)src, d = (uintptr_t)dst, nbytes = (uintptr_t)n_words * 4;
+    if (n_words > 0 && s < d + nbytes && d < s + nbytes) return RWKV7_EINVAL;   // [src, src + 4n) and [dst, dst + 4n) overlap
+    if (n_words == 0) dst = nullptr;   // nothing to store: the digest entry's empty case (out[0] = accumulate ? out[0] : 0)
+    return rwkv7::buf_digest_u32(n_words, first_index, src, dst, partials, out, accumulate != 0, (hipStream_t)stream);
 }
 int rwkv7_adamw_bf16(long n, float *p32, const void *g16, float *m, float *v, void *p16, float lr, float beta1, float beta2,
                      float eps, float weight_decay, int step, rwkv7_stream_t stream) {

@@ -7,6 +7,9 @@
 `first` is the GLOBAL index of the buffer's first word, so the digest of a buffer is the wrapping sum of the digests of its
 slabs.  Tensors on the HIP device go through the kernel (csrc/buf_digest.hip); host tensors -- the CPU trainers of the gloo
 tests -- through the numpy restatement below.  Both are exact: they give the same 64 bits.
+
+snapshot_launch / snapshot_digest copy the words to a second buffer in the same pass (rwkv7_buf_snapshot_digest_u32): what the
+trainer's non-blocking checkpoints take of a state buffer before the next step overwrites it.
 """
 import numpy as np
 import torch
@@ -70,4 +73,27 @@ def buf_digest(t, first=0):
         return fallback_digest(t, first)
     out = torch.zeros(1, dtype=torch.int64, device=t.device)
     launch(t, first, out, workspace(_n_words(t), t.device))
+    return int(out.item()) & MASK64
+
+
+def snapshot_launch(src, dst, first, out, ws, accumulate=False):
+    """Enqueue the snapshot kernel: dst's raw words = src's, out[0] = their digest (as `launch`).  src and dst: device tensors of
+    the same dtype and length that do not overlap.  Nothing is read back."""
+    n = _n_words(src)
+    if dst.dtype != src.dtype or dst.numel() != src.numel() or not dst.is_contiguous():
+        raise ValueError("snapshot: dst must be a contiguous tensor of src's dtype and length")
+    _lib.call("rwkv7_buf_snapshot_digest_u32", out, n, int(first), src if n else None, dst if n else None, ws if n else None, out,
+              int(bool(accumulate)))
+
+
+def snapshot_digest(src, dst, first=0):
+    """dst = src bit for bit, and the digest of the copied words as a Python int: one kernel pass when both live on the HIP device,
+    dst.copy_(src) and the numpy restatement over dst otherwise (host tensors)."""
+    if not (src.is_cuda and dst.is_cuda):
+        if dst.dtype != src.dtype or dst.shape != src.shape:
+            raise ValueError("snapshot: dst must have src's dtype and shape")
+        dst.copy_(src)
+        return fallback_digest(dst, first)
+    out = torch.zeros(1, dtype=torch.int64, device=src.device)
+    snapshot_launch(src, dst, first, out, workspace(_n_words(src), src.device))
     return int(out.item()) & MASK64

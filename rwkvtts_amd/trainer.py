@@ -20,6 +20,7 @@ import json
 import math
 import os
 import shutil
+import threading
 import warnings
 from typing import List, Optional
 
@@ -391,14 +392,88 @@ DIGEST_NAMES = ("master", "exp_avg", "exp_avg_sq", "param")
 
 
 def _write_synced(path, data):
-    """data (bytes, or a uint8 numpy array) to `path`, flushed to the disk before the call returns."""
+    """data (bytes, a uint8 numpy array, or an iterable of such arrays that are written one after the other) to `path`, flushed to
+    the disk before the call returns."""
     with open(path, "wb") as f:
         if isinstance(data, (bytes, bytearray)):
             f.write(data)
-        else:
+        elif hasattr(data, "tofile"):
             data.tofile(f)
+        else:
+            for piece in data:
+                piece.tofile(f)
         f.flush()
         os.fsync(f.fileno())
+
+
+def _write_checkpoint_files(tmp, job, payload):
+    """What one rank contributes to <tag>.tmp/, shared by the blocking save and the writer thread of the non-blocking one: the
+    range's .bin files and its .json (if the rank writes tensors), rng_rank<r>.pt, and rank 0's meta.json.  job:
+    DataParallelTrainer._checkpoint_job's record, complete before the first byte is written; payload(name): the raw bytes of the
+    range of buffer `name`, in a form _write_synced takes.  Reads no trainer; _write_synced is looked up at every call."""
+    for name, fname in job["files"].items():
+        _write_synced(os.path.join(tmp, fname), payload(name))
+    if job["files"]:
+        _write_synced(os.path.join(tmp, job["stem"] + ".json"), job["range_json"])
+    rng_path = os.path.join(tmp, f"rng_rank{job['rank']}.pt")
+    torch.save(job["rng"], rng_path)
+    with open(rng_path, "rb") as f:
+        os.fsync(f.fileno())
+    if job["meta_json"] is not None:
+        _write_synced(os.path.join(tmp, "meta.json"), job["meta_json"])
+
+
+CHECKPOINT_PIECE_BYTES = 64 << 20   # each of the TWO pinned host buffers a non-blocking save copies its staging through
+
+
+def _staged_pieces(staging, pinned, stream):
+    """The raw bytes of the device tensor `staging` as uint8 numpy arrays of at most len(pinned[0]) bytes, in order: piece i + 1 is
+    on its way into one pinned buffer (on `stream`) while the consumer writes piece i out of the other.  A yielded array is valid
+    until the next one is asked for."""
+    raw = staging.view(torch.uint8)
+    n, step = raw.numel(), pinned[0].numel()
+    sizes = [min(step, n - s_) for s_ in range(0, n, step)]
+    events = [None, None]
+
+    def issue(i):
+        with torch.cuda.stream(stream):
+            pinned[i % 2][:sizes[i]].copy_(raw[i * step:i * step + sizes[i]], non_blocking=True)
+            events[i % 2] = torch.cuda.Event()
+            events[i % 2].record(stream)
+
+    if sizes:
+        issue(0)
+    for i, m in enumerate(sizes):
+        events[i % 2].synchronize()
+        if i + 1 < len(sizes):
+            issue(i + 1)   # into the buffer of piece i - 1, which the consumer has finished with
+        yield pinned[i % 2][:m].numpy()
+
+
+class PendingCheckpoint:
+    """A non-blocking save that has not been finalised (DataParallelTrainer.pending_checkpoint): its tag, the path it will have,
+    the step it was taken at and the four digests of this rank's range at that moment."""
+
+    def __init__(self, dir, tag, path, step_idx, digests, keep_last):
+        self.dir, self.tag, self.path, self.step_idx, self.digests, self.keep_last = dir, tag, path, step_idx, digests, keep_last
+        self.error = None    # the writer thread's exception, if it raised one
+        self.thread = None
+
+    def __repr__(self):
+        return f"PendingCheckpoint(tag={self.tag!r}, path={self.path!r}, step_idx={self.step_idx})"
+
+
+def _checkpoint_writer(pending, tmp, job, payload, stream, event):
+    """The writer thread of a non-blocking save.  It reads the staging buffers and writes files: no trainer state, no collective."""
+    try:
+        if stream is not None:
+            stream.wait_event(event)   # the snapshot kernels, in the order of the stream they were enqueued on
+        _write_checkpoint_files(tmp, job, payload)
+    except Exception as e:   # kept for checkpoint_wait(), which raises on the calling thread of every rank
+        pending.error = e
+    finally:
+        if stream is not None:
+            stream.synchronize()   # no copy into the pinned buffers is left in flight, whatever happened
 
 
 def _sync_dir(path):
@@ -559,6 +634,8 @@ class DataParallelTrainer:
         self._acc_flag = torch.zeros(1, dtype=torch.float32, device=dev)
         self.step_idx = 0
         self.last_lr = None
+        self._pending = None          # the one non-blocking save in flight (PendingCheckpoint)
+        self._ckpt_staging = None     # its staging buffers, allocated on the first non-blocking save and kept
         # modules that cache tensors derived from parameters (RWKV7Attention._stacked_mix): the optimizer kernel rewrites
         # parameter memory through raw pointers without touching autograd's version counters, so they are told explicitly
         self._param_caches = [m for m in model.modules() if hasattr(m, "_mix_key") or hasattr(m, "_stacked_mix")]
@@ -822,56 +899,21 @@ class DataParallelTrainer:
         if self.world > 1:
             dist.barrier(group=self.reducer.group)
 
-    def save_checkpoint(self, dir, tag=None, extra=None, keep_last=3):
-        """Write the training state to <dir>/<tag>/ (tag: "step_<step_idx>" by default) and return that path; what the reference
-        scripts ask of `model_engine.save_checkpoint(output_dir)` (train_scripts/train_spark_rwkv7speech.py:199-217, 695, 734).
-        A collective when world > 1: every rank calls it with the same arguments, on a directory all ranks can see.
-
-        Written: the fp32 masters and both moments, the model-dtype flat parameters (so that no rounding has to be reproduced),
-        step_idx and last_lr, the layout (names, shapes, offsets), group_defs and the hyper-parameters (for information), one digest
-        per buffer and written range, `extra` (JSON: epoch, batch index, data cursor) and every rank's host and device RNG state.
-        Not written: gradients, the fp32 micro-batch accumulator -- saving inside an accumulation window is a RuntimeError.
-        Replicated mode: rank 0 writes the tensors, after the digests have shown the replicas to be identical; shard mode: every
-        rank writes its own slab (foreign slabs of the masters and moments are stale on a rank).
-        Everything goes to <dir>/<tag>.tmp/, every file is fsynced by its writer; after a barrier rank 0 renames the directory,
-        rewrites <dir>/latest and deletes the oldest complete checkpoints beyond keep_last (None: keep all) and stale .tmp directories.
-        One device synchronisation and device-to-host copies on the calling thread; nothing of step() changes."""
-        if self._acc_count != 0:
-            raise RuntimeError(f"save_checkpoint inside an accumulation window ({self._acc_count} micro-batches pending): "
-                               "checkpoints are taken at step boundaries, the fp32 accumulator is not serialised")
-        extra_json = json.dumps(extra)   # not JSON-serialisable: TypeError before anything is written
-        tag = f"step_{self.step_idx}" if tag is None else str(tag)
-        if not tag or tag.endswith(".tmp") or tag == "latest" or os.path.basename(tag) != tag:
-            raise ValueError(f"bad checkpoint tag {tag!r}")
+    def _checkpoint_job(self, tag, extra_json, own, whole):
+        """Everything this rank's checkpoint files hold besides the tensors, taken NOW: the range and its file names, the JSON texts
+        (already encoded), the host and device RNG states."""
         rank, world = self.reducer.rank, self.world
-        tmp, final = os.path.join(dir, tag + ".tmp"), os.path.join(dir, tag)
         lo, hi = self._own_range()
-        own = self._range_digests([(lo, hi)])[0]
-        whole = self._combine_digests(own) if world > 1 else own   # replicated mode: raises if the replicas have diverged
-        if rank == 0:
-            os.makedirs(dir, exist_ok=True)
-            if os.path.isdir(tmp):
-                shutil.rmtree(tmp)
-            os.makedirs(tmp)
-        self._barrier()
         hexd = lambda vals: {n: "%016x" % v for n, v in zip(DIGEST_NAMES, vals)}
         same = self.master is self.flat.flat_param
+        stem = f"range_{lo:012d}_{hi:012d}"
+        files = {}
         if (rank == 0 or self.shard_optimizer) and hi > lo:
-            stem = f"range_{lo:012d}_{hi:012d}"
-            files = {}
-            for name, buf in zip(DIGEST_NAMES, (self.master, self.exp_avg, self.exp_avg_sq, self.flat.flat_param)):
-                if name == "param" and same:
-                    continue
-                files[name] = f"{stem}.{name}.bin"
-                _write_synced(os.path.join(tmp, files[name]), buf[lo:hi].detach().cpu().view(torch.uint8).numpy())
-            _write_synced(os.path.join(tmp, stem + ".json"),
-                          json.dumps(dict(lo=lo, hi=hi, rank=rank, files=files, digest=hexd(own)), indent=1).encode())
+            files = {name: f"{stem}.{name}.bin" for name in DIGEST_NAMES if not (name == "param" and same)}
         rng = {"cpu": torch.get_rng_state()}
         if self.master.is_cuda:
             rng["cuda"] = torch.cuda.get_rng_state(self.master.device)
-        torch.save(rng, os.path.join(tmp, f"rng_rank{rank}.pt"))
-        with open(os.path.join(tmp, f"rng_rank{rank}.pt"), "rb") as f:
-            os.fsync(f.fileno())
+        meta_json = None
         if rank == 0:
             ranges = [self.reducer.slab(r) for r in range(world)] if self.shard_optimizer else [(0, self.flat.numel)]
             sched = [k for k, v in SCHEDULES.items() if v is self.schedule]
@@ -885,9 +927,24 @@ class DataParallelTrainer:
                                    max_grad_norm=self.max_grad_norm, nan_guard=self.nan_guard,
                                    schedule=sched[0] if sched else repr(self.schedule)),
                         extra=json.loads(extra_json))
-            _write_synced(os.path.join(tmp, "meta.json"), json.dumps(meta, indent=1).encode())
+            meta_json = json.dumps(meta, indent=1).encode()
+        return dict(rank=rank, stem=stem, files=files, rng=rng, meta_json=meta_json,
+                    range_json=json.dumps(dict(lo=lo, hi=hi, rank=rank, files=files, digest=hexd(own)), indent=1).encode())
+
+    def _checkpoint_open(self, dir, tmp):
+        """Rank 0 creates <tag>.tmp/ (a stale one is removed first); nobody writes before it exists."""
+        if self.reducer.rank == 0:
+            os.makedirs(dir, exist_ok=True)
+            if os.path.isdir(tmp):
+                shutil.rmtree(tmp)
+            os.makedirs(tmp)
         self._barrier()
-        if rank == 0:
+
+    def _checkpoint_finish(self, dir, tag, keep_last):
+        """Every rank's files are written and fsynced: rename, `latest`, stale .tmp directories, keep_last.  Returns the final path."""
+        tmp, final = os.path.join(dir, tag + ".tmp"), os.path.join(dir, tag)
+        self._barrier()
+        if self.reducer.rank == 0:
             _sync_dir(tmp)
             if os.path.isdir(final):
                 shutil.rmtree(final)
@@ -905,6 +962,141 @@ class DataParallelTrainer:
         self._barrier()
         return final
 
+    def save_checkpoint(self, dir, tag=None, extra=None, keep_last=3, blocking=True):
+        """Write the training state to <dir>/<tag>/ (tag: "step_<step_idx>" by default) and return that path; what the reference
+        scripts ask of `model_engine.save_checkpoint(output_dir)` (train_scripts/train_spark_rwkv7speech.py:199-217, 695, 734).
+        A collective when world > 1: every rank calls it with the same arguments, on a directory all ranks can see.
+
+        Written: the fp32 masters and both moments, the model-dtype flat parameters (so that no rounding has to be reproduced),
+        step_idx and last_lr, the layout (names, shapes, offsets), group_defs and the hyper-parameters (for information), one digest
+        per buffer and written range, `extra` (JSON: epoch, batch index, data cursor) and every rank's host and device RNG state.
+        Not written: gradients, the fp32 micro-batch accumulator -- saving inside an accumulation window is a RuntimeError.
+        Replicated mode: rank 0 writes the tensors, after the digests have shown the replicas to be identical; shard mode: every
+        rank writes its own slab (foreign slabs of the masters and moments are stale on a rank).
+        Everything goes to <dir>/<tag>.tmp/, every file is fsynced by its writer; after a barrier rank 0 renames the directory,
+        rewrites <dir>/latest and deletes the oldest complete checkpoints beyond keep_last (None: keep all) and stale .tmp directories.
+        blocking=True: one device synchronisation and device-to-host copies on the calling thread; nothing of step() changes.
+
+        blocking=False: the call returns the path the checkpoint WILL have once checkpoint_wait() has finalised it.  On the calling
+        thread: the same checks; a save still pending is finalised first (one in flight at a time, finalised in the order started);
+        the rank's range of the four buffers is copied into staging buffers of the same dtype and length on the current stream, each
+        by the one kernel pass that also digests the words it writes (rwkv7_buf_snapshot_digest_u32; host tensors: a copy and the
+        numpy digest), so later step() calls cannot reach what is saved; the four digests are read back -- the one device
+        synchronisation -- and, with several ranks, compared or combined as in the blocking save, so diverged replicas raise before
+        anything is written; RNG states, step_idx, last_lr, layout and hyper-parameters are captured; <tag>.tmp/ is created.  One
+        writer thread (not a daemon) then waits for the snapshot on a side stream of its own, copies the staging to the host
+        through two pinned buffers of CHECKPOINT_PIECE_BYTES used alternately, and writes and fsyncs the very files, names and bytes
+        the blocking save writes.  It touches no trainer state and issues no collective.  step() and accumulate() neither wait for it nor
+        finalise it.  The staging buffers are kept for the next save (release_checkpoint_staging() frees them).  Until
+        checkpoint_wait() -- or the next save_checkpoint / load_checkpoint on this trainer, which call it -- the checkpoint is not a
+        candidate for loading: if the process exits without it, the files may all be complete, but <tag>.tmp/ is never renamed."""
+        if self._acc_count != 0:
+            raise RuntimeError(f"save_checkpoint inside an accumulation window ({self._acc_count} micro-batches pending): "
+                               "checkpoints are taken at step boundaries, the fp32 accumulator is not serialised")
+        extra_json = json.dumps(extra)   # not JSON-serialisable: TypeError before anything is written
+        tag = f"step_{self.step_idx}" if tag is None else str(tag)
+        if not tag or tag.endswith(".tmp") or tag == "latest" or os.path.basename(tag) != tag:
+            raise ValueError(f"bad checkpoint tag {tag!r}")
+        self.checkpoint_wait()
+        world = self.world
+        tmp, final = os.path.join(dir, tag + ".tmp"), os.path.join(dir, tag)
+        lo, hi = self._own_range()
+        bufs = dict(zip(DIGEST_NAMES, (self.master, self.exp_avg, self.exp_avg_sq, self.flat.flat_param)))
+        if blocking:
+            own = self._range_digests([(lo, hi)])[0]
+            whole = self._combine_digests(own) if world > 1 else own   # replicated mode: raises if the replicas have diverged
+            self._checkpoint_open(dir, tmp)
+            _write_checkpoint_files(tmp, self._checkpoint_job(tag, extra_json, own, whole),
+                                    lambda name: bufs[name][lo:hi].detach().cpu().view(torch.uint8).numpy())
+            return self._checkpoint_finish(dir, tag, keep_last)
+        own, stream, event = self._snapshot(bufs, lo, hi)
+        whole = self._combine_digests(own) if world > 1 else own
+        job = self._checkpoint_job(tag, extra_json, own, whole)
+        self._checkpoint_open(dir, tmp)
+        staged = self._ckpt_staging
+        if stream is None:
+            payload = lambda name: staged["bufs"][name].view(torch.uint8).numpy()
+        else:
+            payload = lambda name: _staged_pieces(staged["bufs"][name], staged["pinned"], stream)
+        p = PendingCheckpoint(dir, tag, final, self.step_idx, dict(zip(DIGEST_NAMES, own)), keep_last)
+        p.thread = threading.Thread(target=_checkpoint_writer, args=(p, tmp, job, payload, stream, event),
+                                    name=f"checkpoint-writer-{tag}", daemon=False)
+        self._pending = p
+        p.thread.start()
+        return final
+
+    def _snapshot(self, bufs, lo, hi):
+        """[lo, hi) of the four state buffers into the staging buffers (allocated on first use: the same dtype and length as the
+        range; on the HIP path also the writer's side stream and its two pinned buffers), and the four digests of what was written,
+        with global word indices as _range_digests computes them.  HIP path: four rwkv7_buf_snapshot_digest_u32 calls on the current
+        stream, an event behind them, ONE read-back; returns (digests, side stream, event).  Otherwise host staging tensors and the
+        numpy restatement; returns (digests, None, None).  With an fp32 model master IS flat_param: one staging buffer, one value."""
+        same = self.master is self.flat.flat_param
+        if self._ckpt_staging is None:
+            dev = self.master.device if self.hip_adamw else torch.device("cpu")
+            st = dict(bufs={name: torch.empty(hi - lo, dtype=b.dtype, device=dev) for name, b in bufs.items()
+                            if not (name == "param" and same)})
+            if self.hip_adamw:
+                st["stream"] = torch.cuda.Stream(dev)
+                st["pinned"] = [torch.empty(CHECKPOINT_PIECE_BYTES, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+            self._ckpt_staging = st
+        st = self._ckpt_staging
+        per_word = {name: 4 // b.element_size() for name, b in bufs.items()}
+        if not self.hip_adamw:
+            own = {name: _digest.snapshot_digest(bufs[name][lo:hi].detach(), dst, lo // per_word[name]) for name, dst in st["bufs"].items()}
+            return [own["master" if same and name == "param" else name] for name in DIGEST_NAMES], None, None
+        if getattr(self, "_digest_ws", None) is None:
+            self._digest_ws = _digest.workspace(self.flat.numel, self.master.device)
+        out = torch.zeros(4, dtype=torch.int64, device=self.master.device)
+        for j, name in enumerate(DIGEST_NAMES):
+            _digest.snapshot_launch(bufs[name][lo:hi], st["bufs"][name], lo // per_word[name], out[j:j + 1], self._digest_ws)
+        event = torch.cuda.Event()
+        event.record()
+        return [v & _digest.MASK64 for v in out.tolist()], st["stream"], event
+
+    @property
+    def pending_checkpoint(self):
+        """None, or the PendingCheckpoint of the non-blocking save that checkpoint_wait() has not finalised yet."""
+        return self._pending
+
+    def checkpoint_done(self):
+        """True when no save is pending or THIS rank's writer thread has finished.  Local: no collective, no waiting."""
+        return self._pending is None or not self._pending.thread.is_alive()
+
+    def checkpoint_wait(self):
+        """Finalise the pending non-blocking save and return its path; None when nothing is pending.  A collective when world > 1.
+        Joins the writer thread; the ranks agree on whether any writer failed (all-reduce MAX of a flag).  All succeeded: the tail of
+        the blocking save in its order -- barrier, rank 0 fsyncs and renames the directory, rewrites `latest`, removes stale .tmp
+        directories, prunes to keep_last, barrier.  Any failed: rank 0 removes <tag>.tmp/, `latest` and every complete checkpoint stay
+        as they were, and EVERY rank raises RuntimeError naming the tag, chained to the writer's exception on the rank that has it.
+        Either way nothing is pending afterwards and the trainer stays usable."""
+        p = self._pending
+        if p is None:
+            return None
+        p.thread.join()
+        self._pending = None
+        failed = p.error is not None
+        if self.world > 1:
+            r_ = self.reducer
+            flag = torch.tensor([int(failed)], dtype=torch.int32, device=self.master.device if r_.backend == "nccl" else "cpu")
+            dist.all_reduce(flag, op=dist.ReduceOp.MAX, group=r_.group)
+            failed = bool(flag.item())
+        if not failed:
+            return self._checkpoint_finish(p.dir, p.tag, p.keep_last)
+        if self.reducer.rank == 0:   # every writer has been joined: nobody writes into it any more
+            shutil.rmtree(os.path.join(p.dir, p.tag + ".tmp"), ignore_errors=True)
+        self._barrier()
+        where = "on this rank" if p.error is not None else "on another rank"
+        raise RuntimeError(f"checkpoint {p.tag!r}: the writer failed {where}; nothing was renamed, "
+                           f"`latest` and the complete checkpoints in {p.dir} are unchanged") from p.error
+
+    def release_checkpoint_staging(self):
+        """Free the staging buffers of the non-blocking saves (and the pinned buffers and side stream of the HIP path); the next
+        non-blocking save allocates them again.  RuntimeError while a save is pending: call checkpoint_wait() first."""
+        if self._pending is not None:
+            raise RuntimeError(f"checkpoint {self._pending.tag!r} is pending: checkpoint_wait() before releasing its staging buffers")
+        self._ckpt_staging = None
+
     def load_checkpoint(self, dir, tag=None):
         """Restore what save_checkpoint wrote into this FRESHLY constructed trainer (a model of the same architecture) and return
         the saved `extra`.  tag=None: the tag named by <dir>/latest.  Every rank reads the whole checkpoint (a collective only in
@@ -918,7 +1110,9 @@ class DataParallelTrainer:
         one: RuntimeError naming the buffer on a mismatch -- a truncated or corrupted file and a bad copy alike.
         RNG: this rank's host and device states are restored if the checkpoint has them for this rank and the world size is
         unchanged; otherwise they are left alone, with a warning.  Schedule, parameter groups and the clip threshold are the new
-        trainer's own (a differing stored group table is a warning); the reducer discovers its buckets again as on any fresh trainer."""
+        trainer's own (a differing stored group table is a warning); the reducer discovers its buckets again as on any fresh trainer.
+        A non-blocking save pending on THIS trainer is finalised first (checkpoint_wait())."""
+        self.checkpoint_wait()
         if tag is None:
             try:
                 with open(os.path.join(dir, "latest")) as f:
