@@ -473,6 +473,23 @@ int rwkv7_ce_fwd_bwd_ld_bf16(long rows, int V, long ld, void *logits, const long
  *      registers: one read, one write); any V, ld >= V and alignment is correct. ---- */
 int rwkv7_kl_acc_fwd_bwd_bf16(long rows, int V, long ld, const void *logits, void *dlogits, const long *labels, long ignore_index,
                               float smoothing, float scale, float *loss_rows, int *correct_rows, rwkv7_stream_t stream);
+/* ---- head metrics for held-out evaluation: ONE read-only pass over a chunk of bf16 head logits [rows, ld].  Nothing is written to
+ *      the logits; columns V .. ld - 1 are never read.  No gradient is formed.
+ *        kind = 0 : cross-entropy with label smoothing, the formula of rwkv7_ce_fwd_bwd_ls_bf16 (smoothing = 0: plain CE)
+ *        kind = 1 : the Cosy label-smoothing KL, the formula of rwkv7_kl_acc_fwd_bwd_bf16; its constant C is computed by this entry on
+ *                   the HOST in double and handed to the kernel as a float, as that entry does
+ *        loss_rows[row]    = the row's loss; BIT-IDENTICAL to what rwkv7_ce_fwd_bwd_ld_bf16 (kind 0) / rwkv7_kl_acc_fwd_bwd_bf16
+ *                            (kind 1, in place) write for the same logits at the same address modulo 16 bytes, labels and smoothing:
+ *                            the fp32 row reduction runs in the training kernel's order
+ *        correct_rows[row] = 1 if the LOWEST index among the row's maxima equals the label, else 0 (the KL entry's rule)
+ *        argmax_rows[row]  = that lowest index; may be NULL; written for ignored rows too
+ *      Rows with label == ignore_index give loss_rows = 0 and correct_rows = 0.  Reductions run in fp32 from the bf16 logits with the
+ *      running maximum subtracted before exp.  Labels must be ignore_index or lie in [0, V): they are NOT checked on the device (the
+ *      kernel indexes x[label]).  RWKV7_EINVAL, before any launch: a NULL logits / labels / loss_rows / correct_rows, rows <= 0, V < 2,
+ *      ld < V, kind outside {0, 1}, smoothing outside [0, 1).  A wave per row; fastest on 16-byte aligned rows (16-byte loads, one
+ *      trip through HBM); any V >= 2, ld >= V and 2-byte alignment of the base pointer is correct. ---- */
+int rwkv7_head_eval_bf16(long rows, int V, long ld, const void *logits, const long *labels, long ignore_index, int kind, float smoothing,
+                         float *loss_rows, int *correct_rows, int *argmax_rows, rwkv7_stream_t stream);
 
 /* ---- optimizer step (train_spark_rwkv7speech.py:178-197; torch.optim.AdamW update rule, decoupled weight decay) on a
  *      flat parameter buffer: fp32 master weights p32 and moments m, v updated in place from bf16 gradients g16; the

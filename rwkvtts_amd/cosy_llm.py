@@ -18,7 +18,8 @@ from torch.nn.utils.rnn import pad_sequence
 
 from .backbone import Cache, ModelOutput, RWKV7Config, RWKV7Model
 from .hf_api import HFModelMixin
-from .losses import fused_linear_kl_accuracy, label_smoothing_kl, label_smoothing_kl_fused, th_accuracy
+from .losses import (EVAL_KL, eval_mode, fused_linear_eval, fused_linear_kl_accuracy, label_smoothing_kl, label_smoothing_kl_fused,
+                     th_accuracy)
 
 IGNORE_ID = -1  # cosyvoice/utils/common.py:24
 
@@ -105,6 +106,14 @@ def nucleus_sampling(weighted_scores, top_p=0.8, top_k=25, generator=None):
     return indices[prob.multinomial(1, replacement=True, generator=generator)]
 
 
+def _cosy_metrics(hidden, labels, lm_head, smoothing, normalize_length):
+    """eval_metrics of the Cosy layout from the backbone's hidden states [B, L, D] and the targets [B, L] (IGNORE_ID ignored)."""
+    loss_sum, tokens, correct = fused_linear_eval(hidden, labels.to(hidden.device), lm_head.weight, lm_head.bias, IGNORE_ID, EVAL_KL,
+                                                  smoothing=smoothing)
+    denom = tokens if normalize_length else torch.full_like(tokens, hidden.shape[0])
+    return dict(loss=(loss_sum / denom).float().reshape(()), loss_sum=loss_sum, tokens=tokens, correct=correct, denom=denom)
+
+
 class RWKV7CosyLM(HFModelMixin, nn.Module):
     config_class = RWKV7CosyConfig
 
@@ -185,6 +194,23 @@ class RWKV7CosyLM(HFModelMixin, nn.Module):
             return ((loss,) if loss is not None else ()) + (logits, outputs.past_key_values)
         return ModelOutput(loss=loss, logits=logits, past_key_values=outputs.past_key_values, hidden_states=None,
                            attentions=None)
+
+    def eval_metrics(self, input_ids=None, attention_mask=None, inputs_embeds=None, labels=None, max_tokens_k: Optional[int] = None,
+                     **kwargs):
+        """Held-out metrics of one batch (forward's batch kwargs: `batch=` with its target construction and max_tokens_k slicing, or
+        embeddings / ids with labels, -1 ignored): eval mode, no dropout, no autograd, the previous mode restored.  The backbone once,
+        then losses.fused_linear_eval (the label-smoothing KL and th_accuracy's count) on the hidden states -- the [B, L, V] logits never
+        exist.  Returns device tensors: loss (criterion_ce's definition: the KL sum over the valid tokens or over the batch size, as
+        length_normalized_loss says), loss_sum fp64 [1], tokens and correct int64 [1], denom [1] (what loss_sum is divided by)."""
+        with eval_mode(self):
+            if "batch" in kwargs:
+                inputs_embeds, attention_mask, labels = self.build_inputs(kwargs["batch"])
+                if max_tokens_k is not None:
+                    max_bsz = max_tokens_k * 1024 // inputs_embeds.shape[1]
+                    if max_bsz < inputs_embeds.shape[0]:
+                        inputs_embeds, labels, attention_mask = inputs_embeds[:max_bsz], labels[:max_bsz], attention_mask[:max_bsz]
+            hidden = self.model(input_ids=input_ids, attention_mask=attention_mask, inputs_embeds=inputs_embeds)[0]
+            return _cosy_metrics(hidden, labels, self.lm_head, self.config.lsm_weight, self.config.length_normalized_loss)
 
     def forward_one_step(self, xs, masks, cache=None):
         """cosy_llm.py:274-286 / llm.py:146-158."""
@@ -371,3 +397,15 @@ class RWKV7LM(nn.Module):
                                   self.length_normalized_loss)
         acc = th_accuracy(logits.view(-1, self.speech_token_size + 1), lm_target, ignore_label=IGNORE_ID)
         return {"loss": loss, "acc": acc}
+
+    build_inputs = RWKV7CosyLM.build_inputs
+
+    def eval_metrics(self, batch: dict):
+        """Held-out metrics of one batch (forward's argument): eval mode, no dropout, no autograd, the previous mode restored; see
+        RWKV7CosyLM.eval_metrics.  `acc` of forward is correct / tokens.  Needs an llm that exposes .model and .lm_head."""
+        if not (hasattr(self.llm, "model") and hasattr(self.llm, "lm_head")):
+            raise TypeError("RWKV7LM.eval_metrics needs an llm with .model and .lm_head (the hidden states go to the fused head)")
+        with eval_mode(self):
+            lm_input, attention_mask, lm_target = self.build_inputs(batch)
+            hidden = self.llm.model(inputs_embeds=lm_input, attention_mask=attention_mask)[0]
+            return _cosy_metrics(hidden, lm_target, self.llm.lm_head, self.lsm_weight, self.length_normalized_loss)

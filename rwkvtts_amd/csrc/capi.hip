@@ -35,6 +35,7 @@ int chunk_debug_tr16(const uint16_t *, const int *, uint16_t *, hipStream_t);
 int gemv32_bf16(int, int, int, const void *, const void *, const void *, void *, hipStream_t);
 int ce_fwd_bwd(long, int, long, void *, const long *, long, float, float *, float, hipStream_t);
 int kl_acc_fwd_bwd(long, int, long, const void *, void *, const long *, long, float, float, float, float *, int *, hipStream_t);
+int head_eval(long, int, long, const void *, const long *, long, int, float, float, float *, int *, int *, hipStream_t);
 int adamw_step(long, float *, const void *, float *, float *, void *, const uint8_t *, const float *, const float *, float, float, float, float,
                float, float, float, hipStream_t);
 int adamw_clip_step(long, float *, const void *, float *, float *, void *, const uint8_t *, const float *, const float *, const float *,
@@ -814,6 +815,18 @@ int rwkv7_kl_acc_fwd_bwd_bf16(long rows, int V, long ld, const void *logits, voi
     const double C = (1.0 - s) * log(1.0 - s) + (s > 0.0 ? s * log(s / (double)(V - 1)) : 0.0);
     return rwkv7::kl_acc_fwd_bwd(rows, V, ld, logits, dlogits, labels, ignore_index, smoothing, (float)C, scale, loss_rows, correct_rows,
                                  (hipStream_t)stream);
+}
+int rwkv7_head_eval_bf16(long rows, int V, long ld, const void *logits, const long *labels, long ignore_index, int kind, float smoothing,
+                         float *loss_rows, int *correct_rows, int *argmax_rows, rwkv7_stream_t stream) {
+    if (rows <= 0 || V < 2 || ld < V || (kind != 0 && kind != 1) ||
+        any_null({logits, (const void *)labels, (const void *)loss_rows, (const void *)correct_rows}))
+        return RWKV7_EINVAL;
+    if (!(smoothing >= 0.f && smoothing < 1.f)) return RWKV7_EINVAL;
+    // kind 1: the entropy constant of the target distribution, exactly as rwkv7_kl_acc_fwd_bwd_bf16 forms it
+    const double s = (double)smoothing;
+    const double C = kind == 1 ? (1.0 - s) * log(1.0 - s) + (s > 0.0 ? s * log(s / (double)(V - 1)) : 0.0) : 0.0;
+    return rwkv7::head_eval(rows, V, ld, logits, labels, ignore_index, kind, smoothing, (float)C, loss_rows, correct_rows, argmax_rows,
+                            (hipStream_t)stream);
 }
 int rwkv7_wgrad_skinny_bf16(long M, int N, int K, int S, const void *dy, const void *x, float *parts, rwkv7_stream_t stream) {
     if (any_null({dy, x, parts})) return RWKV7_EINVAL;

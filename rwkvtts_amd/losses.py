@@ -8,7 +8,11 @@ label_smoothing_kl         : third_party/cosyvoice/transformer/label_smoothing_l
 th_accuracy                : third_party/cosyvoice/utils/common.py:76-95.
 fused_linear_kl_accuracy   : the two above on the head GEMM's bf16 logits chunk by chunk through rwkv7_kl_acc_fwd_bwd_bf16 (opt-in:
     RWKV7LM(fused_loss=True)); label_smoothing_kl_fused: the loss alone on logits the caller keeps (RWKV7CosyConfig(fused_loss=True)).
+fused_linear_eval          : forward-only loss sum / valid count / correct count of a head for held-out evaluation, chunk by chunk
+    through rwkv7_head_eval_bf16 (the heads' eval_metrics, DataParallelTrainer.evaluate).
 """
+import contextlib
+import math
 import os
 
 import torch
@@ -317,3 +321,97 @@ def label_smoothing_kl_fused(logits, target, size, padding_idx, smoothing, norma
     if not (_kl_acc_gate(x, t) and 0 <= smoothing < 1 and x.is_contiguous()):
         return label_smoothing_kl(logits, target, size, padding_idx, smoothing, normalize_length)
     return _KLFromLogits.apply(x, t, logits.shape[0], float(smoothing), normalize_length, padding_idx)
+
+
+# ---- held-out evaluation ---------------------------------------------------------------------------------
+EVAL_HITS = [0]   # launches of rwkv7_head_eval_bf16 (one per chunk): how a test sees which route a call took
+EVAL_CE, EVAL_KL = 0, 1   # `kind` of rwkv7_head_eval_bf16: cross-entropy with label smoothing / the Cosy label-smoothing KL
+EVAL_CHUNK_ROWS = int(os.environ.get("RWKV7_EVAL_CHUNK_ROWS", "0"))   # rows per chunk where the caller names none (0: auto_chunk)
+
+
+@contextlib.contextmanager
+def eval_mode(module):
+    """module.eval() under torch.no_grad() for the block; the previous mode is restored afterwards.  Dropout draws nothing in eval
+    mode, so the host and device random streams are where they were."""
+    was_training = module.training
+    module.eval()
+    try:
+        with torch.no_grad():
+            yield
+    finally:
+        module.train(was_training)
+
+
+def _eval_rows_torch(logits, labels, ignore_index, kind, smoothing):
+    """The two row formulas of rwkv7_head_eval_bf16 in torch, fp32 from the logits as given: (loss_rows fp32, correct_rows bool)."""
+    x = logits.float()
+    V = x.shape[1]
+    valid = labels != ignore_index
+    y = labels.clamp(min=0).unsqueeze(1)
+    lse = torch.logsumexp(x, dim=1)
+    xy = x.gather(1, y).squeeze(1)
+    if kind == EVAL_CE:
+        per = lse - xy
+        if smoothing > 0:
+            per = (1 - smoothing) * per + smoothing * (lse - x.mean(dim=1))
+    else:
+        per = -(1 - smoothing) * (xy - lse)
+        if smoothing > 0:
+            C = (1 - smoothing) * math.log(1 - smoothing) + smoothing * math.log(smoothing / (V - 1))
+            per = per + C - smoothing / (V - 1) * ((x.sum(dim=1) - xy) - (V - 1) * lse)
+    correct = (x.argmax(dim=1) == labels) & valid   # torch.argmax: the lowest index among the maxima
+    return per.masked_fill(~valid, 0.0), correct
+
+
+@torch.no_grad()
+def fused_linear_eval(hidden, labels, weight, bias, ignore_index, kind, smoothing=0.0, chunk=None):
+    """Forward-only metrics of a head: hidden [..., D], labels [...] -> device tensors (loss_sum fp64 [1], n_valid int64 [1],
+    n_correct int64 [1]) of F.linear(hidden, weight, bias): the sum over the valid rows of the head's per-row training loss (kind
+    EVAL_CE: cross-entropy with label smoothing, as fused_linear_cross_entropy; EVAL_KL: the Cosy label-smoothing KL, as
+    fused_linear_kl_accuracy), the number of labels != ignore_index, and the number of valid rows whose argmax (lowest index among the
+    maxima) is the label.  No autograd, no host synchronisation.
+    bf16 CUDA hidden / weight / bias with int64 labels: chunk by chunk over the rows, the head GEMM into ONE reused bf16 buffer of
+    [chunk, ld] logits (ld = V rounded up to 16-byte rows), then rwkv7_head_eval_bf16 on it -- nothing larger than chunk x ld logits is
+    ever held, and the per-row losses are bit for bit those of the training kernels.  Anything else: the same values from fp32 logits
+    in torch, chunk by chunk as well.  chunk: rows per round (None: EVAL_CHUNK_ROWS if set, else auto_chunk)."""
+    if kind not in (EVAL_CE, EVAL_KL) or not 0 <= smoothing < 1:
+        raise ValueError(f"fused_linear_eval: kind must be 0 (CE) or 1 (KL) and smoothing in [0, 1), got {kind}, {smoothing}")
+    D, V = hidden.shape[-1], weight.shape[0]
+    h2, lab = hidden.reshape(-1, D), labels.reshape(-1)
+    N, dev = h2.shape[0], h2.device
+    hip = _kl_acc_gate(h2, lab, weight, bias)
+    if chunk is None:
+        # torch route: fp32 logits and one fp32 temporary of that size
+        chunk = EVAL_CHUNK_ROWS or auto_chunk(N, V, h2.element_size() if hip else 8)
+    chunk = max(1, min(chunk, N))
+    loss_sum = torch.zeros(1, dtype=torch.float64, device=dev)
+    n_correct = torch.zeros(1, dtype=torch.int64, device=dev)
+    n_valid = (lab != ignore_index).sum().reshape(1)
+    if hip:
+        if CHECK_LABELS:
+            bad = (lab != ignore_index) & ((lab < 0) | (lab >= V))
+            assert not bool(bad.any()), f"labels outside [0, {V}) that are not ignore_index={ignore_index}"
+        ld = -(-V // 8) * 8
+        buf = torch.empty(chunk, ld, dtype=h2.dtype, device=dev)
+        loss_rows = torch.empty(chunk, dtype=torch.float32, device=dev)
+        correct = torch.empty(chunk, dtype=torch.int32, device=dev)
+        lab = lab.contiguous()
+        wt = weight.t()
+    for s in range(0, N, chunk):
+        h, lb = h2[s:s + chunk], lab[s:s + chunk]
+        rows = h.shape[0]
+        if hip:
+            out = buf[:rows, :V]   # rows of ld elements: the GEMM writes the V logits, the kernel never reads the rest
+            if bias is None:
+                torch.mm(h, wt, out=out)
+            else:
+                torch.addmm(bias, h, wt, out=out)
+            _lib.call("rwkv7_head_eval_bf16", buf, rows, V, ld, buf, lb, ignore_index, kind, float(smoothing), loss_rows, correct, None)
+            EVAL_HITS[0] += 1
+            loss_sum += loss_rows[:rows].sum(dtype=torch.float64)
+            n_correct += correct[:rows].sum()
+        else:
+            per, ok = _eval_rows_torch(F.linear(h, weight, bias), lb, ignore_index, kind, smoothing)
+            loss_sum += per.sum(dtype=torch.float64)
+            n_correct += ok.sum()
+    return loss_sum, n_valid, n_correct

@@ -20,7 +20,7 @@ import torch.nn.functional as F
 
 from .backbone import Cache, Linear, ModelOutput, RWKV7Config, RWKV7Model
 from .hf_api import HFModelMixin
-from .losses import fused_linear_cross_entropy
+from .losses import EVAL_CE, eval_mode, fused_linear_cross_entropy, fused_linear_eval
 
 
 class RWKV7SpeechConfig(RWKV7Config):
@@ -108,6 +108,26 @@ class RWKV7ForSpeech(HFModelMixin, nn.Module):
             return (loss,) + out if loss is not None else out
         return ModelOutput(loss=loss, logits=logits, past_key_values=outputs.past_key_values, hidden_states=None,
                            attentions=None)
+
+    def eval_metrics(self, input_ids=None, attention_mask=None, inputs_embeds=None, labels=None, **kwargs):
+        """Held-out metrics of one batch (forward's batch kwargs; labels required): eval mode, no dropout, no autograd, the previous
+        mode restored.  The backbone once, then losses.fused_linear_eval on the hidden states -- the [B, T, V] logits never exist.
+        Labels as in forward: shifted by one here, -100 ignored, packed rows past cu_seqlens[-1] ignored unless strict_reference_loss.
+        Returns device tensors: loss (the training loss' definition: mean CE over the valid positions), loss_sum fp64 [1], tokens and
+        correct int64 [1], denom [1] (what loss_sum is divided by: tokens)."""
+        for k in ("past_key_values", "use_cache", "output_attentions", "output_hidden_states", "return_dict", "logits_to_keep"):
+            kwargs.pop(k, None)
+        with eval_mode(self):
+            hidden = self.model(input_ids=input_ids, attention_mask=attention_mask, inputs_embeds=inputs_embeds, **kwargs)[0]
+            ignore_index = getattr(self.criterion, "ignore_index", -100)
+            labels = labels.to(hidden.device)
+            labels = torch.cat((labels[..., 1:], torch.full_like(labels[:, :1], ignore_index)), 1)
+            cu = kwargs.get("cu_seqlens")
+            if cu is not None and not getattr(self.config, "strict_reference_loss", False):   # see forward
+                pos = torch.arange(labels.shape[1], device=labels.device)
+                labels = torch.where(pos.unsqueeze(0) >= cu[-1].to(labels.device), torch.full_like(labels, ignore_index), labels)
+            loss_sum, tokens, correct = fused_linear_eval(hidden, labels, self.lm_head.weight, self.lm_head.bias, ignore_index, EVAL_CE)
+        return dict(loss=(loss_sum / tokens).float().reshape(()), loss_sum=loss_sum, tokens=tokens, correct=correct, denom=tokens)
 
     def prepare_inputs_for_generation(self, input_ids=None, past_key_values=None, attention_mask=None,
                                       inputs_embeds=None, use_cache=True, logits_to_keep=None, **kwargs):

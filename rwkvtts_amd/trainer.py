@@ -837,6 +837,40 @@ class DataParallelTrainer:
         self.step_idx += 1
         return loss.detach()
 
+    def evaluate(self, batches):
+        """Held-out evaluation.  batches: an iterable of batch dicts, this rank's shard (at least one batch on
+        every rank).  model.eval_metrics per batch; the sums stay on the device, ONE all_reduce(SUM) at the end when world > 1 (a
+        collective: every rank calls evaluate), then ONE host read.  Returns Python numbers: `loss` (recomputed from the global sums
+        with the head's own normalisation: loss_sum / tokens for the token-mean heads, summed over the channels for XY), `accuracy`
+        (correct / tokens), `tokens`, and for a multi-channel head `per_channel` = {"loss", "accuracy", "tokens"} lists.
+        Nothing of the run moves: eval mode under no_grad (no dropout draw, no gradient hook fires), so parameters, masters, moments,
+        step_idx, the learning rate, the flat gradient buffer, the NaN flag, the reducer's bucket bookkeeping and the host and device
+        random streams are what they were -- k steps, evaluate, m steps is bit-identical to k + m steps.  Not allowed inside an
+        accumulation window; allowed while a non-blocking checkpoint's writer is running (it reads its own staged copy)."""
+        if self._acc_count != 0:
+            raise RuntimeError(f"evaluate inside an accumulation window ({self._acc_count} micro-batches pending): "
+                               "call step() first")
+        sums = None   # fp64 [4, channels]: loss_sum, denom, tokens, correct (counts are exact in fp64 up to 2^53)
+        for batch in batches:
+            m = self.model.eval_metrics(**batch)
+            cur = torch.stack([m[k].double() for k in ("loss_sum", "denom", "tokens", "correct")])
+            sums = cur if sums is None else sums.add_(cur)
+        if sums is None:
+            raise ValueError("evaluate needs at least one batch on every rank")
+        if self.world > 1:
+            if self.reducer.backend != "nccl":
+                sums = sums.cpu()
+            dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=self.reducer.group)
+        loss_sum, denom, tokens, correct = sums.tolist()
+        nan = float("nan")
+        losses = [ls / d if d else nan for ls, d in zip(loss_sum, denom)]
+        total = int(sum(tokens))
+        out = dict(loss=sum(losses), accuracy=sum(correct) / total if total else nan, tokens=total)
+        if len(tokens) > 1:
+            out["per_channel"] = dict(loss=losses, accuracy=[c / t if t else nan for c, t in zip(correct, tokens)],
+                                      tokens=[int(t) for t in tokens])
+        return out
+
     # ---- state digest and checkpoints (DESIGN.md section 6.2) ------------------------------------------------------------------
     def _own_range(self):
         """[lo, hi) of the flat buffers this rank is the authority on: its slab in shard mode, everything otherwise."""

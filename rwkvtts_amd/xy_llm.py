@@ -20,7 +20,7 @@ import torch.nn.functional as F
 
 from .backbone import Cache, ModelOutput, RWKV7Config, RWKV7Model
 from .hf_api import HFModelMixin
-from .losses import fused_linear_cross_entropy
+from .losses import EVAL_CE, eval_mode, fused_linear_cross_entropy, fused_linear_eval
 
 
 class RWKV7XYConfig(RWKV7Config):
@@ -114,6 +114,21 @@ class RWKV7XYLM(HFModelMixin, nn.Module):
             return ((total_loss,) if total_loss is not None else ()) + (all_logits, outputs.past_key_values)
         return ModelOutput(loss=total_loss, logits=all_logits, past_key_values=outputs.past_key_values,
                            hidden_states=None, attentions=None)
+
+    def eval_metrics(self, input_ids=None, attention_mask=None, inputs_embeds=None, labels=None, **kwargs):
+        """Held-out metrics of one batch (forward's batch kwargs; labels [B, T, C] required, not shifted, -100 ignored): eval mode, no
+        dropout, no autograd, the previous mode restored.  The backbone once, then losses.fused_linear_eval per channel on the hidden
+        states with the heads' label_smoothing -- no head's [B, T, V] logits ever exist.  Returns device tensors: loss (the training
+        loss' definition: the sum of the per-channel mean CEs), loss_sum fp64 [C], tokens and correct int64 [C], denom [C] (what each
+        channel's loss_sum is divided by: its tokens)."""
+        with eval_mode(self):
+            if inputs_embeds is None and input_ids is not None:
+                inputs_embeds = self.embed(input_ids)
+            hidden = self.model(inputs_embeds=inputs_embeds, attention_mask=attention_mask)[0]
+            per = [fused_linear_eval(hidden, labels[:, :, i].to(hidden.device), self.heads[i].weight, self.heads[i].bias, -100, EVAL_CE,
+                                     smoothing=self.config.lsm_weight) for i in range(self.config.num_channels)]
+        loss_sum, tokens, correct = (torch.cat(t) for t in zip(*per))
+        return dict(loss=(loss_sum / tokens).sum().float(), loss_sum=loss_sum, tokens=tokens, correct=correct, denom=tokens)
 
     def is_audio_token(self, token_id):
         c = self.config
