@@ -490,6 +490,24 @@ int rwkv7_kl_acc_fwd_bwd_bf16(long rows, int V, long ld, const void *logits, voi
  *      trip through HBM); any V >= 2, ld >= V and 2-byte alignment of the base pointer is correct. ---- */
 int rwkv7_head_eval_bf16(long rows, int V, long ld, const void *logits, const long *labels, long ignore_index, int kind, float smoothing,
                          float *loss_rows, int *correct_rows, int *argmax_rows, rwkv7_stream_t stream);
+/* ---- per-sequence scores from the per-row outputs of rwkv7_head_eval_bf16: ONE launch after the last chunk of a batch, over the
+ *      full-length loss_rows / correct_rows / labels (16 bytes per row; the logits are never kept).  Sequence s owns rows
+ *      seq_start[s] .. seq_start[s + 1] - 1 (seq_start: int64 [n_seq + 1] on the DEVICE, non-decreasing); over its rows with
+ *      label != ignore_index:
+ *        loss_sum[s]   = the sum of loss_rows, accumulated in fp64
+ *        tokens[s]     = the number of such rows;   correct[s] = the sum of correct_rows over them
+ *        worst_loss[s] = the maximum of loss_rows (a NaN counts as the largest, as torch.max / torch.argmax take it)
+ *        worst_row[s]  = the LOWEST row index, relative to seq_start[s], that attains worst_loss
+ *      A sequence with no such row (an empty range included) gives 0, 0, 0, 0.0f, -1.
+ *      FIXED summation order, a function of the sequence's length alone -- not of the grid, of n_seq, of which workgroup takes the
+ *      sequence or of how the rows were chunked upstream: one 256-thread workgroup per sequence; thread t adds rows t, t + 256, ... in
+ *      ascending order into one fp64 partial; an xor butterfly (32 .. 1) combines a wave; waves 0, 1, 2, 3 are added in that order
+ *      through LDS.  No atomics, nothing shared between workgroups; the results are stored by one thread.
+ *      seq_start is device data and is NOT range-checked: every row in [seq_start[s], seq_start[s + 1]) is read (a decreasing pair is
+ *      an empty sequence).  RWKV7_EINVAL, before any launch: a NULL pointer, n_seq <= 0 or n_seq >= 2^31. ---- */
+int rwkv7_seq_scores_f32(long n_seq, const long *seq_start, const float *loss_rows, const int *correct_rows, const long *labels,
+                         long ignore_index, double *loss_sum, long *tokens, long *correct, float *worst_loss, long *worst_row,
+                         rwkv7_stream_t stream);
 
 /* ---- optimizer step (train_spark_rwkv7speech.py:178-197; torch.optim.AdamW update rule, decoupled weight decay) on a
  *      flat parameter buffer: fp32 master weights p32 and moments m, v updated in place from bf16 gradients g16; the

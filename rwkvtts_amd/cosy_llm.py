@@ -18,8 +18,8 @@ from torch.nn.utils.rnn import pad_sequence
 
 from .backbone import Cache, ModelOutput, RWKV7Config, RWKV7Model
 from .hf_api import HFModelMixin
-from .losses import (EVAL_KL, eval_mode, fused_linear_eval, fused_linear_kl_accuracy, label_smoothing_kl, label_smoothing_kl_fused,
-                     th_accuracy)
+from .losses import (EVAL_KL, SCORE_KEYS, eval_mode, fused_linear_eval, fused_linear_kl_accuracy, fused_linear_score, label_smoothing_kl,
+                     label_smoothing_kl_fused, padded_seq_start, th_accuracy)
 
 IGNORE_ID = -1  # cosyvoice/utils/common.py:24
 
@@ -114,6 +114,15 @@ def _cosy_metrics(hidden, labels, lm_head, smoothing, normalize_length):
     return dict(loss=(loss_sum / denom).float().reshape(()), loss_sum=loss_sum, tokens=tokens, correct=correct, denom=denom)
 
 
+def _cosy_scores(hidden, labels, lm_head, smoothing):
+    """score of the Cosy layout from the backbone's hidden states [B, L, D] and the targets [B, L] (IGNORE_ID ignored): utterance b
+    is batch row b, scored over its lm_target rows with the label-smoothing KL."""
+    B, L = labels.shape
+    out = fused_linear_score(hidden, labels.to(hidden.device), lm_head.weight, lm_head.bias, IGNORE_ID, EVAL_KL, smoothing=smoothing,
+                             seq_start=padded_seq_start(B, L, hidden.device))
+    return dict(zip(SCORE_KEYS, out))
+
+
 class RWKV7CosyLM(HFModelMixin, nn.Module):
     config_class = RWKV7CosyConfig
 
@@ -203,14 +212,27 @@ class RWKV7CosyLM(HFModelMixin, nn.Module):
         exist.  Returns device tensors: loss (criterion_ce's definition: the KL sum over the valid tokens or over the batch size, as
         length_normalized_loss says), loss_sum fp64 [1], tokens and correct int64 [1], denom [1] (what loss_sum is divided by)."""
         with eval_mode(self):
-            if "batch" in kwargs:
-                inputs_embeds, attention_mask, labels = self.build_inputs(kwargs["batch"])
-                if max_tokens_k is not None:
-                    max_bsz = max_tokens_k * 1024 // inputs_embeds.shape[1]
-                    if max_bsz < inputs_embeds.shape[0]:
-                        inputs_embeds, labels, attention_mask = inputs_embeds[:max_bsz], labels[:max_bsz], attention_mask[:max_bsz]
-            hidden = self.model(input_ids=input_ids, attention_mask=attention_mask, inputs_embeds=inputs_embeds)[0]
+            hidden, labels = self._scored_rows(input_ids, attention_mask, inputs_embeds, labels, max_tokens_k, kwargs)
             return _cosy_metrics(hidden, labels, self.lm_head, self.config.lsm_weight, self.config.length_normalized_loss)
+
+    def _scored_rows(self, input_ids, attention_mask, inputs_embeds, labels, max_tokens_k, kwargs):
+        """What eval_metrics and score evaluate (call inside eval_mode): the backbone's hidden states [B, L, D] and the targets [B, L]."""
+        if "batch" in kwargs:
+            inputs_embeds, attention_mask, labels = self.build_inputs(kwargs["batch"])
+            if max_tokens_k is not None:
+                max_bsz = max_tokens_k * 1024 // inputs_embeds.shape[1]
+                if max_bsz < inputs_embeds.shape[0]:
+                    inputs_embeds, labels, attention_mask = inputs_embeds[:max_bsz], labels[:max_bsz], attention_mask[:max_bsz]
+        return self.model(input_ids=input_ids, attention_mask=attention_mask, inputs_embeds=inputs_embeds)[0], labels
+
+    def score(self, input_ids=None, attention_mask=None, inputs_embeds=None, labels=None, max_tokens_k: Optional[int] = None, **kwargs):
+        """Per-utterance scores of one batch (eval_metrics' batch kwargs, rows and targets; the backbone once, eval mode, no autograd,
+        the previous mode restored): one sequence per utterance over its lm_target rows -- a dict of [B] device tensors: loss_sum fp64
+        (the label-smoothing KL summed over the utterance's targets), tokens and correct int64, worst_loss fp32 and worst_row int64 (the
+        first position of the utterance's row of the batch with the largest loss); losses.fused_linear_score."""
+        with eval_mode(self):
+            hidden, labels = self._scored_rows(input_ids, attention_mask, inputs_embeds, labels, max_tokens_k, kwargs)
+            return _cosy_scores(hidden, labels, self.lm_head, self.config.lsm_weight)
 
     def forward_one_step(self, xs, masks, cache=None):
         """cosy_llm.py:274-286 / llm.py:146-158."""
@@ -409,3 +431,12 @@ class RWKV7LM(nn.Module):
             lm_input, attention_mask, lm_target = self.build_inputs(batch)
             hidden = self.llm.model(inputs_embeds=lm_input, attention_mask=attention_mask)[0]
             return _cosy_metrics(hidden, lm_target, self.llm.lm_head, self.lsm_weight, self.length_normalized_loss)
+
+    def score(self, batch: dict):
+        """Per-utterance scores of one batch (forward's argument; eval_metrics' rows and targets): see RWKV7CosyLM.score."""
+        if not (hasattr(self.llm, "model") and hasattr(self.llm, "lm_head")):
+            raise TypeError("RWKV7LM.score needs an llm with .model and .lm_head (the hidden states go to the fused head)")
+        with eval_mode(self):
+            lm_input, attention_mask, lm_target = self.build_inputs(batch)
+            hidden = self.llm.model(inputs_embeds=lm_input, attention_mask=attention_mask)[0]
+            return _cosy_scores(hidden, lm_target, self.llm.lm_head, self.lsm_weight)

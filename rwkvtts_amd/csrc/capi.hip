@@ -36,6 +36,7 @@ int gemv32_bf16(int, int, int, const void *, const void *, const void *, void *,
 int ce_fwd_bwd(long, int, long, void *, const long *, long, float, float *, float, hipStream_t);
 int kl_acc_fwd_bwd(long, int, long, const void *, void *, const long *, long, float, float, float, float *, int *, hipStream_t);
 int head_eval(long, int, long, const void *, const long *, long, int, float, float, float *, int *, int *, hipStream_t);
+int seq_scores(long, const long *, const float *, const int *, const long *, long, double *, long *, long *, float *, long *, hipStream_t);
 int adamw_step(long, float *, const void *, float *, float *, void *, const uint8_t *, const float *, const float *, float, float, float, float,
                float, float, float, hipStream_t);
 int adamw_clip_step(long, float *, const void *, float *, float *, void *, const uint8_t *, const float *, const float *, const float *,
@@ -827,6 +828,16 @@ int rwkv7_head_eval_bf16(long rows, int V, long ld, const void *logits, const lo
     const double C = kind == 1 ? (1.0 - s) * log(1.0 - s) + (s > 0.0 ? s * log(s / (double)(V - 1)) : 0.0) : 0.0;
     return rwkv7::head_eval(rows, V, ld, logits, labels, ignore_index, kind, smoothing, (float)C, loss_rows, correct_rows, argmax_rows,
                             (hipStream_t)stream);
+}
+int rwkv7_seq_scores_f32(long n_seq, const long *seq_start, const float *loss_rows, const int *correct_rows, const long *labels,
+                         long ignore_index, double *loss_sum, long *tokens, long *correct, float *worst_loss, long *worst_row,
+                         rwkv7_stream_t stream) {
+    if (n_seq <= 0 || n_seq > 0x7fffffffL ||   // one workgroup per sequence: the grid's x extent
+        any_null({(const void *)seq_start, (const void *)loss_rows, (const void *)correct_rows, (const void *)labels,
+                  (const void *)loss_sum, (const void *)tokens, (const void *)correct, (const void *)worst_loss, (const void *)worst_row}))
+        return RWKV7_EINVAL;
+    return rwkv7::seq_scores(n_seq, seq_start, loss_rows, correct_rows, labels, ignore_index, loss_sum, tokens, correct, worst_loss,
+                             worst_row, (hipStream_t)stream);
 }
 int rwkv7_wgrad_skinny_bf16(long M, int N, int K, int S, const void *dy, const void *x, float *parts, rwkv7_stream_t stream) {
     if (any_null({dy, x, parts})) return RWKV7_EINVAL;

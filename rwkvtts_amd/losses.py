@@ -10,6 +10,9 @@ fused_linear_kl_accuracy   : the two above on the head GEMM's bf16 logits chunk 
     RWKV7LM(fused_loss=True)); label_smoothing_kl_fused: the loss alone on logits the caller keeps (RWKV7CosyConfig(fused_loss=True)).
 fused_linear_eval          : forward-only loss sum / valid count / correct count of a head for held-out evaluation, chunk by chunk
     through rwkv7_head_eval_bf16 (the heads' eval_metrics, DataParallelTrainer.evaluate).
+fused_linear_score         : the same rows reduced per SEQUENCE instead of per batch (loss sum, tokens, correct, worst token): the
+    per-row outputs of rwkv7_head_eval_bf16 kept for the whole batch, then one rwkv7_seq_scores_f32 launch (the heads' score,
+    DataParallelTrainer.score).
 """
 import contextlib
 import math
@@ -415,3 +418,120 @@ def fused_linear_eval(hidden, labels, weight, bias, ignore_index, kind, smoothin
             loss_sum += per.sum(dtype=torch.float64)
             n_correct += ok.sum()
     return loss_sum, n_valid, n_correct
+
+
+# ---- per-utterance scores -----------------------------------------------------------------------------------
+SCORE_HITS = [0]   # launches of rwkv7_seq_scores_f32 (one per call): how a test sees which route a call took
+SCORE_KEYS = ("loss_sum", "tokens", "correct", "worst_loss", "worst_row")
+SCORE_CHUNK_ALIGN = 64   # HIP route: rows per head GEMM call are a multiple of this (see _score_rows)
+
+
+def _score_rows(hidden, labels, weight, bias, ignore_index, kind, smoothing, chunk):
+    """(loss_rows fp32 [N], correct_rows int32 [N], labels int64 [N] contiguous, hip) of F.linear(hidden, weight, bias) for ALL N rows,
+    filled chunk by chunk exactly as fused_linear_eval walks them: the same gate, the same GEMM into one reused [chunk, ld] bf16 buffer,
+    rwkv7_head_eval_bf16 writing into slices of the full-length arrays (HIP route), or _eval_rows_torch per chunk.
+    HIP route: the library GEMM takes another kernel, with another rounding of a few logits, for calls of a handful of rows (measured:
+    up to 15; from 16 rows on a row's logits did not depend on the number of rows in the call).  So that the chunk size changes no bit
+    of the scores, no call is that small: the chunk is rounded up to a multiple of SCORE_CHUNK_ALIGN = 64 rows, and a shorter last
+    chunk is taken as the LAST `chunk` rows (it overlaps its predecessor, whose rows get the same values again)."""
+    if kind not in (EVAL_CE, EVAL_KL) or not 0 <= smoothing < 1:
+        raise ValueError(f"fused_linear_score: kind must be 0 (CE) or 1 (KL) and smoothing in [0, 1), got {kind}, {smoothing}")
+    D, V = hidden.shape[-1], weight.shape[0]
+    h2, lab = hidden.reshape(-1, D), labels.reshape(-1).contiguous()
+    N, dev = h2.shape[0], h2.device
+    hip = _kl_acc_gate(h2, lab, weight, bias)
+    if chunk is None:
+        chunk = EVAL_CHUNK_ROWS or auto_chunk(N, V, h2.element_size() if hip else 8)
+    if hip:
+        chunk = -(-max(1, chunk) // SCORE_CHUNK_ALIGN) * SCORE_CHUNK_ALIGN
+    chunk = max(1, min(chunk, N))
+    starts = list(range(0, N, chunk))
+    loss_rows = torch.empty(N, dtype=torch.float32, device=dev)
+    correct_rows = torch.empty(N, dtype=torch.int32, device=dev)
+    if hip:
+        if CHECK_LABELS:
+            bad = (lab != ignore_index) & ((lab < 0) | (lab >= V))
+            assert not bool(bad.any()), f"labels outside [0, {V}) that are not ignore_index={ignore_index}"
+        ld = -(-V // 8) * 8
+        buf = torch.empty(chunk, ld, dtype=h2.dtype, device=dev)
+        wt = weight.t()
+        starts[-1] = N - chunk   # every GEMM call has `chunk` rows (N rows when one chunk holds them all)
+    for s in starts:
+        h, lb = h2[s:s + chunk], lab[s:s + chunk]
+        rows = h.shape[0]
+        if hip:
+            out = buf[:rows, :V]   # rows of ld elements: the GEMM writes the V logits, the kernel never reads the rest
+            if bias is None:
+                torch.mm(h, wt, out=out)
+            else:
+                torch.addmm(bias, h, wt, out=out)
+            _lib.call("rwkv7_head_eval_bf16", buf, rows, V, ld, buf, lb, ignore_index, kind, float(smoothing), loss_rows[s:s + rows],
+                      correct_rows[s:s + rows], None)
+            EVAL_HITS[0] += 1
+        else:
+            per, ok = _eval_rows_torch(F.linear(h, weight, bias), lb, ignore_index, kind, smoothing)
+            loss_rows[s:s + rows] = per
+            correct_rows[s:s + rows] = ok
+    return loss_rows, correct_rows, lab, hip
+
+
+def _seq_scores_torch(seq_start, loss_rows, correct_rows, labels, ignore_index):
+    """rwkv7_seq_scores_f32's definitions in torch, sequence by sequence (seq_start is read on the host): the fp64 sum in row order
+    (a cumulative sum), the counts, the maximum (NaN largest) and the first row that attains it."""
+    st = seq_start.tolist()
+    n_seq, dev = len(st) - 1, loss_rows.device
+    loss_sum = torch.zeros(n_seq, dtype=torch.float64, device=dev)
+    tokens = torch.zeros(n_seq, dtype=torch.int64, device=dev)
+    correct = torch.zeros(n_seq, dtype=torch.int64, device=dev)
+    worst_loss = torch.zeros(n_seq, dtype=torch.float32, device=dev)
+    worst_row = torch.full((n_seq,), -1, dtype=torch.int64, device=dev)
+    valid = labels != ignore_index
+    for s in range(n_seq):
+        idx = valid[st[s]:st[s + 1]].nonzero().squeeze(1)   # rows of the sequence that count, relative to its start
+        if idx.numel() == 0:
+            continue
+        v = loss_rows[st[s]:st[s + 1]][idx]
+        loss_sum[s] = v.double().cumsum(0)[-1]
+        tokens[s] = idx.numel()
+        correct[s] = correct_rows[st[s]:st[s + 1]][idx].sum()
+        worst_loss[s] = v.max()
+        worst_row[s] = idx[v.argmax()]   # torch.argmax: the lowest index among the maxima, a NaN counts as the largest
+    return loss_sum, tokens, correct, worst_loss, worst_row
+
+
+@torch.no_grad()
+def fused_linear_score(hidden, labels, weight, bias, ignore_index, kind, smoothing=0.0, *, seq_start, chunk=None):
+    """Per-sequence scores of a head: hidden [..., D], labels [...] (N rows once flattened), seq_start int64 [n_seq + 1] (non-decreasing
+    row offsets into the flattened rows; sequence s owns rows seq_start[s] .. seq_start[s + 1] - 1; values are clamped to [0, N]) ->
+    five device tensors of length n_seq over each sequence's rows with label != ignore_index:
+      loss_sum fp64 (the sum of the head's per-row loss, the rows and formulas of fused_linear_eval), tokens int64, correct int64,
+      worst_loss fp32 (the largest row loss), worst_row int64 (the first row, relative to the sequence's start, that attains it);
+      a sequence without such a row gives 0, 0, 0, 0.0, -1.
+    No autograd.  bf16 CUDA hidden / weight / bias with int64 labels: the chunked head GEMM and rwkv7_head_eval_bf16 of
+    fused_linear_eval, each chunk writing its slice of full-length loss_rows / correct_rows (16 bytes per row with the labels; the
+    logits are never kept), then ONE rwkv7_seq_scores_f32 launch whose summation order depends on a sequence's length alone -- no host
+    synchronisation.  Anything else: the same definitions in torch (_eval_rows_torch per chunk, then a row-order fp64 sum and a
+    max / first argmax per sequence; this route reads seq_start on the host).  chunk: as in fused_linear_eval; on the HIP route it is
+    rounded up to a multiple of 64 rows and the last chunk overlaps its predecessor (_score_rows), so that the outputs are
+    bit-identical for every chunk size as long as the library GEMM gives a row the same logits whatever the number of rows in the
+    call -- observed from 16 rows per call on, not promised by the library."""
+    if seq_start is None or seq_start.dim() != 1 or seq_start.numel() < 2:
+        raise ValueError("fused_linear_score: seq_start must be a 1-D tensor of n_seq + 1 >= 2 row offsets")
+    loss_rows, correct_rows, lab, hip = _score_rows(hidden, labels, weight, bias, ignore_index, kind, smoothing, chunk)
+    N, dev = lab.numel(), lab.device
+    st = seq_start.to(device=dev, dtype=torch.int64).clamp(0, N).contiguous()   # the kernel checks no range: keep every read inside
+    if not hip:
+        return _seq_scores_torch(st, loss_rows, correct_rows, lab, ignore_index)
+    n_seq = st.numel() - 1
+    loss_sum = torch.empty(n_seq, dtype=torch.float64, device=dev)
+    tokens, correct, worst_row = (torch.empty(n_seq, dtype=torch.int64, device=dev) for _ in range(3))
+    worst_loss = torch.empty(n_seq, dtype=torch.float32, device=dev)
+    _lib.call("rwkv7_seq_scores_f32", loss_rows, n_seq, st, loss_rows, correct_rows, lab, ignore_index, loss_sum, tokens, correct,
+              worst_loss, worst_row)
+    SCORE_HITS[0] += 1
+    return loss_sum, tokens, correct, worst_loss, worst_row
+
+
+def padded_seq_start(B, T, device):
+    """seq_start of a padded [B, T] batch flattened row-major: sequence b is the rows b T .. (b + 1) T - 1."""
+    return torch.arange(B + 1, dtype=torch.int64, device=device) * T

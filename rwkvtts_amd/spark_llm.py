@@ -20,7 +20,8 @@ import torch.nn.functional as F
 
 from .backbone import Cache, Linear, ModelOutput, RWKV7Config, RWKV7Model
 from .hf_api import HFModelMixin
-from .losses import EVAL_CE, eval_mode, fused_linear_cross_entropy, fused_linear_eval
+from .losses import (EVAL_CE, SCORE_KEYS, eval_mode, fused_linear_cross_entropy, fused_linear_eval, fused_linear_score,
+                     padded_seq_start)
 
 
 class RWKV7SpeechConfig(RWKV7Config):
@@ -115,19 +116,46 @@ class RWKV7ForSpeech(HFModelMixin, nn.Module):
         Labels as in forward: shifted by one here, -100 ignored, packed rows past cu_seqlens[-1] ignored unless strict_reference_loss.
         Returns device tensors: loss (the training loss' definition: mean CE over the valid positions), loss_sum fp64 [1], tokens and
         correct int64 [1], denom [1] (what loss_sum is divided by: tokens)."""
-        for k in ("past_key_values", "use_cache", "output_attentions", "output_hidden_states", "return_dict", "logits_to_keep"):
-            kwargs.pop(k, None)
         with eval_mode(self):
-            hidden = self.model(input_ids=input_ids, attention_mask=attention_mask, inputs_embeds=inputs_embeds, **kwargs)[0]
-            ignore_index = getattr(self.criterion, "ignore_index", -100)
-            labels = labels.to(hidden.device)
-            labels = torch.cat((labels[..., 1:], torch.full_like(labels[:, :1], ignore_index)), 1)
-            cu = kwargs.get("cu_seqlens")
-            if cu is not None and not getattr(self.config, "strict_reference_loss", False):   # see forward
-                pos = torch.arange(labels.shape[1], device=labels.device)
-                labels = torch.where(pos.unsqueeze(0) >= cu[-1].to(labels.device), torch.full_like(labels, ignore_index), labels)
+            hidden, labels, ignore_index, _ = self._scored_rows(input_ids, attention_mask, inputs_embeds, labels, kwargs)
             loss_sum, tokens, correct = fused_linear_eval(hidden, labels, self.lm_head.weight, self.lm_head.bias, ignore_index, EVAL_CE)
         return dict(loss=(loss_sum / tokens).float().reshape(()), loss_sum=loss_sum, tokens=tokens, correct=correct, denom=tokens)
+
+    def _scored_rows(self, input_ids, attention_mask, inputs_embeds, labels, kwargs):
+        """What eval_metrics and score evaluate (call inside eval_mode): the backbone's hidden states, forward's shifted labels, the
+        ignore index and cu_seqlens (None for a padded batch)."""
+        for k in ("past_key_values", "use_cache", "output_attentions", "output_hidden_states", "return_dict", "logits_to_keep"):
+            kwargs.pop(k, None)
+        hidden = self.model(input_ids=input_ids, attention_mask=attention_mask, inputs_embeds=inputs_embeds, **kwargs)[0]
+        ignore_index = getattr(self.criterion, "ignore_index", -100)
+        labels = labels.to(hidden.device)
+        labels = torch.cat((labels[..., 1:], torch.full_like(labels[:, :1], ignore_index)), 1)
+        cu = kwargs.get("cu_seqlens")
+        if cu is not None and not getattr(self.config, "strict_reference_loss", False):   # see forward
+            pos = torch.arange(labels.shape[1], device=labels.device)
+            labels = torch.where(pos.unsqueeze(0) >= cu[-1].to(labels.device), torch.full_like(labels, ignore_index), labels)
+        return hidden, labels, ignore_index, cu
+
+    def score(self, input_ids=None, attention_mask=None, inputs_embeds=None, labels=None, **kwargs):
+        """Per-utterance scores of one batch (eval_metrics' batch kwargs, rows and shifted labels; the backbone once, eval mode, no
+        autograd, the previous mode restored): a dict of device tensors of length n_seq -- loss_sum fp64 (teacher-forced CE summed over
+        the utterance's valid positions), tokens and correct int64, worst_loss fp32 and worst_row int64 (the first position, relative to
+        the utterance's first row, with the largest loss; -1 without a valid position); losses.fused_linear_score.
+        Padded [B, T]: utterance b is batch row b.  Packed cu_seqlens: utterance s is the rows cu_seqlens[s] .. cu_seqlens[s + 1] - 1 of
+        the packed row, labels shifted across the whole row as in forward (the builder's own -100 at a boundary decides what the last
+        position of an utterance counts); with strict_reference_loss the rows past cu_seqlens[-1], which eval_metrics then counts,
+        form one more (possibly empty) utterance at the end.  Summed over the utterances, tokens and correct equal eval_metrics'."""
+        with eval_mode(self):
+            hidden, labels, ignore_index, cu = self._scored_rows(input_ids, attention_mask, inputs_embeds, labels, kwargs)
+            B, T = labels.shape
+            if cu is None:
+                seq_start = padded_seq_start(B, T, hidden.device)
+            else:
+                seq_start = cu.to(device=hidden.device, dtype=torch.int64)
+                if getattr(self.config, "strict_reference_loss", False):
+                    seq_start = torch.cat((seq_start, torch.full_like(seq_start[:1], B * T)))
+            out = fused_linear_score(hidden, labels, self.lm_head.weight, self.lm_head.bias, ignore_index, EVAL_CE, seq_start=seq_start)
+        return dict(zip(SCORE_KEYS, out))
 
     def prepare_inputs_for_generation(self, input_ids=None, past_key_values=None, attention_mask=None,
                                       inputs_embeds=None, use_cache=True, logits_to_keep=None, **kwargs):

@@ -871,6 +871,28 @@ class DataParallelTrainer:
                                       tokens=[int(t) for t in tokens])
         return out
 
+    def score(self, batches):
+        """Per-utterance scores (DESIGN.md section 6.4).  batches: an iterable of batch dicts, this rank's own (at least one);
+        model.score per batch, the outputs concatenated on the device along the utterance axis, then ONE host read.  No collective:
+        every rank gets the scores of what it submitted.  Returns a dict of numpy arrays with one entry per utterance in submission
+        order ([channels, utterances] for a multi-channel head): loss_sum fp64, tokens, correct, worst_loss, worst_row (-1: no valid
+        position) and mean_loss = loss_sum / max(tokens, 1).
+        Like evaluate, it moves nothing of the run (eval mode under no_grad: no dropout draw, no gradient hook): parameters, masters,
+        moments, step_idx, the learning rate, the flat gradient buffer, the NaN flag, the reducer's bucket bookkeeping, the host and
+        device random streams and the train / eval mode are what they were -- k steps, score, m steps is bit-identical to k + m steps.
+        Not allowed inside an accumulation window."""
+        if self._acc_count != 0:
+            raise RuntimeError(f"score inside an accumulation window ({self._acc_count} micro-batches pending): call step() first")
+        per = [self.model.score(**batch) for batch in batches]
+        if not per:
+            raise ValueError("score needs at least one batch")
+        keys = list(per[0])
+        # one device tensor [5, ..., utterances] in fp64 (counts and rows are exact up to 2^53, an fp32 loss converts exactly): one read
+        flat = torch.stack([torch.cat([p[k].double() for p in per], dim=-1) for k in keys]).cpu().numpy()
+        out = {k: flat[i] if k == "loss_sum" else flat[i].astype("float32" if k == "worst_loss" else "int64") for i, k in enumerate(keys)}
+        out["mean_loss"] = out["loss_sum"] / out["tokens"].clip(min=1)
+        return out
+
     # ---- state digest and checkpoints (DESIGN.md section 6.2) ------------------------------------------------------------------
     def _own_range(self):
         """[lo, hi) of the flat buffers this rank is the authority on: its slab in shard mode, everything otherwise."""

@@ -20,7 +20,8 @@ import torch.nn.functional as F
 
 from .backbone import Cache, ModelOutput, RWKV7Config, RWKV7Model
 from .hf_api import HFModelMixin
-from .losses import EVAL_CE, eval_mode, fused_linear_cross_entropy, fused_linear_eval
+from .losses import (EVAL_CE, SCORE_KEYS, eval_mode, fused_linear_cross_entropy, fused_linear_eval, fused_linear_score,
+                     padded_seq_start)
 
 
 class RWKV7XYConfig(RWKV7Config):
@@ -129,6 +130,20 @@ class RWKV7XYLM(HFModelMixin, nn.Module):
                                      smoothing=self.config.lsm_weight) for i in range(self.config.num_channels)]
         loss_sum, tokens, correct = (torch.cat(t) for t in zip(*per))
         return dict(loss=(loss_sum / tokens).sum().float(), loss_sum=loss_sum, tokens=tokens, correct=correct, denom=tokens)
+
+    def score(self, input_ids=None, attention_mask=None, inputs_embeds=None, labels=None, **kwargs):
+        """Per-utterance scores of one batch (eval_metrics' batch kwargs, rows and labels; the backbone once, eval mode, no autograd,
+        the previous mode restored): utterance b is batch row b, one losses.fused_linear_score call per channel with the heads'
+        label_smoothing, stacked to [C, B] device tensors -- loss_sum fp64, tokens and correct int64, worst_loss fp32, worst_row int64
+        (the first frame of the utterance with the channel's largest loss; -1 where the channel has no valid frame)."""
+        with eval_mode(self):
+            if inputs_embeds is None and input_ids is not None:
+                inputs_embeds = self.embed(input_ids)
+            hidden = self.model(inputs_embeds=inputs_embeds, attention_mask=attention_mask)[0]
+            seq_start = padded_seq_start(hidden.shape[0], hidden.shape[1], hidden.device)
+            per = [fused_linear_score(hidden, labels[:, :, i].to(hidden.device), self.heads[i].weight, self.heads[i].bias, -100, EVAL_CE,
+                                      smoothing=self.config.lsm_weight, seq_start=seq_start) for i in range(self.config.num_channels)]
+        return {k: torch.stack(t) for k, t in zip(SCORE_KEYS, zip(*per))}
 
     def is_audio_token(self, token_id):
         c = self.config
