@@ -805,17 +805,20 @@ int rwkv7_ce_fwd_bwd_ld_bf16(long rows, int V, long ld, void *logits, const long
     if (!(label_smoothing >= 0.f && label_smoothing < 1.f)) return RWKV7_EINVAL;
     return rwkv7::ce_fwd_bwd(rows, V, ld, logits, labels, ignore_index, scale, loss_rows, label_smoothing, (hipStream_t)stream);
 }
+// the entropy constant of the label-smoothing KL's target distribution (1 - s on the label, s / (V - 1) elsewhere), sum_j t_j ln t_j
+// with 0 ln 0 = 0 (what F.kl_div gives for a zero target)
+static float kl_entropy_const(float smoothing, int V) {
+    const double s = (double)smoothing;
+    return (float)((1.0 - s) * log(1.0 - s) + (s > 0.0 ? s * log(s / (double)(V - 1)) : 0.0));
+}
 int rwkv7_kl_acc_fwd_bwd_bf16(long rows, int V, long ld, const void *logits, void *dlogits, const long *labels, long ignore_index,
                               float smoothing, float scale, float *loss_rows, int *correct_rows, rwkv7_stream_t stream) {
     if (rows <= 0 || V < 2 || ld < V ||
         any_null({logits, (const void *)dlogits, (const void *)labels, (const void *)loss_rows, (const void *)correct_rows}))
         return RWKV7_EINVAL;
     if (!(smoothing >= 0.f && smoothing < 1.f)) return RWKV7_EINVAL;
-    // the entropy constant of the target distribution, sum_j t_j ln t_j with 0 ln 0 = 0 (what F.kl_div gives for a zero target)
-    const double s = (double)smoothing;
-    const double C = (1.0 - s) * log(1.0 - s) + (s > 0.0 ? s * log(s / (double)(V - 1)) : 0.0);
-    return rwkv7::kl_acc_fwd_bwd(rows, V, ld, logits, dlogits, labels, ignore_index, smoothing, (float)C, scale, loss_rows, correct_rows,
-                                 (hipStream_t)stream);
+    return rwkv7::kl_acc_fwd_bwd(rows, V, ld, logits, dlogits, labels, ignore_index, smoothing, kl_entropy_const(smoothing, V), scale,
+                                 loss_rows, correct_rows, (hipStream_t)stream);
 }
 int rwkv7_head_eval_bf16(long rows, int V, long ld, const void *logits, const long *labels, long ignore_index, int kind, float smoothing,
                          float *loss_rows, int *correct_rows, int *argmax_rows, rwkv7_stream_t stream) {
@@ -823,10 +826,8 @@ int rwkv7_head_eval_bf16(long rows, int V, long ld, const void *logits, const lo
         any_null({logits, (const void *)labels, (const void *)loss_rows, (const void *)correct_rows}))
         return RWKV7_EINVAL;
     if (!(smoothing >= 0.f && smoothing < 1.f)) return RWKV7_EINVAL;
-    // kind 1: the entropy constant of the target distribution, exactly as rwkv7_kl_acc_fwd_bwd_bf16 forms it
-    const double s = (double)smoothing;
-    const double C = kind == 1 ? (1.0 - s) * log(1.0 - s) + (s > 0.0 ? s * log(s / (double)(V - 1)) : 0.0) : 0.0;
-    return rwkv7::head_eval(rows, V, ld, logits, labels, ignore_index, kind, smoothing, (float)C, loss_rows, correct_rows, argmax_rows,
+    const float C = kind == 1 ? kl_entropy_const(smoothing, V) : 0.f;
+    return rwkv7::head_eval(rows, V, ld, logits, labels, ignore_index, kind, smoothing, C, loss_rows, correct_rows, argmax_rows,
                             (hipStream_t)stream);
 }
 int rwkv7_seq_scores_f32(long n_seq, const long *seq_start, const float *loss_rows, const int *correct_rows, const long *labels,

@@ -1125,266 +1125,6 @@ int adamw_step(long n, float *p32, const void *g16, float *m, float *v, void *p1
 }
 
 // ------------------------------------------------------------------------------------------------------
-// softmax cross-entropy of one chunk of head logits, forward and backward in one kernel
-// (model/llm/spark_llm.py:146-160 uses rwkvfla's FusedLinearCrossEntropyLoss; the chunking over tokens lives in
-// rwkvtts_amd/losses.py).  One wave per row: online max / sum-of-exp over the row (bf16 logits as the GEMM wrote them,
-// no fp32 copy), then the row is rewritten IN PLACE with d loss / d logits = (softmax - onehot(label)) * scale, or 0
-// for ignored rows; loss_rows[row] = (logsumexp - logit[label]) * valid.  Two reads (the second from L2) + one write.
-// ------------------------------------------------------------------------------------------------------
-// Round 4: the row is walked in 16-byte pieces (8 logits per lane and load; V is odd for the Spark head -- 8 193 -- so a row starts
-// on any 2-byte boundary: up to 7 single elements in front of the first aligned piece and behind the last), one running-max rescale per
-// piece instead of one per element (9 exponentials per 8 logits instead of 16), the gradients leave as 16-byte stores through
-// v_cvt_pk_bf16_f32.  The first form read and wrote 2 bytes per lane and instruction: 98 us per 4 096 x 8 193 chunk.
-// label smoothing ls (torch.nn.CrossEntropyLoss(label_smoothing), xy_llm.py:233-240): loss = (1 - ls)(lse - x[label]) + ls (lse - mean x),
-// d loss / d x_j = softmax_j - ls / V - (1 - ls) [j == label]; ls = 0 is the plain form, bit for bit what it was.
-// ld: elements between rows (>= V; round 6: the Spark head's logits live in a buffer padded to a multiple of 256 columns, so rows are 16-byte
-// aligned and the head GEMMs see aligned leading dimensions; the padding columns are neither read nor written here)
-__global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(long rows, int V, long ld, bf16_t *__restrict__ logits, const long *__restrict__ labels,
-                                                         long ignore_index, float scale, float *__restrict__ loss_rows, float ls) {
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    uint16_t *x = reinterpret_cast<uint16_t *>(logits) + row * ld;
-    const long lab = labels[row];
-    const bool valid = lab != ignore_index;
-    // [0, head) singles, [head, head + 8 nv) aligned pieces, [head + 8 nv, V) singles
-    int head = (int)(((16 - (reinterpret_cast<uintptr_t>(x) & 15)) & 15) >> 1);
-    head = head < V ? head : V;
-    const int nv = (V - head) >> 3, tail0 = head + 8 * nv;
-    const uint4 *xv = reinterpret_cast<const uint4 *>(x + head);
-    float m = -INFINITY, ssum = 0.f, xsum = 0.f;   // xsum: sum of the logits (the smoothing term)
-    auto one = [&](float v) {
-        const float mn = fmaxf(m, v);
-        ssum = ssum * __expf(m - mn) + __expf(v - mn);
-        m = mn;
-        xsum += v;
-    };
-    if (lane < head) one(bf2f(x[lane]));
-    if (tail0 + lane < V) one(bf2f(x[tail0 + lane]));
-    for (int i = lane; i < nv; i += 64) {
-        const uint4 r = xv[i];
-        float f[8];
-        f[0] = __uint_as_float(r.x << 16); f[1] = __uint_as_float(r.x & 0xffff0000u);
-        f[2] = __uint_as_float(r.y << 16); f[3] = __uint_as_float(r.y & 0xffff0000u);
-        f[4] = __uint_as_float(r.z << 16); f[5] = __uint_as_float(r.z & 0xffff0000u);
-        f[6] = __uint_as_float(r.w << 16); f[7] = __uint_as_float(r.w & 0xffff0000u);
-        float mx = fmaxf(fmaxf(fmaxf(f[0], f[1]), fmaxf(f[2], f[3])), fmaxf(fmaxf(f[4], f[5]), fmaxf(f[6], f[7])));
-        const float mn = fmaxf(m, mx);
-        float e = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            e += __expf(f[j] - mn);
-            xsum += f[j];
-        }
-        ssum = ssum * __expf(m - mn) + e;
-        m = mn;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        xsum += __shfl_xor(xsum, off);
-        const float mo = __shfl_xor(m, off), so = __shfl_xor(ssum, off);
-        const float mn = fmaxf(m, mo);
-        // a lane that saw no element carries (m, ssum) = (-inf, 0): exp(-inf - mn) = 0 keeps it out, and two such lanes give exp(nan) * 0
-        ssum = (m == mn ? ssum : ssum * __expf(m - mn)) + (mo == mn ? so : so * __expf(mo - mn));
-        m = mn;
-    }
-    const float lse = m + __logf(ssum);
-    if (lane == 0) {
-        const float nll = lse - bf2f(x[lab < 0 ? 0 : lab]);
-        loss_rows[row] = valid ? (ls > 0.f ? (1.f - ls) * nll + ls * (lse - xsum / (float)V) : nll) : 0.f;
-    }
-    const float sc = valid ? scale : 0.f, hit = 1.f - ls, off_all = ls / (float)V;
-    auto grad1 = [&](int j) {
-        const float p = __expf(bf2f(x[j]) - lse) - off_all - (j == lab ? hit : 0.f);
-        x[j] = (uint16_t)pk_bf16(p * sc, 0.f);
-    };
-    if (lane < head) grad1(lane);
-    if (tail0 + lane < V) grad1(tail0 + lane);
-    uint4 *xw = reinterpret_cast<uint4 *>(x + head);
-    const int labv = (int)lab - head;   // position of the label among the aligned elements (anything outside [0, 8 nv): no hit)
-    for (int i = lane; i < nv; i += 64) {
-        const uint4 r = xv[i];
-        float f[8];
-        f[0] = __uint_as_float(r.x << 16); f[1] = __uint_as_float(r.x & 0xffff0000u);
-        f[2] = __uint_as_float(r.y << 16); f[3] = __uint_as_float(r.y & 0xffff0000u);
-        f[4] = __uint_as_float(r.z << 16); f[5] = __uint_as_float(r.z & 0xffff0000u);
-        f[6] = __uint_as_float(r.w << 16); f[7] = __uint_as_float(r.w & 0xffff0000u);
-#pragma unroll
-        for (int j = 0; j < 8; j++) f[j] = (__expf(f[j] - lse) - off_all - (8 * i + j == labv ? hit : 0.f)) * sc;
-        xw[i] = make_uint4(pk_bf16(f[0], f[1]), pk_bf16(f[2], f[3]), pk_bf16(f[4], f[5]), pk_bf16(f[6], f[7]));
-    }
-}
-
-int ce_fwd_bwd(long rows, int V, long ld, void *logits, const long *labels, long ignore_index, float scale, float *loss_rows,
-               float label_smoothing, hipStream_t st) {
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(ce_fwd_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, rows, V, ld, (bf16_t *)logits, labels,
-                       ignore_index, scale, loss_rows, label_smoothing);
-    return (int)hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------------------
-// label-smoothing KL loss + accuracy of one chunk of Cosy head logits, forward and backward in one kernel
-// (third_party/cosyvoice/transformer/label_smoothing_loss.py:68-96 + utils/common.py:76-95; the chunking over tokens lives in
-// rwkvtts_amd/losses.py).  Target distribution t: 1 - s on the label, s / (V - 1) elsewhere.  Per valid row
-//   loss = C - (1 - s)(x_y - lse) - s/(V-1) ((sum_j x_j - x_y) - (V-1) lse),  C = (1-s) ln(1-s) + s ln(s/(V-1))  (host, double -> float)
-//   dx_j = (exp(x_j - lse) - t_j) * scale        (one bf16 rounding of the fp32 value)
-//   correct = [lowest index among the row's maxima == y]                       (torch.argmax's tie rule on the CPU)
-// ignored rows: 0 everywhere.  ONE 256-thread workgroup per row (V = 6562: 820 16-byte pieces, 3.2 per thread).  REG: V <= 8192 and
-// the row is kept in registers between the reduction and the gradient (one read, one write); otherwise the second pass reads the row again
-// (from L2: a 16 KB+ row a workgroup has just walked).  Every thread reads in the second pass exactly the elements it then writes, and the
-// label's logit is read before the block-wide reduction, so dx may be x (in place).
-// A row is walked as [0, head) singles, nv 16-byte pieces, [tail0, V) singles -- rows of an unpadded V = 6562 buffer start on 4-byte
-// boundaries.  vec = 0 (x and dx differ modulo 16 bytes): head = V, everything goes through the 2-byte loops.  Columns V .. ld - 1 are
-// neither read nor written.  All reductions in fp32 from the bf16 logits (running maximum subtracted before exp); the closing arithmetic
-// of the row's loss runs in double on one thread.
-// ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void unpack8(const uint4 r, float *f) {
-    f[0] = __uint_as_float(r.x << 16); f[1] = __uint_as_float(r.x & 0xffff0000u);
-    f[2] = __uint_as_float(r.y << 16); f[3] = __uint_as_float(r.y & 0xffff0000u);
-    f[4] = __uint_as_float(r.z << 16); f[5] = __uint_as_float(r.z & 0xffff0000u);
-    f[6] = __uint_as_float(r.w << 16); f[7] = __uint_as_float(r.w & 0xffff0000u);
-}
-
-template <bool REG>
-__global__ __launch_bounds__(256) void kl_acc_fwd_bwd_kernel(long rows, int V, long ld, const uint16_t *logits, uint16_t *dlogits,
-                                                             const long *__restrict__ labels, long ignore_index, float s, float C, float scale,
-                                                             float *__restrict__ loss_rows, int *__restrict__ correct_rows, int vec) {
-    __shared__ float red_m[4], red_s[4], red_x[4];
-    __shared__ int red_i[4];
-    const int tid = threadIdx.x, wave = tid >> 6;
-    for (long row = blockIdx.x; row < rows; row += gridDim.x) {
-        const uint16_t *x = logits + row * ld;
-        uint16_t *dx = dlogits + row * ld;
-        const long lab = labels[row];
-        int head = vec ? (int)(((16 - (reinterpret_cast<uintptr_t>(x) & 15)) & 15) >> 1) : V;
-        head = head < V ? head : V;
-        const int nv = (V - head) >> 3, tail0 = head + 8 * nv;
-        const uint4 *xv = reinterpret_cast<const uint4 *>(x + head);
-        uint4 *dv = reinterpret_cast<uint4 *>(dx + head);
-        if (lab == ignore_index) {   // the whole workgroup takes this branch: no barrier is skipped by a part of it
-            for (int j = tid; j < head; j += 256) dx[j] = 0;
-            for (int j = tail0 + tid; j < V; j += 256) dx[j] = 0;
-            for (int i = tid; i < nv; i += 256) dv[i] = make_uint4(0u, 0u, 0u, 0u);
-            if (tid == 0) {
-                loss_rows[row] = 0.f;
-                correct_rows[row] = 0;
-            }
-            continue;
-        }
-        const float xy = bf2f(x[lab]);   // before any store of this row
-        float m = -INFINITY, ssum = 0.f, xsum = 0.f;
-        int best = 0x7fffffff;           // lowest index at which the running maximum m was seen
-        auto one = [&](float v, int j) {
-            best = (v > m || (v == m && j < best)) ? j : best;
-            const float mn = fmaxf(m, v);
-            ssum = ssum * __expf(m - mn) + __expf(v - mn);
-            m = mn;
-            xsum += v;
-        };
-        for (int j = tid; j < head; j += 256) one(bf2f(x[j]), j);
-        for (int j = tail0 + tid; j < V; j += 256) one(bf2f(x[j]), j);
-        uint4 r[4];
-        auto piece = [&](const uint4 q, int i) {
-            float f[8];
-            unpack8(q, f);
-            const float mx = fmaxf(fmaxf(fmaxf(f[0], f[1]), fmaxf(f[2], f[3])), fmaxf(fmaxf(f[4], f[5]), fmaxf(f[6], f[7])));
-            if (mx > m || (mx == m && head + 8 * i < best)) {
-#pragma unroll
-                for (int j = 7; j >= 0; j--) best = f[j] == mx ? head + 8 * i + j : best;
-            }
-            const float mn = fmaxf(m, mx);
-            float e = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                e += __expf(f[j] - mn);
-                xsum += f[j];
-            }
-            ssum = ssum * __expf(m - mn) + e;
-            m = mn;
-        };
-        if (REG) {
-#pragma unroll
-            for (int k = 0; k < 4; k++)
-                if (tid + 256 * k < nv) r[k] = xv[tid + 256 * k];
-#pragma unroll
-            for (int k = 0; k < 4; k++)
-                if (tid + 256 * k < nv) piece(r[k], tid + 256 * k);
-        } else {
-            for (int i = tid; i < nv; i += 256) piece(xv[i], i);
-        }
-        // (m, ssum, xsum, best) over the wave, then over the four waves.  A thread that saw no element carries (-inf, 0, 0, INT_MAX):
-        // exp(-inf - mn) = 0 keeps it out, and two such threads must not form exp(nan) * 0
-        auto merge = [&](float mo, float so, float xo, int bo) {
-            best = (mo > m || (mo == m && bo < best)) ? bo : best;
-            const float mn = fmaxf(m, mo);
-            ssum = (m == mn ? ssum : ssum * __expf(m - mn)) + (mo == mn ? so : so * __expf(mo - mn));
-            m = mn;
-            xsum += xo;
-        };
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const float mo = __shfl_xor(m, off), so = __shfl_xor(ssum, off), xo = __shfl_xor(xsum, off);
-            const int bo = __shfl_xor(best, off);
-            merge(mo, so, xo, bo);
-        }
-        if ((tid & 63) == 0) {
-            red_m[wave] = m; red_s[wave] = ssum; red_x[wave] = xsum; red_i[wave] = best;
-        }
-        __syncthreads();
-        m = red_m[0]; ssum = red_s[0]; xsum = red_x[0]; best = red_i[0];
-#pragma unroll
-        for (int w = 1; w < 4; w++) merge(red_m[w], red_s[w], red_x[w], red_i[w]);
-        __syncthreads();   // red_* are free for the next row
-        const float lse = m + __logf(ssum);
-        if (tid == 0) {
-            const double L = (double)m + log((double)ssum), dxy = (double)xy, ds = (double)s, vm1 = (double)(V - 1);
-            double loss = -(1.0 - ds) * (dxy - L);
-            if (s > 0.f) loss += (double)C - ds / vm1 * (((double)xsum - dxy) - vm1 * L);
-            loss_rows[row] = (float)loss;
-            correct_rows[row] = best == (int)lab ? 1 : 0;
-        }
-        const float hit = 1.f - s, off_t = s / (float)(V - 1);
-        auto grad1 = [&](int j) {
-            const float g = (__expf(bf2f(x[j]) - lse) - (j == lab ? hit : off_t)) * scale;
-            dx[j] = (uint16_t)pk_bf16(g, 0.f);
-        };
-        for (int j = tid; j < head; j += 256) grad1(j);
-        for (int j = tail0 + tid; j < V; j += 256) grad1(j);
-        const int labv = (int)lab - head;   // position of the label among the aligned elements (outside [0, 8 nv): no hit)
-        auto gpiece = [&](const uint4 q, int i) {
-            float f[8];
-            unpack8(q, f);
-#pragma unroll
-            for (int j = 0; j < 8; j++) f[j] = (__expf(f[j] - lse) - (8 * i + j == labv ? hit : off_t)) * scale;
-            dv[i] = make_uint4(pk_bf16(f[0], f[1]), pk_bf16(f[2], f[3]), pk_bf16(f[4], f[5]), pk_bf16(f[6], f[7]));
-        };
-        if (REG) {
-#pragma unroll
-            for (int k = 0; k < 4; k++)
-                if (tid + 256 * k < nv) gpiece(r[k], tid + 256 * k);
-        } else {
-            for (int i = tid; i < nv; i += 256) gpiece(xv[i], i);
-        }
-    }
-}
-
-int kl_acc_fwd_bwd(long rows, int V, long ld, const void *logits, void *dlogits, const long *labels, long ignore_index, float smoothing,
-                   float C, float scale, float *loss_rows, int *correct_rows, hipStream_t st) {
-    (void)hipGetLastError();
-    // 16-byte pieces need x and dx rows that agree modulo 16 bytes (same ld: the two base pointers decide it for every row)
-    const int vec = ((reinterpret_cast<uintptr_t>(logits) ^ reinterpret_cast<uintptr_t>(dlogits)) & 15) == 0;
-    const unsigned grid = (unsigned)(rows < (1L << 20) ? rows : (1L << 20));
-    if (vec && V <= 8192)
-        hipLaunchKernelGGL(kl_acc_fwd_bwd_kernel<true>, dim3(grid), dim3(256), 0, st, rows, V, ld, (const uint16_t *)logits,
-                           (uint16_t *)dlogits, labels, ignore_index, smoothing, C, scale, loss_rows, correct_rows, vec);
-    else
-        hipLaunchKernelGGL(kl_acc_fwd_bwd_kernel<false>, dim3(grid), dim3(256), 0, st, rows, V, ld, (const uint16_t *)logits,
-                           (uint16_t *)dlogits, labels, ignore_index, smoothing, C, scale, loss_rows, correct_rows, vec);
-    return (int)hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------------------
 // out[n] (bf16) = (accumulate ? out[n] : 0) + sum_s parts[s][n] (fp32): the last step of the split weight gradient
 // (fused.wgrad_splitk) written straight into the gradient buffer -- replaces reduce + cast + accumulate launches
 // ------------------------------------------------------------------------------------------------------

@@ -29,6 +29,21 @@ PADDED_HEAD = os.environ.get("RWKV7_PADDED_HEAD", "1") == "1"   # A/B switch (se
 PADDED_HEAD_HITS = [0]
 
 
+def _check_labels(labels, V, ignore_index):
+    """RWKV7_CHECK_LABELS=1: labels must be < V or == ignore_index, since the head kernels index x[label] unchecked (one host sync per
+    call, debugging only)."""
+    if CHECK_LABELS:
+        bad = (labels != ignore_index) & ((labels < 0) | (labels >= V))
+        assert not bool(bad.any()), f"labels outside [0, {V}) that are not ignore_index={ignore_index}"
+
+
+def _hip_gate(x, labels, *more):
+    """The HIP head kernels apply: bf16 CUDA x (hidden states or logits) and every tensor of `more` (weight, bias) that is not None,
+    int64 labels, and the A/B switch on."""
+    return (HIP_CE and x.is_cuda and x.dtype == torch.bfloat16 and labels.dtype == torch.int64
+            and all(m is None or (m.is_cuda and m.dtype == torch.bfloat16) for m in more))
+
+
 class _FusedLinearCE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, hidden, weight, bias, labels, ignore_index, chunk, label_smoothing):
@@ -47,12 +62,9 @@ class _FusedLinearCE(torch.autograd.Function):
         # softmax and the smoothing mean term sum(x)/V are computed in fp32 FROM those bf16 logits, where the torch chain below keeps
         # fp32 logits.  The formula is torch's CrossEntropyLoss(label_smoothing, ignore_index); tests/test_heads_reference.py holds
         # bias + smoothing to the training tolerance against the reference's own forward.  Labels must be < V or == ignore_index
-        # (the kernel indexes x[label]); RWKV7_CHECK_LABELS=1 asserts it (one host sync per call, debugging only).
-        if CHECK_LABELS:
-            bad = (labels != ignore_index) & ((labels < 0) | (labels >= weight.shape[0]))
-            assert not bool(bad.any()), f"labels outside [0, {weight.shape[0]}) that are not ignore_index={ignore_index}"
-        hip_ce = (HIP_CE and hidden.is_cuda and hidden.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16
-                  and (bias is None or bias.dtype == torch.bfloat16) and 0 <= label_smoothing < 1 and labels.dtype == torch.int64)
+        # (the kernel indexes x[label]); RWKV7_CHECK_LABELS=1 asserts it.
+        _check_labels(labels, weight.shape[0], ignore_index)
+        hip_ce = _hip_gate(hidden, labels, weight, bias) and 0 <= label_smoothing < 1
         # Round 6 (late): a vocabulary that is not a multiple of 256 (the Spark head: 8 193) makes every row of the logits start on a 2-byte
         # boundary and gives the three head GEMMs an odd leading dimension (0.75 PF/s in the library).  With PADDED_HEAD the logits live in
         # a [rows, Vp] buffer, Vp = V rounded up to 256, the weight in a zero-padded [Vp, D] copy: the logits GEMM runs on the own kernel
@@ -164,8 +176,7 @@ def fused_linear_cross_entropy(hidden, labels, weight, bias=None, ignore_index=-
     if chunk is None:
         # the HIP kernel path keeps ONE bf16 logits tensor per chunk; the torch chain (RWKV7_HIP_CE=0, fp32 models, int32 labels, a
         # non-bf16 bias) keeps fp32 logits, an fp32 softmax and a copy in the hidden dtype: budget 3 x 4 bytes per logit there
-        hip = (HIP_CE and hidden.is_cuda and hidden.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16
-               and (bias is None or bias.dtype == torch.bfloat16) and labels.dtype == torch.int64)
+        hip = _hip_gate(hidden, labels, weight, bias)
         chunk = auto_chunk(hidden.numel() // D, weight.shape[0], hidden.element_size() if hip else 12)
     return _FusedLinearCE.apply(hidden.reshape(-1, D), weight, bias, labels.reshape(-1), ignore_index, chunk,
                                 label_smoothing)
@@ -199,19 +210,12 @@ def th_accuracy(pad_outputs, pad_targets, ignore_label):
 KL_ACC_HITS = [0]   # launches of rwkv7_kl_acc_fwd_bwd_bf16 (one per chunk): how a test sees which route a call took
 
 
-def _kl_acc_gate(x, labels, *more):
-    return (HIP_CE and x.is_cuda and x.dtype == torch.bfloat16 and labels.dtype == torch.int64
-            and all(m is None or (m.is_cuda and m.dtype == torch.bfloat16) for m in more))
-
-
 def _kl_acc_rows(logits, dlogits, labels, V, ignore_index, smoothing, scale=1.0):
     """rwkv7_kl_acc_fwd_bwd_bf16 on 2-D bf16 logits [rows, ld] (unit column stride; columns V.. untouched): writes
     (softmax - true_dist) * scale into dlogits (which may BE logits) and returns (loss_rows fp32 [rows], correct_rows int32 [rows])."""
     rows, ld = logits.shape[0], logits.stride(0)
     assert logits.stride(1) == 1 and dlogits.stride() == logits.stride() and dlogits.shape == logits.shape
-    if CHECK_LABELS:
-        bad = (labels != ignore_index) & ((labels < 0) | (labels >= V))
-        assert not bool(bad.any()), f"labels outside [0, {V}) that are not ignore_index={ignore_index}"
+    _check_labels(labels, V, ignore_index)
     lab = labels.contiguous()
     loss_rows = torch.empty(rows, dtype=torch.float32, device=logits.device)
     correct = torch.empty(rows, dtype=torch.int32, device=logits.device)
@@ -281,7 +285,7 @@ def fused_linear_kl_accuracy(hidden, labels, weight, bias, batch_size, smoothing
     rounding (see _FusedLinearKLAcc) and must be the true count."""
     D, V = hidden.shape[-1], weight.shape[0]
     h2, lab = hidden.reshape(-1, D), labels.reshape(-1)
-    if not (_kl_acc_gate(h2, lab, weight, bias) and 0 <= smoothing < 1):
+    if not (_hip_gate(h2, lab, weight, bias) and 0 <= smoothing < 1):
         logits = F.linear(h2, weight, bias)
         loss = label_smoothing_kl(logits.unsqueeze(0), lab.unsqueeze(0), V, ignore_index, smoothing, normalize_length)   # "batch" of 1
         return loss if normalize_length else loss / batch_size, th_accuracy(logits, lab.unsqueeze(0), ignore_index)
@@ -321,7 +325,7 @@ def label_smoothing_kl_fused(logits, target, size, padding_idx, smoothing, norma
     """label_smoothing_kl with the fp32 chain replaced by the HIP kernel where it applies (bf16 CUDA logits, int64 target); the logits
     are left as they are."""
     x, t = logits.reshape(-1, size), target.reshape(-1)
-    if not (_kl_acc_gate(x, t) and 0 <= smoothing < 1 and x.is_contiguous()):
+    if not (_hip_gate(x, t) and 0 <= smoothing < 1 and x.is_contiguous()):
         return label_smoothing_kl(logits, target, size, padding_idx, smoothing, normalize_length)
     return _KLFromLogits.apply(x, t, logits.shape[0], float(smoothing), normalize_length, padding_idx)
 
@@ -366,6 +370,60 @@ def _eval_rows_torch(logits, labels, ignore_index, kind, smoothing):
     return per.masked_fill(~valid, 0.0), correct
 
 
+def _eval_chunks(hidden, labels, weight, bias, ignore_index, kind, smoothing, chunk, *, align=1, overlap_last=False, out=None):
+    """The forward-only chunk walk under fused_linear_eval and _score_rows: yields (hip, loss_rows fp32 [rows], correct_rows [rows]) of
+    F.linear(hidden, weight, bias) for one chunk of rows after the other; hip: which route the call takes.
+    HIP route (_hip_gate): the head GEMM into ONE reused bf16 buffer of [chunk, ld] logits (ld = V rounded up to 16-byte rows), then
+    rwkv7_head_eval_bf16 on it (correct_rows int32).  Anything else: _eval_rows_torch of the chunk's logits (correct_rows bool).
+    chunk: rows per round (None: EVAL_CHUNK_ROWS if set, else auto_chunk).  On the HIP route it is rounded up to a multiple of `align`,
+    and with overlap_last a shorter last chunk is taken as the LAST `chunk` rows, so that every GEMM call has `chunk` rows.
+    out: None -- on the HIP route the yielded rows live in chunk-sized buffers that the next round overwrites; or full-length
+    (loss_rows fp32 [N], correct_rows int32 [N]), which every round fills at its rows' positions (the kernel writes there directly)."""
+    if kind not in (EVAL_CE, EVAL_KL) or not 0 <= smoothing < 1:
+        raise ValueError(f"head evaluation: kind must be 0 (CE) or 1 (KL) and smoothing in [0, 1), got {kind}, {smoothing}")
+    D, V = hidden.shape[-1], weight.shape[0]
+    h2, lab = hidden.reshape(-1, D), labels.reshape(-1)
+    N, dev = h2.shape[0], h2.device
+    hip = _hip_gate(h2, lab, weight, bias)
+    if chunk is None:
+        # torch route: fp32 logits and one fp32 temporary of that size
+        chunk = EVAL_CHUNK_ROWS or auto_chunk(N, V, h2.element_size() if hip else 8)
+    if hip:
+        chunk = -(-max(1, chunk) // align) * align
+    chunk = max(1, min(chunk, N))
+    starts = list(range(0, N, chunk))
+    whole = out is not None
+    if hip:
+        _check_labels(lab, V, ignore_index)
+        ld = -(-V // 8) * 8
+        buf = torch.empty(chunk, ld, dtype=h2.dtype, device=dev)
+        if not whole:
+            out = (torch.empty(chunk, dtype=torch.float32, device=dev), torch.empty(chunk, dtype=torch.int32, device=dev))
+        lab = lab.contiguous()
+        wt = weight.t()
+        if overlap_last:
+            starts[-1] = N - chunk   # N rows when one chunk holds them all
+    for s in starts:
+        h, lb = h2[s:s + chunk], lab[s:s + chunk]
+        rows = h.shape[0]
+        if hip:
+            o = s if whole else 0
+            per, ok = out[0][o:o + rows], out[1][o:o + rows]
+            logits = buf[:rows, :V]   # rows of ld elements: the GEMM writes the V logits, the kernel never reads the rest
+            if bias is None:
+                torch.mm(h, wt, out=logits)
+            else:
+                torch.addmm(bias, h, wt, out=logits)
+            _lib.call("rwkv7_head_eval_bf16", buf, rows, V, ld, buf, lb, ignore_index, kind, float(smoothing), per, ok, None)
+            EVAL_HITS[0] += 1
+        else:
+            per, ok = _eval_rows_torch(F.linear(h, weight, bias), lb, ignore_index, kind, smoothing)
+            if whole:
+                out[0][s:s + rows] = per
+                out[1][s:s + rows] = ok
+        yield hip, per, ok
+
+
 @torch.no_grad()
 def fused_linear_eval(hidden, labels, weight, bias, ignore_index, kind, smoothing=0.0, chunk=None):
     """Forward-only metrics of a head: hidden [..., D], labels [...] -> device tensors (loss_sum fp64 [1], n_valid int64 [1],
@@ -377,46 +435,13 @@ def fused_linear_eval(hidden, labels, weight, bias, ignore_index, kind, smoothin
     [chunk, ld] logits (ld = V rounded up to 16-byte rows), then rwkv7_head_eval_bf16 on it -- nothing larger than chunk x ld logits is
     ever held, and the per-row losses are bit for bit those of the training kernels.  Anything else: the same values from fp32 logits
     in torch, chunk by chunk as well.  chunk: rows per round (None: EVAL_CHUNK_ROWS if set, else auto_chunk)."""
-    if kind not in (EVAL_CE, EVAL_KL) or not 0 <= smoothing < 1:
-        raise ValueError(f"fused_linear_eval: kind must be 0 (CE) or 1 (KL) and smoothing in [0, 1), got {kind}, {smoothing}")
-    D, V = hidden.shape[-1], weight.shape[0]
-    h2, lab = hidden.reshape(-1, D), labels.reshape(-1)
-    N, dev = h2.shape[0], h2.device
-    hip = _kl_acc_gate(h2, lab, weight, bias)
-    if chunk is None:
-        # torch route: fp32 logits and one fp32 temporary of that size
-        chunk = EVAL_CHUNK_ROWS or auto_chunk(N, V, h2.element_size() if hip else 8)
-    chunk = max(1, min(chunk, N))
-    loss_sum = torch.zeros(1, dtype=torch.float64, device=dev)
-    n_correct = torch.zeros(1, dtype=torch.int64, device=dev)
+    lab = labels.reshape(-1)
+    loss_sum = torch.zeros(1, dtype=torch.float64, device=hidden.device)
+    n_correct = torch.zeros(1, dtype=torch.int64, device=hidden.device)
     n_valid = (lab != ignore_index).sum().reshape(1)
-    if hip:
-        if CHECK_LABELS:
-            bad = (lab != ignore_index) & ((lab < 0) | (lab >= V))
-            assert not bool(bad.any()), f"labels outside [0, {V}) that are not ignore_index={ignore_index}"
-        ld = -(-V // 8) * 8
-        buf = torch.empty(chunk, ld, dtype=h2.dtype, device=dev)
-        loss_rows = torch.empty(chunk, dtype=torch.float32, device=dev)
-        correct = torch.empty(chunk, dtype=torch.int32, device=dev)
-        lab = lab.contiguous()
-        wt = weight.t()
-    for s in range(0, N, chunk):
-        h, lb = h2[s:s + chunk], lab[s:s + chunk]
-        rows = h.shape[0]
-        if hip:
-            out = buf[:rows, :V]   # rows of ld elements: the GEMM writes the V logits, the kernel never reads the rest
-            if bias is None:
-                torch.mm(h, wt, out=out)
-            else:
-                torch.addmm(bias, h, wt, out=out)
-            _lib.call("rwkv7_head_eval_bf16", buf, rows, V, ld, buf, lb, ignore_index, kind, float(smoothing), loss_rows, correct, None)
-            EVAL_HITS[0] += 1
-            loss_sum += loss_rows[:rows].sum(dtype=torch.float64)
-            n_correct += correct[:rows].sum()
-        else:
-            per, ok = _eval_rows_torch(F.linear(h, weight, bias), lb, ignore_index, kind, smoothing)
-            loss_sum += per.sum(dtype=torch.float64)
-            n_correct += ok.sum()
+    for _, per, ok in _eval_chunks(hidden, lab, weight, bias, ignore_index, kind, smoothing, chunk):
+        loss_sum += per.sum(dtype=torch.float64)   # chunk by chunk: loss_sum's bits depend on this order
+        n_correct += ok.sum()
     return loss_sum, n_valid, n_correct
 
 
@@ -428,50 +453,19 @@ SCORE_CHUNK_ALIGN = 64   # HIP route: rows per head GEMM call are a multiple of 
 
 def _score_rows(hidden, labels, weight, bias, ignore_index, kind, smoothing, chunk):
     """(loss_rows fp32 [N], correct_rows int32 [N], labels int64 [N] contiguous, hip) of F.linear(hidden, weight, bias) for ALL N rows,
-    filled chunk by chunk exactly as fused_linear_eval walks them: the same gate, the same GEMM into one reused [chunk, ld] bf16 buffer,
-    rwkv7_head_eval_bf16 writing into slices of the full-length arrays (HIP route), or _eval_rows_torch per chunk.
+    filled chunk by chunk by the walk fused_linear_eval uses (_eval_chunks): the same gate, the same GEMM into one reused [chunk, ld]
+    bf16 buffer, rwkv7_head_eval_bf16 writing into slices of the full-length arrays (HIP route), or _eval_rows_torch per chunk.
     HIP route: the library GEMM takes another kernel, with another rounding of a few logits, for calls of a handful of rows (measured:
     up to 15; from 16 rows on a row's logits did not depend on the number of rows in the call).  So that the chunk size changes no bit
     of the scores, no call is that small: the chunk is rounded up to a multiple of SCORE_CHUNK_ALIGN = 64 rows, and a shorter last
     chunk is taken as the LAST `chunk` rows (it overlaps its predecessor, whose rows get the same values again)."""
-    if kind not in (EVAL_CE, EVAL_KL) or not 0 <= smoothing < 1:
-        raise ValueError(f"fused_linear_score: kind must be 0 (CE) or 1 (KL) and smoothing in [0, 1), got {kind}, {smoothing}")
-    D, V = hidden.shape[-1], weight.shape[0]
-    h2, lab = hidden.reshape(-1, D), labels.reshape(-1).contiguous()
-    N, dev = h2.shape[0], h2.device
-    hip = _kl_acc_gate(h2, lab, weight, bias)
-    if chunk is None:
-        chunk = EVAL_CHUNK_ROWS or auto_chunk(N, V, h2.element_size() if hip else 8)
-    if hip:
-        chunk = -(-max(1, chunk) // SCORE_CHUNK_ALIGN) * SCORE_CHUNK_ALIGN
-    chunk = max(1, min(chunk, N))
-    starts = list(range(0, N, chunk))
-    loss_rows = torch.empty(N, dtype=torch.float32, device=dev)
-    correct_rows = torch.empty(N, dtype=torch.int32, device=dev)
-    if hip:
-        if CHECK_LABELS:
-            bad = (lab != ignore_index) & ((lab < 0) | (lab >= V))
-            assert not bool(bad.any()), f"labels outside [0, {V}) that are not ignore_index={ignore_index}"
-        ld = -(-V // 8) * 8
-        buf = torch.empty(chunk, ld, dtype=h2.dtype, device=dev)
-        wt = weight.t()
-        starts[-1] = N - chunk   # every GEMM call has `chunk` rows (N rows when one chunk holds them all)
-    for s in starts:
-        h, lb = h2[s:s + chunk], lab[s:s + chunk]
-        rows = h.shape[0]
-        if hip:
-            out = buf[:rows, :V]   # rows of ld elements: the GEMM writes the V logits, the kernel never reads the rest
-            if bias is None:
-                torch.mm(h, wt, out=out)
-            else:
-                torch.addmm(bias, h, wt, out=out)
-            _lib.call("rwkv7_head_eval_bf16", buf, rows, V, ld, buf, lb, ignore_index, kind, float(smoothing), loss_rows[s:s + rows],
-                      correct_rows[s:s + rows], None)
-            EVAL_HITS[0] += 1
-        else:
-            per, ok = _eval_rows_torch(F.linear(h, weight, bias), lb, ignore_index, kind, smoothing)
-            loss_rows[s:s + rows] = per
-            correct_rows[s:s + rows] = ok
+    lab = labels.reshape(-1).contiguous()
+    loss_rows = torch.empty(lab.numel(), dtype=torch.float32, device=hidden.device)
+    correct_rows = torch.empty(lab.numel(), dtype=torch.int32, device=hidden.device)
+    hip = False
+    for hip, _, _ in _eval_chunks(hidden, lab, weight, bias, ignore_index, kind, smoothing, chunk, align=SCORE_CHUNK_ALIGN,
+                                  overlap_last=True, out=(loss_rows, correct_rows)):
+        pass   # every round has written its rows of the two arrays
     return loss_rows, correct_rows, lab, hip
 
 

@@ -1,6 +1,6 @@
 """Same-process A/B of the held-out evaluation head, in one process:
   1. kernel : rwkv7_head_eval_bf16 against the training entry of the same kind on the same chunk of bf16 logits
-              (kind 0: rwkv7_ce_fwd_bwd_ld_bf16 in place; kind 1: rwkv7_kl_acc_fwd_bwd_bf16 in place), chunk shapes 8192 x 8193,
+              (the three kernels of csrc/head_loss.hip; kind 0: rwkv7_ce_fwd_bwd_ld_bf16 in place; kind 1: rwkv7_kl_acc_fwd_bwd_bf16 in place), chunk shapes 8192 x 8193,
               8192 x 6562 and 2048 x 66661, rows padded to 16 bytes, smoothing 0.1, a tenth of the rows ignored.  The in-place entries
               overwrite the logits with their gradient: after the first call they time on those values (the work per element is the same).
   2. model  : RWKV7ForSpeech.eval_metrics against the eval-mode forward(labels=...) it replaces, Spark head (V = 8193) at B = 8,
