@@ -415,40 +415,29 @@ class RWKV7Attention(nn.Module):
             a_pre = self.a_lora.lora[2](hid["a"])
             g = self.g_lora.lora[2](hid["g"])
             v_pre = None if self.layer_idx == 0 else self.v_lora.lora[2](hid["v"])
+        else:
+            if (self.layer_idx != 0 and DUAL_LINEAR_XV and self.v_proj.bias is None
+                    and fused.dual_linear_supported(xv, self.v_proj.weight, self.v_lora.lora[0].weight)):
+                # xv feeds the value projection AND the value-residual branch: one autograd node, the input gradient without an add pass
+                v, v_lo = fused.dual_linear(xv, self.v_proj.weight, self.v_lora.lora[0].weight)
+            else:
+                v = self.v_proj(xv)
+            w_pre = self.w_lora(xw)
+            a_pre = self.a_lora(xa)
+            g = self.g_lora(xg)
             if self.layer_idx == 0:
-                if mask is not None:
-                    v = v * mask
-                v_first = v
-            if mask is not None:
-                r = r * mask
-            y, vf_next = fused.tmix_core(r, w_pre, k, v, a_pre, g, v_pre, v_first, self.k_k, self.k_a, self.g_norm.weight,
-                                         self.g_norm.bias, self.r_k, mask, H, self.g_norm.eps, self.layer_idx == 0, seq_start)
-            if resid is not None and self.o_proj.bias is None:
-                x1 = fused.linear_add(y, self.o_proj.weight, resid)
-                if x1 is not None:
-                    return (x1, True), (v_first if vf_next is None else vf_next)
-            return self.o_proj(y), (v_first if vf_next is None else vf_next)
-        if (self.layer_idx != 0 and DUAL_LINEAR_XV and self.v_proj.bias is None
-                and fused.dual_linear_supported(xv, self.v_proj.weight, self.v_lora.lora[0].weight)):
-            # xv feeds the value projection AND the value-residual branch: one autograd node, the input gradient without an add pass
-            v, v_lo = fused.dual_linear(xv, self.v_proj.weight, self.v_lora.lora[0].weight)
-        else:
-            v = self.v_proj(xv)
-        w_pre = self.w_lora(xw)
-        a_pre = self.a_lora(xa)
-        g = self.g_lora(xg)
-        if self.layer_idx == 0:
-            v_pre = None
-        else:
-            v_pre = self.v_lora.forward_from_hidden(v_lo) if v_lo is not None else self.v_lora(xv)
+                v_pre = None
+            else:
+                v_pre = self.v_lora.forward_from_hidden(v_lo) if v_lo is not None else self.v_lora(xv)
         if self.layer_idx == 0:
             if mask is not None:
                 v = v * mask  # rwkv_s2s_single_ffn.py:178: v is masked before it becomes v_first
             v_first = v
         if mask is not None:
             r = r * mask
-        if seq_start is not None or (state is None and torch.is_grad_enabled() and (r.requires_grad or w_pre.requires_grad)
-                                     and FUSED_TMIX_CORE):
+
+        def core():
+            """The training node from here to the block's output (with resid: the residual add in the output projection's epilogue)."""
             y, vf_next = fused.tmix_core(r, w_pre, k, v, a_pre, g, v_pre, v_first, self.k_k, self.k_a, self.g_norm.weight,
                                          self.g_norm.bias, self.r_k, mask, H, self.g_norm.eps, self.layer_idx == 0, seq_start)
             if resid is not None and self.o_proj.bias is None:
@@ -456,6 +445,12 @@ class RWKV7Attention(nn.Module):
                 if x1 is not None:
                     return (x1, True), (v_first if vf_next is None else vf_next)
             return self.o_proj(y), (v_first if vf_next is None else vf_next)
+
+        if hid is not None:
+            return core()
+        if seq_start is not None or (state is None and torch.is_grad_enabled() and (r.requires_grad or w_pre.requires_grad)
+                                     and FUSED_TMIX_CORE):
+            return core()
         w, k2, v2, a_in, b_in = fused.tmix_prepare(w_pre, k, v, a_pre, v_pre, v_first, self.k_k, self.k_a, mask,
                                                    H, self.layer_idx == 0)
         if state is None:

@@ -35,6 +35,10 @@ def _c(t):
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _c_opt(t):
+    return None if t is None else _c(t)
+
+
 def _call(name, ref, *args):
     _lib.call(f"rwkv7_{name}_{_sfx(ref)}", ref, *args)
 
@@ -67,34 +71,58 @@ def _mask_rows(mask, like):
     return mask.reshape(-1).to(like.dtype).contiguous()
 
 
+def _grid(rows, run, blocks):
+    """Workgroups of a row kernel that walks runs of `run` rows: workgroup b takes the runs b, b + nb, b + 2 nb, ..."""
+    return max(1, min(-(-rows // run), blocks))
+
+
+def _ints(xs):
+    return (ctypes.c_int * len(xs))(*xs)
+
+
+# Every row kernel has ONE launcher below, next to the nodes that use it: it takes contiguous tensors, allocates the kernel's outputs,
+# sizes the grid from the module's constants AT THE CALL (tests and tools patch them) and returns the outputs.  Parameter-gradient
+# partials are summed (_colsum) inside the launcher where every node sums them right behind the launch, and handed back raw where a
+# node queues other work in between -- the launch order of every node is part of what the tests pin.
+def _mix_fwd(x, xp, mask, params):
+    """rwkv7_mix_fwd: out [nmix, B, T, D], lerp i of x * mask with its predecessor row (xp: the carried row before t = 0, or None)."""
+    B, T, D = x.shape
+    nmix = params.shape[0]
+    out = torch.empty(nmix, B, T, D, dtype=x.dtype, device=x.device)
+    _call("mix_fwd", x, B, T, D, nmix, x, xp, mask, params, out, min(B * T, _MIX_FWD_BLOCKS))
+    return out
+
+
+def _mix_bwd(gs, x, xp, mask, params):
+    """rwkv7_mix_bwd on the nmix output gradients gs (None: zeros).  Returns (dx, the coefficients' partials [nb, nmix, D] fp32, gs
+    as the kernel read them)."""
+    B, T, D = x.shape
+    nmix = params.shape[0]
+    gs = [torch.zeros_like(x) if g is None else _c(g) for g in gs]
+    nb = _grid(B * T, _MIX_BWD_ROWS, _MIX_BWD_BLOCKS)    # (see mix_bwd_kernel)
+    dx = torch.empty_like(x)
+    part = torch.empty(nb, nmix, D, dtype=torch.float32, device=x.device)
+    _call("mix_bwd", x, B, T, D, nmix, _lib.ptr_array(gs), x, xp, mask, params, dx, part, nb, _MIX_BWD_ROWS)
+    return dx, part, gs
+
+
 class _Mix(torch.autograd.Function):
     """nmix outputs are separate autograd outputs (slices of one buffer), so backward receives nmix separate
     gradients and hands their pointers to the kernel -- no torch.stack of 6 x [B,T,D] on the way back."""
 
     @staticmethod
     def forward(ctx, x, x_prev, mask, params):
-        B, T, D = x.shape
         x, params = _c(x), _c(params)
-        nmix = params.shape[0]
-        out = torch.empty(nmix, B, T, D, dtype=x.dtype, device=x.device)
         xp = None if x_prev is None else _c(x_prev.to(x.dtype))
-        _call("mix_fwd", x, B, T, D, nmix, x, xp, mask, params, out, min(B * T, _MIX_FWD_BLOCKS))
+        out = _mix_fwd(x, xp, mask, params)
         ctx.save_for_backward(x, xp, mask, params)
         ctx.xp_dtype = None if x_prev is None else x_prev.dtype
-        return tuple(out[i] for i in range(nmix))
+        return tuple(out[i] for i in range(params.shape[0]))
 
     @staticmethod
     def backward(ctx, *gs):
         x, xp, mask, params = ctx.saved_tensors
-        B, T, D = x.shape
-        nmix = params.shape[0]
-        gs = [torch.zeros_like(x) if g is None else _c(g) for g in gs]
-        # workgroup b walks the _MIX_BWD_ROWS-row runs b, b + nb, b + 2 nb, ... (see mix_bwd_kernel)
-        nb = max(1, min(-(-B * T // _MIX_BWD_ROWS), _MIX_BWD_BLOCKS))
-        dx = torch.empty_like(x)
-        part = torch.empty(nb, nmix, D, dtype=torch.float32, device=x.device)
-        ptrs = _lib.ptr_array(gs)
-        _call("mix_bwd", x, B, T, D, nmix, ptrs, x, xp, mask, params, dx, part, nb, _MIX_BWD_ROWS)
+        dx, part, gs = _mix_bwd(gs, x, xp, mask, params)
         dxp = None
         if ctx.needs_input_grad[1]:
             # mix_fwd takes the carried row x_prev UNMASKED as the step before t = 0: d out_i[:, 0] / d x_prev = params[i]
@@ -117,6 +145,16 @@ FUSED_MIX_LORA_HITS = [0]
 WGRAD_SLABS_WCAT = 32
 
 
+def _wcat_grads(dx, dG, wcat, x):
+    """The low-rank branches' gradient through G = x wcat^T: their input gradient accumulates into the lerp stage's dx (beta = 1);
+    returns d wcat = dG^T x."""
+    D = x.shape[-1]
+    dG2 = _c(dG).view(-1, dG.shape[-1])
+    # the library's addmm_ stays: an own kernel of this family did the shape in 69 us against 51.5 (profiles/r06zz_lora_dx_ab.txt)
+    dx.view(-1, D).addmm_(dG2, wcat)
+    return wgrad_splitk(dG2, x.view(-1, D), slabs=WGRAD_SLABS_WCAT)   # [2 R, D] = [576, 1024]: 69 us with 32 slabs, 100 with 8
+
+
 class _MixLora(torch.autograd.Function):
     """(x_r, x_k, x_v, G) = (the three token-shift lerps that feed full projections, x @ wcat^T)."""
 
@@ -124,31 +162,18 @@ class _MixLora(torch.autograd.Function):
     def forward(ctx, x, mask, params, wcat):
         B, T, D = x.shape
         x, params, wcat = _c(x), _c(params), _c(wcat)
-        nmix = params.shape[0]
-        out = torch.empty(nmix, B, T, D, dtype=x.dtype, device=x.device)
-        _call("mix_fwd", x, B, T, D, nmix, x, None, mask, params, out, min(B * T, _MIX_FWD_BLOCKS))
+        out = _mix_fwd(x, None, mask, params)
         G = torch.mm(x.view(-1, D), wcat.t())
         ctx.save_for_backward(x, mask, params, wcat)
         FUSED_MIX_LORA_HITS[0] += 1
-        return (*[out[i] for i in range(nmix)], G.view(B, T, -1))
+        return (*[out[i] for i in range(params.shape[0])], G.view(B, T, -1))
 
     @staticmethod
     def backward(ctx, *gs):
         x, mask, params, wcat = ctx.saved_tensors
-        B, T, D = x.shape
         nmix = params.shape[0]
-        dG = gs[nmix]
-        gs = [torch.zeros_like(x) if g is None else _c(g) for g in gs[:nmix]]
-        nb = max(1, min(-(-B * T // _MIX_BWD_ROWS), _MIX_BWD_BLOCKS))
-        dx = torch.empty_like(x)
-        part = torch.empty(nb, nmix, D, dtype=torch.float32, device=x.device)
-        ptrs = _lib.ptr_array(gs)
-        _call("mix_bwd", x, B, T, D, nmix, ptrs, x, None, mask, params, dx, part, nb, _MIX_BWD_ROWS)
-        dwcat = None
-        if dG is not None:
-            dG2 = _c(dG).view(-1, dG.shape[-1])
-            dx.view(-1, D).addmm_(dG2, wcat)          # the branches' input gradient accumulates into the lerp stage's dx
-            dwcat = wgrad_splitk(dG2, x.view(-1, D), slabs=WGRAD_SLABS_WCAT)   # [2 R, D] = [576, 1024]: 69 us with 32 slabs, 100 with 8
+        dx, part, _ = _mix_bwd(gs[:nmix], x, None, mask, params)
+        dwcat = None if gs[nmix] is None else _wcat_grads(dx, gs[nmix], wcat, x)
         return dx, None, _colsum(part, params.dtype), dwcat
 
 
@@ -169,39 +194,56 @@ def mix_lora_supported(x, state, seq_start, w1s=None, mask=None):
     return True
 
 
+def _wcat_fwd(w1s, mus):
+    """rwkv7_mix_lora_wcat_fwd: wcat [2 R, D] = [W1_i * (1 - mu_i) ; W1_i * mu_i] of all branches."""
+    ranks = [w.shape[0] for w in w1s]
+    D = w1s[0].shape[1]
+    wcat = torch.empty(2 * sum(ranks), D, dtype=w1s[0].dtype, device=w1s[0].device)
+    _lib.call("rwkv7_mix_lora_wcat_fwd_bf16", wcat, len(w1s), _ints(ranks), _lib.ptr_array(w1s), _lib.ptr_array(mus), D, wcat)
+    return wcat
+
+
+def _wcat_bwd(dwcat, w1s, mus):
+    """rwkv7_mix_lora_wcat_bwd: (d W1_i, d mu_i [D]) of every branch from d wcat."""
+    nb = len(w1s)
+    D = w1s[0].shape[1]
+    dw1 = [torch.empty_like(w) for w in w1s]
+    dmu = [torch.empty(D, dtype=w1s[0].dtype, device=w1s[0].device) for _ in range(nb)]
+    _lib.call("rwkv7_mix_lora_wcat_bwd_bf16", dwcat, nb, _ints([w.shape[0] for w in w1s]), _lib.ptr_array(w1s), _lib.ptr_array(mus), D,
+              dwcat, _lib.ptr_array(dw1), _lib.ptr_array(dmu))
+    return dw1, dmu
+
+
 class _WcatBuild(torch.autograd.Function):
-    """wcat [2 R, D] = [W1_i * (1 - mu_i) ; W1_i * mu_i] of all branches (rwkv7_mix_lora_wcat_*: one small kernel each way instead of
-    a dozen tensor ops per branch)."""
+    """wcat of all branches (rwkv7_mix_lora_wcat_*: one small kernel each way instead of a dozen tensor ops per branch)."""
 
     @staticmethod
     def forward(ctx, nb, *ts):
         w1s, mus = [_c(t) for t in ts[:nb]], [_c(t) for t in ts[nb:]]
-        D = w1s[0].shape[1]
-        ranks = (ctypes.c_int * nb)(*[w.shape[0] for w in w1s])
-        R = sum(w.shape[0] for w in w1s)
-        wcat = torch.empty(2 * R, D, dtype=w1s[0].dtype, device=w1s[0].device)
-        _lib.call("rwkv7_mix_lora_wcat_fwd_bf16", wcat, nb, ranks, _lib.ptr_array(w1s), _lib.ptr_array(mus), D, wcat)
         ctx.save_for_backward(*w1s, *mus)
         ctx.nb = nb
         ctx.mu_shapes = [t.shape for t in ts[nb:]]
-        return wcat
+        return _wcat_fwd(w1s, mus)
 
     @staticmethod
     def backward(ctx, dwcat):
-        nb = ctx.nb
         ts = ctx.saved_tensors
-        w1s, mus = ts[:nb], ts[nb:]
-        D = w1s[0].shape[1]
-        ranks = (ctypes.c_int * nb)(*[w.shape[0] for w in w1s])
-        dwcat = _c(dwcat)
-        dw1 = [torch.empty_like(w) for w in w1s]
-        dmu = [torch.empty(D, dtype=w1s[0].dtype, device=w1s[0].device) for _ in range(nb)]
-        _lib.call("rwkv7_mix_lora_wcat_bwd_bf16", dwcat, nb, ranks, _lib.ptr_array(w1s), _lib.ptr_array(mus), D, dwcat, _lib.ptr_array(dw1),
-                  _lib.ptr_array(dmu))
+        dw1, dmu = _wcat_bwd(_c(dwcat), ts[:ctx.nb], ts[ctx.nb:])
         return (None, *dw1, *[g.view(sh) for g, sh in zip(dmu, ctx.mu_shapes)])
 
 
 _ACT_CODE = {None: 0, "tanh": 1, "sigmoid": 2}
+
+
+def _combine_bwd(das, outs, mask, ranks, acts, shape):
+    """rwkv7_mix_lora_combine_bwd: dG (`shape`: [B, T, 2 R] or [B * T, 2 R]) from the gradients das (None: zeros) of the branches'
+    activated hidden states outs [B, T, r_i]."""
+    B, T = outs[0].shape[:2]
+    das = [torch.zeros_like(o) if g is None else _c(g) for g, o in zip(das, outs)]
+    dG = torch.empty(shape, dtype=outs[0].dtype, device=outs[0].device)
+    _lib.call("rwkv7_mix_lora_combine_bwd_bf16", dG, len(ranks), _ints(ranks), _ints(acts), B * T, T, mask, _lib.ptr_array(outs),
+              _lib.ptr_array(das), dG)
+    return dG
 
 
 class _CombineAct(torch.autograd.Function):
@@ -211,10 +253,8 @@ class _CombineAct(torch.autograd.Function):
     def forward(ctx, G, mask, ranks, acts):
         B, T, R2 = G.shape
         G = _c(G)
-        nb = len(ranks)
         outs = [torch.empty(B, T, r, dtype=G.dtype, device=G.device) for r in ranks]
-        cr, ca = (ctypes.c_int * nb)(*ranks), (ctypes.c_int * nb)(*acts)
-        _lib.call("rwkv7_mix_lora_combine_fwd_bf16", G, nb, cr, ca, B * T, T, G, mask, _lib.ptr_array(outs))
+        _lib.call("rwkv7_mix_lora_combine_fwd_bf16", G, len(ranks), _ints(ranks), _ints(acts), B * T, T, G, mask, _lib.ptr_array(outs))
         ctx.save_for_backward(mask, *outs)
         ctx.ranks, ctx.acts, ctx.shape = ranks, acts, (B, T, R2)
         return tuple(outs)
@@ -222,13 +262,7 @@ class _CombineAct(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *das):
         mask, *outs = ctx.saved_tensors
-        B, T, R2 = ctx.shape
-        nb = len(ctx.ranks)
-        das = [torch.zeros_like(o) if g is None else _c(g) for g, o in zip(das, outs)]
-        dG = torch.empty(B, T, R2, dtype=outs[0].dtype, device=outs[0].device)
-        cr, ca = (ctypes.c_int * nb)(*ctx.ranks), (ctypes.c_int * nb)(*ctx.acts)
-        _lib.call("rwkv7_mix_lora_combine_bwd_bf16", dG, nb, cr, ca, B * T, T, mask, _lib.ptr_array(outs), _lib.ptr_array(das), dG)
-        return dG, None, None, None
+        return _combine_bwd(das, outs, mask, ctx.ranks, ctx.acts, ctx.shape), None, None, None
 
 
 # Round 6 (late): the branches' down projections with the lerp as the A PROLOGUE of one own MFMA kernel (csrc/lora_down.hip) instead of the
@@ -262,49 +296,30 @@ class _MixLoraDirect(torch.autograd.Function):
         B, T, D = x.shape
         x, params = _c(x), _c(params)
         w1s, mus = [_c(t) for t in ts[:nb]], [_c(t.reshape(-1)) for t in ts[nb:]]
-        nmix = params.shape[0]
-        out = torch.empty(nmix, B, T, D, dtype=x.dtype, device=x.device)
-        _call("mix_fwd", x, B, T, D, nmix, x, None, mask, params, out, min(B * T, _MIX_FWD_BLOCKS))
+        out = _mix_fwd(x, None, mask, params)
         ranks = [w.shape[0] for w in w1s]
-        cr, ca = (ctypes.c_int * nb)(*ranks), (ctypes.c_int * nb)(*acts)
+        cr = _ints(ranks)
         packed = torch.empty(sum(ranks), D, dtype=x.dtype, device=x.device)
         hs = [torch.empty(B, T, r, dtype=x.dtype, device=x.device) for r in ranks]
         _lib.call("rwkv7_lora_down_pack_bf16", x, nb, cr, _lib.ptr_array(w1s), D, packed)
-        _lib.call("rwkv7_lora_down_fwd_bf16", x, nb, cr, ca, B * T, T, D, x, mask, _lib.ptr_array(mus), packed, _lib.ptr_array(hs))
+        _lib.call("rwkv7_lora_down_fwd_bf16", x, nb, cr, _ints(acts), B * T, T, D, x, mask, _lib.ptr_array(mus), packed, _lib.ptr_array(hs))
         ctx.save_for_backward(x, mask, params, *w1s, *mus, *hs)
         ctx.nb, ctx.acts, ctx.mu_shapes = nb, acts, [t.shape for t in ts[nb:]]
         LORA_DOWN_DIRECT_HITS[0] += 1
         FUSED_MIX_LORA_HITS[0] += 1
-        return (*[out[i] for i in range(nmix)], *hs)
+        return (*[out[i] for i in range(params.shape[0])], *hs)
 
     @staticmethod
     def backward(ctx, *gs):
         nb = ctx.nb
         x, mask, params, *rest = ctx.saved_tensors
         w1s, mus, hs = rest[:nb], rest[nb:2 * nb], rest[2 * nb:]
-        B, T, D = x.shape
         nmix = params.shape[0]
         ranks = [w.shape[0] for w in w1s]
-        R = sum(ranks)
-        cr, ca = (ctypes.c_int * nb)(*ranks), (ctypes.c_int * nb)(*ctx.acts)
-        das = [torch.zeros_like(h) if g is None else _c(g) for g, h in zip(gs[nmix:], hs)]
-        dG = torch.empty(B * T, 2 * R, dtype=x.dtype, device=x.device)
-        _lib.call("rwkv7_mix_lora_combine_bwd_bf16", x, nb, cr, ca, B * T, T, mask, _lib.ptr_array(hs), _lib.ptr_array(das), dG)
-        g3 = [torch.zeros_like(x) if g is None else _c(g) for g in gs[:nmix]]
-        nblk = max(1, min(-(-B * T // _MIX_BWD_ROWS), _MIX_BWD_BLOCKS))
-        dx = torch.empty_like(x)
-        part = torch.empty(nblk, nmix, D, dtype=torch.float32, device=x.device)
-        ptrs = _lib.ptr_array(g3)
-        _call("mix_bwd", x, B, T, D, nmix, ptrs, x, None, mask, params, dx, part, nblk, _MIX_BWD_ROWS)
-        wcat = torch.empty(2 * R, D, dtype=x.dtype, device=x.device)
-        _lib.call("rwkv7_mix_lora_wcat_fwd_bf16", x, nb, cr, _lib.ptr_array(w1s), _lib.ptr_array(mus), D, wcat)
-        # the library's addmm_ stays: an own kernel of this family did the shape in 69 us against 51.5 (profiles/r06zz_lora_dx_ab.txt)
-        dx.view(-1, D).addmm_(dG, wcat)
-        dwcat = _c(wgrad_splitk(dG, x.view(-1, D), slabs=WGRAD_SLABS_WCAT))
-        dw1 = [torch.empty_like(w) for w in w1s]
-        dmu = [torch.empty(D, dtype=x.dtype, device=x.device) for _ in range(nb)]
-        _lib.call("rwkv7_mix_lora_wcat_bwd_bf16", x, nb, cr, _lib.ptr_array(w1s), _lib.ptr_array(mus), D, dwcat, _lib.ptr_array(dw1),
-                  _lib.ptr_array(dmu))
+        dG = _combine_bwd(gs[nmix:], hs, mask, ranks, ctx.acts, (x.shape[0] * x.shape[1], 2 * sum(ranks)))
+        dx, part, _ = _mix_bwd(gs[:nmix], x, None, mask, params)
+        dwcat = _c(_wcat_grads(dx, dG, _wcat_fwd(w1s, mus), x))
+        dw1, dmu = _wcat_bwd(dwcat, w1s, mus)
         return (dx, None, _colsum(part, params.dtype), None, None, *dw1, *[g.view(sh) for g, sh in zip(dmu, ctx.mu_shapes)])
 
 
@@ -552,19 +567,39 @@ def key_relu_sq(x, weight):
     return None
 
 
+def _tmix_prepare_fwd(w_pre, k, v, a_pre, v_pre, v_first, mask, k_k, k_a):
+    """rwkv7_tmix_prepare_fwd: [w, k2, v2, a_in, b_in], the scan's operands."""
+    rows, D = k.numel() // k.shape[-1], k.shape[-1]
+    outs = [torch.empty_like(k) for _ in range(5)]
+    _call("tmix_prepare_fwd", k, rows, D, w_pre, k, v, a_pre, v_pre, v_first, mask, k_k, k_a, *outs, min(rows, _FWD_BLOCKS))
+    return outs
+
+
+def _tmix_post_fwd(y, r, k, v, g, gn_w, gn_b, r_k, eps):
+    """rwkv7_tmix_post_fwd: GroupNorm of the scan's y + bonus, gated."""
+    rows, D = y.numel() // y.shape[-1], y.shape[-1]
+    out = torch.empty_like(y)
+    _call("tmix_post_fwd", y, rows, D, y, r, k, v, g, gn_w, gn_b, r_k, eps, out, min(rows, _FWD_BLOCKS))
+    return out
+
+
+def _tmix_post_bwd(dout, y, r, k, v, g, gn_w, gn_b, r_k, eps):
+    """rwkv7_tmix_post_bwd: ([d_y, d_r, d_k, d_v, d_g], the partials [nb, 3, D] fp32 of gn_w, gn_b, r_k)."""
+    rows, D = y.numel() // y.shape[-1], y.shape[-1]
+    nb = min(rows, _BWD_BLOCKS)
+    ds = [torch.empty_like(y) for _ in range(5)]
+    part = torch.empty(nb, 3, D, dtype=torch.float32, device=y.device)
+    _call("tmix_post_bwd", y, rows, D, dout, y, r, k, v, g, gn_w, gn_b, r_k, eps, *ds, part, nb)
+    return ds, part
+
+
 class _TmixPrepare(torch.autograd.Function):
     @staticmethod
     def forward(ctx, w_pre, k, v, a_pre, v_pre, v_first, k_k, k_a, mask):
-        B, T, D = k.shape
-        w_pre, k, v, a_pre = _c(w_pre), _c(k), _c(v), _c(a_pre)
-        v_pre = None if v_pre is None else _c(v_pre)
-        v_first = None if v_first is None else _c(v_first)
+        w_pre, k, v, a_pre, v_pre, v_first = _c(w_pre), _c(k), _c(v), _c(a_pre), _c_opt(v_pre), _c_opt(v_first)
         k_k, k_a = _c(k_k.to(k.dtype)), _c(k_a.to(k.dtype))
-        outs = [torch.empty_like(k) for _ in range(5)]
-        rows = B * T
-        _call("tmix_prepare_fwd", k, rows, D, w_pre, k, v, a_pre, v_pre, v_first, mask, k_k, k_a, *outs, min(rows, _FWD_BLOCKS))
         ctx.save_for_backward(w_pre, k, v, a_pre, v_pre, v_first, k_k, k_a, mask)
-        return tuple(outs)
+        return tuple(_tmix_prepare_fwd(w_pre, k, v, a_pre, v_pre, v_first, mask, k_k, k_a))
 
     @staticmethod
     def backward(ctx, d_w, d_k2, d_v2, d_a, d_b):
@@ -595,28 +630,18 @@ def tmix_prepare(w_pre, k, v, a_pre, v_pre, v_first, k_k, k_a, mask, H, is_layer
 class _TmixPost(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, r, k, v, g, gn_w, gn_b, r_k, eps):
-        B, T, D = y.shape
         y, r, k, v, g = _c(y), _c(r), _c(k), _c(v), _c(g)
         gn_w, gn_b, r_k = _c(gn_w.to(y.dtype)), _c(gn_b.to(y.dtype)), _c(r_k.reshape(-1).to(y.dtype))
-        out = torch.empty_like(y)
-        rows = B * T
-        _call("tmix_post_fwd", y, rows, D, y, r, k, v, g, gn_w, gn_b, r_k, eps, out, min(rows, _FWD_BLOCKS))
         ctx.save_for_backward(y, r, k, v, g, gn_w, gn_b, r_k)
         ctx.eps = eps
-        return out
+        return _tmix_post_fwd(y, r, k, v, g, gn_w, gn_b, r_k, eps)
 
     @staticmethod
     def backward(ctx, dout):
-        y, r, k, v, g, gn_w, gn_b, r_k = ctx.saved_tensors
-        B, T, D = y.shape
-        rows = B * T
-        nb = min(rows, _BWD_BLOCKS)
-        dout = _c(dout)
-        d_y, d_r, d_k, d_v, d_g = [torch.empty_like(y) for _ in range(5)]
-        part = torch.empty(nb, 3, D, dtype=torch.float32, device=y.device)
-        _call("tmix_post_bwd", y, rows, D, dout, y, r, k, v, g, gn_w, gn_b, r_k, ctx.eps, d_y, d_r, d_k, d_v, d_g, part, nb)
+        y, *rest = ctx.saved_tensors
+        ds, part = _tmix_post_bwd(_c(dout), y, *rest, ctx.eps)
         dp = _colsum(part, y.dtype)
-        return d_y, d_r, d_k, d_v, d_g, dp[0], dp[1], dp[2], None
+        return (*ds, dp[0], dp[1], dp[2], None)
 
 
 def tmix_post(y, r, k, v, g, gn_weight, gn_bias, r_k, H, eps):
@@ -645,15 +670,10 @@ class _TmixCore(torch.autograd.Function):
         B, T, D = k.shape
         if T % ops.CHUNK_LEN != 0:
             raise ValueError(f"T={T} must be a multiple of {ops.CHUNK_LEN}")
-        r, w_pre, k, v, a_pre, g = _c(r), _c(w_pre), _c(k), _c(v), _c(a_pre), _c(g)
-        v_pre = None if v_pre is None else _c(v_pre)
-        v_first = None if v_first is None else _c(v_first)
+        r, w_pre, k, v, a_pre, g, v_pre, v_first = _c(r), _c(w_pre), _c(k), _c(v), _c(a_pre), _c(g), _c_opt(v_pre), _c_opt(v_first)
         k_k, k_a = _c(k_k.to(k.dtype)), _c(k_a.to(k.dtype))
         gn_w, gn_b, r_k = _c(gn_w.to(k.dtype)), _c(gn_b.to(k.dtype)), _c(r_k.reshape(-1).to(k.dtype))
-        rows = B * T
-        w, k2, v2, a_in, b_in = [torch.empty_like(k) for _ in range(5)]
-        _call("tmix_prepare_fwd", k, rows, D, w_pre, k, v, a_pre, v_pre, v_first, mask, k_k, k_a, w, k2, v2, a_in, b_in,
-              min(rows, _FWD_BLOCKS))
+        w, k2, v2, a_in, b_in = _tmix_prepare_fwd(w_pre, k, v, a_pre, v_pre, v_first, mask, k_k, k_a)
         v4 = lambda t: t.view(B, T, H, 64)
         via_op = VIA_REFERENCE_OP and seq_start is None
         chunked = CHUNKED_WKV_FWD and CHUNKED_WKV_BWD and k.dtype == torch.bfloat16 and T % ops.CHUNK_T == 0 and not via_op
@@ -672,8 +692,7 @@ class _TmixCore(torch.autograd.Function):
                 torch.ops.wind_backstepping.forward(v4(w), v4(r), v4(k2), v4(v2), v4(a_in), v4(b_in), v4(y), s, sa)
             else:
                 ops.wkv7_forward_scalar(v4(w), v4(r), v4(k2), v4(v2), v4(a_in), v4(b_in), v4(y), s, sa)
-        out = torch.empty_like(k)
-        _call("tmix_post_fwd", k, rows, D, y, r, k2, v2, g, gn_w, gn_b, r_k, eps, out, min(rows, _FWD_BLOCKS))
+        out = _tmix_post_fwd(y, r, k2, v2, g, gn_w, gn_b, r_k, eps)
         ctx.save_for_backward(r, w_pre, k, v, a_pre, g, v_pre, v_first, k_k, k_a, gn_w, gn_b, r_k, mask,
                               w, k2, v2, a_in, b_in, y, s, sa, tinv)
         ctx.H, ctx.eps, ctx.chunked_fwd, ctx.seq_start, ctx.via_op = H, eps, chunked, seq_start, via_op
@@ -696,20 +715,18 @@ class _TmixCore(torch.autograd.Function):
         nb = min(rows, _BWD_BLOCKS)
         dout = _c(dout)
         # 1. GroupNorm / bonus / gate
-        part_post = torch.empty(nb, 3, D, dtype=torch.float32, device=k.device)
         compact = COMPACT_POST_BWD
         if compact:
             # the bonus term's contributions to r, k2, v2 are rank-1 per head: one tensor (dt) + two scalars per (row, head) leave
             # this stage instead of three tensors, and stage 3 rebuilds them (three [rows, D] streams fewer per layer)
+            part_post = torch.empty(nb, 3, D, dtype=torch.float32, device=k.device)
             d_y, dt_post, d_g = [torch.empty_like(k) for _ in range(3)]
             hscal = torch.empty(rows, H, 2, dtype=torch.float32, device=k.device)
             d_r_post = d_k2_post = d_v2_post = None
             _call("tmix_post_bwd_compact", k, rows, D, dout, y, r, k2, v2, g, gn_w, gn_b, r_k, ctx.eps, d_y, dt_post, d_g, hscal, part_post,
                   nb)
         else:
-            d_y, d_r_post, d_k2_post, d_v2_post, d_g = [torch.empty_like(k) for _ in range(5)]
-            _call("tmix_post_bwd", k, rows, D, dout, y, r, k2, v2, g, gn_w, gn_b, r_k, ctx.eps, d_y, d_r_post, d_k2_post, d_v2_post, d_g,
-                  part_post, nb)
+            (d_y, d_r_post, d_k2_post, d_v2_post, d_g), part_post = _tmix_post_bwd(dout, y, r, k2, v2, g, gn_w, gn_b, r_k, ctx.eps)
         # 2. scan: chunked MFMA backward (bf16, T % 32 == 0) or the scalar kernel with two workgroups per head
         if WGRAD_SYNC_BEFORE_SCAN:
             wgrad_side_sync(k.device)
@@ -759,9 +776,6 @@ def tmix_core(r, w_pre, k, v, a_pre, g, v_pre, v_first, k_k, k_a, gn_weight, gn_
     return res   # (y, v_first for the next layer)
 
 
-_ACT_ID = {None: 0, "tanh": 1, "sigmoid": 2}
-
-
 def lora_decode_supported(x, rank):
     rows = x.numel() // x.shape[-1]
     return (GEMV_MAX_ROWS and x.is_cuda and x.dtype == torch.bfloat16 and rows <= GEMV_MAX_ROWS and rank in (32, 64, 128)
@@ -775,7 +789,7 @@ def lora_decode(x, w1, w2, bias, activation):
     x2 = _c(x).view(rows, K)
     b2 = None if bias is None else _c(bias)
     y = torch.empty(rows, N, dtype=torch.bfloat16, device=x.device)
-    _lib.call("rwkv7_lora32_bf16", x, rows, N, K, R, _ACT_ID[activation], x2, _c(w1), _c(w2), b2, y)
+    _lib.call("rwkv7_lora32_bf16", x, rows, N, K, R, _ACT_CODE[activation], x2, _c(w1), _c(w2), b2, y)
     return y.view(*x.shape[:-1], N)
 
 
@@ -1099,6 +1113,23 @@ def linear_add(y, weight, resid):
 # ------------------------------------------------------------------------------------------------------
 # residual add + LayerNorm
 # ------------------------------------------------------------------------------------------------------
+def _ln_params(gamma, beta, dtype):
+    """LayerNorm's weight and bias (may be None) as the kernels take them."""
+    return _c(gamma.to(dtype)), (None if beta is None else _c(beta.to(dtype)))
+
+
+def _add_ln_bwd(dh, d_x1, xs, mean, rstd, gamma):
+    """rwkv7_add_ln_bwd: (dx, dgamma, dbeta) from dh and the gradient d_x1 (may be None) that reaches xs = x + branch directly."""
+    D = xs.shape[-1]
+    rows = xs.numel() // D
+    nb = min(rows, _BWD_BLOCKS)
+    dx = torch.empty_like(xs)
+    part = torch.empty(nb, 2, D, dtype=torch.float32, device=xs.device)
+    _call("add_ln_bwd", xs, rows, D, _c(dh), _c_opt(d_x1), xs, mean, rstd, gamma, dx, part, nb)
+    dp = _colsum(part, xs.dtype)
+    return dx, dp[0], dp[1]
+
+
 class _AddLN(torch.autograd.Function):
     """(x1, h) = (x + branch, LayerNorm(x + branch)); with branch None: h = LayerNorm(x) only.
     backward folds the gradient arriving at x1 through the residual path into the LayerNorm backward kernel."""
@@ -1108,8 +1139,7 @@ class _AddLN(torch.autograd.Function):
         D = x.shape[-1]
         x = _c(x)
         rows = x.numel() // D
-        gamma_c = _c(gamma.to(x.dtype))
-        beta_c = None if beta is None else _c(beta.to(x.dtype))
+        gamma_c, beta_c = _ln_params(gamma, beta, x.dtype)
         h = torch.empty_like(x)
         mean = torch.empty(rows, dtype=torch.float32, device=x.device)
         rstd = torch.empty_like(mean)
@@ -1128,8 +1158,6 @@ class _AddLN(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *grads):
         xs, mean, rstd, gamma = ctx.saved_tensors
-        D = xs.shape[-1]
-        rows = xs.numel() // D
         if ctx.has_branch:
             d_x1, dh = grads
         else:
@@ -1137,19 +1165,30 @@ class _AddLN(torch.autograd.Function):
         if dh is None:  # h unused downstream: only the residual path carries gradient
             dx = d_x1
             return dx, (dx if ctx.has_branch else None), None, None, None
-        dh = _c(dh)
-        d_x1 = None if d_x1 is None else _c(d_x1)
-        nb = min(rows, _BWD_BLOCKS)
-        dx = torch.empty_like(xs)
-        part = torch.empty(nb, 2, D, dtype=torch.float32, device=xs.device)
-        _call("add_ln_bwd", xs, rows, D, dh, d_x1, xs, mean, rstd, gamma, dx, part, nb)
-        dp = _colsum(part, xs.dtype)
-        return dx, (dx if ctx.has_branch else None), dp[0], (dp[1] if ctx.has_beta else None), None
+        dx, dgamma, dbeta = _add_ln_bwd(dh, d_x1, xs, mean, rstd, gamma)
+        return dx, (dx if ctx.has_branch else None), dgamma, (dbeta if ctx.has_beta else None), None
 
 
 _ADD_LN_MIX_RUN = 4       # rows per run of the fused add + LayerNorm + token-shift kernels (one neighbour row recomputed per run)
 _ADD_LN_MIX_BLOCKS = 8192
 _ADD_LN_MIX_BWD_BLOCKS = 2048   # also the number of parameter-gradient partials
+
+
+def _add_ln_mix_fwd(x, branch, gamma, beta, eps, mask, params, store_h):
+    """rwkv7_add_ln_mix_fwd, or with store_h rwkv7_add_ln_mix_fwd_h, which also writes h = LayerNorm(x1).  Returns (x1, out
+    [nmix, B, T, D], h or None, mean, rstd, gamma, beta as the kernel took them); x1 = x + branch, x itself without a branch."""
+    B, T, D = x.shape
+    nmix = params.shape[0]
+    gamma_c, beta_c = _ln_params(gamma, beta, x.dtype)
+    out = torch.empty(nmix, B, T, D, dtype=x.dtype, device=x.device)
+    h = torch.empty_like(x) if store_h else None
+    mean = torch.empty(B * T, dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    x1 = None if branch is None else torch.empty_like(x)
+    nb = _grid(B * T, _ADD_LN_MIX_RUN, _ADD_LN_MIX_BLOCKS)
+    _call("add_ln_mix_fwd_h" if store_h else "add_ln_mix_fwd", x, B, T, D, nmix, x, _c_opt(branch), gamma_c, beta_c, eps, mask, params, x1,
+          out, *((h,) if store_h else ()), mean, rstd, nb, _ADD_LN_MIX_RUN)
+    return (x if branch is None else x1), out, h, mean, rstd, gamma_c, beta_c
 
 
 class _AddLNMix(torch.autograd.Function):
@@ -1159,25 +1198,11 @@ class _AddLNMix(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, branch, gamma, beta, eps, mask, params):
-        B, T, D = x.shape
         x, params = _c(x), _c(params)
-        nmix = params.shape[0]
-        gamma_c = _c(gamma.to(x.dtype))
-        beta_c = None if beta is None else _c(beta.to(x.dtype))
-        rows = B * T
-        out = torch.empty(nmix, B, T, D, dtype=x.dtype, device=x.device)
-        mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mean)
-        if branch is not None:
-            branch = _c(branch)
-            x1 = torch.empty_like(x)
-        else:
-            x1 = None
-        nb = max(1, min(-(-rows // _ADD_LN_MIX_RUN), _ADD_LN_MIX_BLOCKS))
-        _call("add_ln_mix_fwd", x, B, T, D, nmix, x, branch, gamma_c, beta_c, eps, mask, params, x1, out, mean, rstd, nb, _ADD_LN_MIX_RUN)
+        x1, out, _, mean, rstd, gamma_c, beta_c = _add_ln_mix_fwd(x, branch, gamma, beta, eps, mask, params, store_h=False)
         ctx.has_branch, ctx.has_beta = branch is not None, beta is not None
-        ctx.save_for_backward(x1 if branch is not None else x, mean, rstd, gamma_c, beta_c, mask, params)
-        return (x1 if branch is not None else x,) + tuple(out[i] for i in range(nmix))
+        ctx.save_for_backward(x1, mean, rstd, gamma_c, beta_c, mask, params)
+        return (x1,) + tuple(out[i] for i in range(params.shape[0]))
 
     @staticmethod
     def backward(ctx, d_x1, *gs):
@@ -1185,67 +1210,14 @@ class _AddLNMix(torch.autograd.Function):
         B, T, D = xs.shape
         nmix = params.shape[0]
         gs = [torch.zeros_like(xs) if g is None else _c(g) for g in gs]
-        d_x1 = None if d_x1 is None else _c(d_x1)
-        rows = B * T
-        nb = max(1, min(-(-rows // _ADD_LN_MIX_RUN), _ADD_LN_MIX_BWD_BLOCKS))
+        nb = _grid(B * T, _ADD_LN_MIX_RUN, _ADD_LN_MIX_BWD_BLOCKS)
         dx = torch.empty_like(xs)
         part = torch.empty(nb, nmix + 2, D, dtype=torch.float32, device=xs.device)
-        ptrs = _lib.ptr_array(gs)
-        _call("mix_add_ln_bwd", xs, B, T, D, nmix, ptrs, d_x1, xs, mean, rstd, gamma, beta, mask, params, dx, part, nb, _ADD_LN_MIX_RUN)
+        _call("mix_add_ln_bwd", xs, B, T, D, nmix, _lib.ptr_array(gs), _c_opt(d_x1), xs, mean, rstd, gamma, beta, mask, params, dx, part, nb,
+              _ADD_LN_MIX_RUN)
         dp = _colsum(part, xs.dtype) if params.dtype == xs.dtype else part.sum(0)
         return (dx, (dx if ctx.has_branch else None), dp[nmix].to(xs.dtype), (dp[nmix + 1].to(xs.dtype) if ctx.has_beta else None),
                 None, None, dp[:nmix].to(params.dtype))
-
-
-class _AddLNMixFwd(torch.autograd.Function):
-    """Forward of _AddLNMix (one pass: residual add + LayerNorm + lerps, rwkv7_add_ln_mix_fwd_h, which also stores h), backward as
-    the two SEPARATE kernels (rwkv7_mix_bwd, rwkv7_add_ln_bwd).  For the time-mix side: its one-pass backward spills (backbone.py,
-    FUSED_ADD_LN_MIX6), its one-pass forward does not."""
-
-    @staticmethod
-    def forward(ctx, x, branch, gamma, beta, eps, mask, params):
-        B, T, D = x.shape
-        x, params = _c(x), _c(params)
-        nmix = params.shape[0]
-        gamma_c = _c(gamma.to(x.dtype))
-        beta_c = None if beta is None else _c(beta.to(x.dtype))
-        rows = B * T
-        out = torch.empty(nmix, B, T, D, dtype=x.dtype, device=x.device)
-        h = torch.empty_like(x)
-        mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mean)
-        if branch is not None:
-            branch = _c(branch)
-            x1 = torch.empty_like(x)
-        else:
-            x1 = None
-        nb = max(1, min(-(-rows // _ADD_LN_MIX_RUN), _ADD_LN_MIX_BLOCKS))
-        _call("add_ln_mix_fwd_h", x, B, T, D, nmix, x, branch, gamma_c, beta_c, eps, mask, params, x1, out, h, mean, rstd, nb,
-              _ADD_LN_MIX_RUN)
-        ctx.has_branch, ctx.has_beta = branch is not None, beta is not None
-        ctx.save_for_backward(x1 if branch is not None else x, h, mean, rstd, gamma_c, mask, params)
-        return (x1 if branch is not None else x,) + tuple(out[i] for i in range(nmix))
-
-    @staticmethod
-    def backward(ctx, d_x1, *gs):
-        xs, h, mean, rstd, gamma, mask, params = ctx.saved_tensors
-        B, T, D = xs.shape
-        nmix = params.shape[0]
-        rows = B * T
-        gs = [torch.zeros_like(xs) if g is None else _c(g) for g in gs]
-        nb = max(1, min(-(-rows // _MIX_BWD_ROWS), _MIX_BWD_BLOCKS))
-        dh = torch.empty_like(xs)
-        part_m = torch.empty(nb, nmix, D, dtype=torch.float32, device=xs.device)
-        ptrs = _lib.ptr_array(gs)
-        _call("mix_bwd", xs, B, T, D, nmix, ptrs, h, None, mask, params, dh, part_m, nb, _MIX_BWD_ROWS)
-        d_x1 = None if d_x1 is None else _c(d_x1)
-        nb2 = min(rows, _BWD_BLOCKS)
-        dx = torch.empty_like(xs)
-        part = torch.empty(nb2, 2, D, dtype=torch.float32, device=xs.device)
-        _call("add_ln_bwd", xs, rows, D, dh, d_x1, xs, mean, rstd, gamma, dx, part, nb2)
-        dp = _colsum(part, xs.dtype)
-        return (dx, (dx if ctx.has_branch else None), dp[0], (dp[1] if ctx.has_beta else None),
-                None, None, _colsum(part_m, params.dtype))
 
 
 # measured (round 4, same-box A/B, tools/ab_step.py): 126.25 -> 126.83 ms per step, +0.58 ms -- the one-pass kernel re-normalises a
@@ -1254,62 +1226,37 @@ class _AddLNMixFwd(torch.autograd.Function):
 FUSED_ADD_LN_MIX_LORA_FWD = os.environ.get("RWKV7_FUSED_ADD_LN_MIX_LORA_FWD", "0") == "1"
 
 
-class _AddLNMixLora(torch.autograd.Function):
-    """(x1, x_r, x_k, x_v, G): _AddLN followed by _MixLora with ONE forward kernel -- residual add + LayerNorm + the three lerps that
-    feed full projections, h = LayerNorm(x1) stored because the branches' GEMM G = h wcat^T (and the backward) read it anyway
-    (rwkv7_add_ln_mix_fwd_h, nmix = 3).  The backward is the separate stages' own: mix_bwd -> + dG wcat -> add_ln_bwd."""
+class _AddLNMixFwd(torch.autograd.Function):
+    """Forward of _AddLNMix (one pass: residual add + LayerNorm + lerps, rwkv7_add_ln_mix_fwd_h, which also stores h), backward as
+    the two SEPARATE kernels (rwkv7_mix_bwd, rwkv7_add_ln_bwd).  For the time-mix side: its one-pass backward spills (backbone.py,
+    FUSED_ADD_LN_MIX6), its one-pass forward does not.
+    With wcat, (x1, x_r, x_k, x_v, G): _AddLN followed by _MixLora with ONE forward kernel -- the three lerps that feed full
+    projections (nmix = 3), h = LayerNorm(x1) stored because the branches' GEMM G = h wcat^T (and the backward) read it anyway.  The
+    backward is still the separate stages' own: mix_bwd -> + dG wcat -> add_ln_bwd."""
 
     @staticmethod
     def forward(ctx, x, branch, gamma, beta, eps, mask, params, wcat):
         B, T, D = x.shape
-        x, params, wcat = _c(x), _c(params), _c(wcat)
-        nmix = params.shape[0]
-        gamma_c = _c(gamma.to(x.dtype))
-        beta_c = None if beta is None else _c(beta.to(x.dtype))
-        rows = B * T
-        out = torch.empty(nmix, B, T, D, dtype=x.dtype, device=x.device)
-        h = torch.empty_like(x)
-        mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mean)
-        if branch is not None:
-            branch = _c(branch)
-            x1 = torch.empty_like(x)
-        else:
-            x1 = None
-        nb = max(1, min(-(-rows // _ADD_LN_MIX_RUN), _ADD_LN_MIX_BLOCKS))
-        _call("add_ln_mix_fwd_h", x, B, T, D, nmix, x, branch, gamma_c, beta_c, eps, mask, params, x1, out, h, mean, rstd, nb,
-              _ADD_LN_MIX_RUN)
-        G = torch.mm(h.view(-1, D), wcat.t())
+        x, params, wcat = _c(x), _c(params), _c_opt(wcat)
+        x1, out, h, mean, rstd, gamma_c, _ = _add_ln_mix_fwd(x, branch, gamma, beta, eps, mask, params, store_h=True)
         ctx.has_branch, ctx.has_beta = branch is not None, beta is not None
-        ctx.save_for_backward(x1 if branch is not None else x, h, mean, rstd, gamma_c, mask, params, wcat)
+        ctx.save_for_backward(x1, h, mean, rstd, gamma_c, mask, params, wcat)
+        outs = (x1, *[out[i] for i in range(params.shape[0])])
+        if wcat is None:
+            return outs
         FUSED_MIX_LORA_HITS[0] += 1
-        return ((x1 if branch is not None else x), *[out[i] for i in range(nmix)], G.view(B, T, -1))
+        return (*outs, torch.mm(h.view(-1, D), wcat.t()).view(B, T, -1))
 
     @staticmethod
     def backward(ctx, d_x1, *gs):
         xs, h, mean, rstd, gamma, mask, params, wcat = ctx.saved_tensors
-        B, T, D = xs.shape
         nmix = params.shape[0]
-        rows = B * T
-        dG = gs[nmix]
-        gs = [torch.zeros_like(xs) if g is None else _c(g) for g in gs[:nmix]]
-        nb = max(1, min(-(-rows // _MIX_BWD_ROWS), _MIX_BWD_BLOCKS))
-        dh = torch.empty_like(xs)
-        part_m = torch.empty(nb, nmix, D, dtype=torch.float32, device=xs.device)
-        ptrs = _lib.ptr_array(gs)
-        _call("mix_bwd", xs, B, T, D, nmix, ptrs, h, None, mask, params, dh, part_m, nb, _MIX_BWD_ROWS)
+        dh, part_m, _ = _mix_bwd(gs[:nmix], h, None, mask, params)
         dwcat = None
-        if dG is not None:
-            dG2 = _c(dG).view(-1, dG.shape[-1])
-            dh.view(-1, D).addmm_(dG2, wcat)
-            dwcat = wgrad_splitk(dG2, h.view(-1, D), slabs=WGRAD_SLABS_WCAT)
-        d_x1 = None if d_x1 is None else _c(d_x1)
-        nb2 = min(rows, _BWD_BLOCKS)
-        dx = torch.empty_like(xs)
-        part = torch.empty(nb2, 2, D, dtype=torch.float32, device=xs.device)
-        _call("add_ln_bwd", xs, rows, D, dh, d_x1, xs, mean, rstd, gamma, dx, part, nb2)
-        dp = _colsum(part, xs.dtype)
-        return (dx, (dx if ctx.has_branch else None), dp[0], (dp[1] if ctx.has_beta else None), None, None,
+        if wcat is not None and gs[nmix] is not None:
+            dwcat = _wcat_grads(dh, gs[nmix], wcat, h)
+        dx, dgamma, dbeta = _add_ln_bwd(dh, d_x1, xs, mean, rstd, gamma)
+        return (dx, (dx if ctx.has_branch else None), dgamma, (dbeta if ctx.has_beta else None), None, None,
                 _colsum(part_m, params.dtype), dwcat)
 
 
@@ -1319,7 +1266,7 @@ def add_layer_norm_mix_lora(x, branch, norm, mask, x_r, x_k, x_v, mus, w1s, acts
     params = torch.cat([p.reshape(1, D) for p in (x_r, x_k, x_v)], 0).to(x.dtype)
     wcat = _WcatBuild.apply(len(w1s), *w1s, *mus)
     mr = _mask_rows(mask, x)
-    x1, xr, xk, xv, G = _AddLNMixLora.apply(x, branch, norm.weight, norm.bias, norm.eps, mr, params, wcat)
+    x1, xr, xk, xv, G = _AddLNMixFwd.apply(x, branch, norm.weight, norm.bias, norm.eps, mr, params, wcat)
     hs = _CombineAct.apply(G, mr, tuple(w.shape[0] for w in w1s), tuple(_ACT_CODE[a] for a in acts))
     return x1, xr, xk, xv, list(hs)
 
@@ -1334,8 +1281,8 @@ def add_layer_norm_mix(x, branch, norm, mask, mix_params, fwd_only=False):
     kernels (_AddLNMixFwd)."""
     D = x.shape[-1]
     params = torch.cat([p.reshape(1, D) for p in mix_params], 0).to(x.dtype) if len(mix_params) > 1 else mix_params[0].reshape(1, D).to(x.dtype)
-    node = _AddLNMixFwd if (fwd_only and len(mix_params) > 1) else _AddLNMix
-    res = node.apply(x, branch, norm.weight, norm.bias, norm.eps, _mask_rows(mask, x), params)
+    args = (x, branch, norm.weight, norm.bias, norm.eps, _mask_rows(mask, x), params)
+    res = _AddLNMixFwd.apply(*args, None) if (fwd_only and len(mix_params) > 1) else _AddLNMix.apply(*args)
     return res[0], res[1:]
 
 

@@ -27,8 +27,6 @@ from .backbone import Cache
 
 C = ops.CHUNK_T
 ROW_ZERO = 1 << 30   # RWKV7_STATE_ROW_ZERO (include/rwkv7_hip.h)
-_RUN = 4             # rows per run of the row kernel, as fused._ADD_LN_MIX_RUN
-_BLOCKS = 8192
 
 
 @dataclass
@@ -135,8 +133,9 @@ def add_ln_mix_rows(x, branch, norm, mask, params, prev_src, last_dst, x_prev_rd
     nmix = params.shape[0]
     out = torch.empty(nmix, T, D, dtype=x.dtype, device=x.device)
     x1 = torch.empty_like(x) if branch is not None else None
+    run = fused._ADD_LN_MIX_RUN   # the row kernel walks runs of rows on the grid of the training-side add + LayerNorm + lerp kernels
     _lib.call("rwkv7_add_ln_mix_rows_fwd_bf16", x, T, D, nmix, x, branch, norm.weight, norm.bias, norm.eps, mask, params, prev_src,
-              last_dst, x_prev_rd, x_prev, x1, out, max(1, min(-(-T // _RUN), _BLOCKS)), _RUN)
+              last_dst, x_prev_rd, x_prev, x1, out, fused._grid(T, run, fused._ADD_LN_MIX_BLOCKS), run)
     return (x if branch is None else x1), out
 
 
