@@ -435,6 +435,9 @@ int rwkv7_add_ln_mix_rows_fwd_bf16(int T, int D, int nmix, const void *x, const 
  *                           preserves bits (NaN payloads included).
  *      The row indices and the tables live on the device and are NOT checked here: the caller guarantees rows inside the caches and
  *      distinct destination rows among the active entries (the Python wrapper validates on the host before it copies them over).
+ *      src_tbl and dst_tbl may name the SAME cache, provided no row is both read and written in one call (no active dst_row[i]
+ *      equals an active src_row[j]); a source row may be repeated, which fans it out (ContinuousDecoder.submit_n copies a prompt's
+ *      row to its sibling candidates' rows this way).
  *      n = 0 returns RWKV7_OK without a launch.  RWKV7_EINVAL: NULL table, NULL index array with n > 0, n < 0, layers < 1, n or
  *      layers > 65535, D or H < 1; RWKV7_ESHAPE: D % 8 != 0 or D > 4096; RWKV7_EHEAD: D != 64 * H.  Nothing is launched then. */
 int rwkv7_cache_rows_commit_bf16(int layers, int n, const void *const *src_tbl, void *const *dst_tbl, const int *src_row,
@@ -784,6 +787,27 @@ typedef struct rwkv7_slot_state {
 } rwkv7_slot_state;
 int rwkv7_sample_slots_f32(int rows, const float *logits, long ld, const int *row_slot, const int *allow_lo, const int *allow_hi,
                            const int *suppress, int nsuppress, int max_domain, const rwkv7_slot_state *st, rwkv7_stream_t stream);
+/* rwkv7_sample_slots_lp_f32: rwkv7_sample_slots_f32 that also reports the log-probability of every id it draws
+ * (ContinuousDecoder(logprobs=True): ranking n candidates of one text without a second, teacher-forced pass).  For a live slot
+ * every field of `st` is written bit for bit as rwkv7_sample_slots_f32 writes it, and in addition
+ *   tok_lp[s][step[s]] = x[id] - max - log sum_j exp(x[j] - max)     (if step[s] < seq_ld; row stride seq_ld, like seq)
+ *   cum_lp[s]         += (double)tok_lp[s][step[s]]                  (plain read, add, store: one workgroup owns a slot)
+ * with x the RAW fp32 logits -- temperature 1, before top-k / top-p -- and j over the ids the draw could have produced at this
+ * step: the allowed range minus `suppress`, minus EOS while step[s] < min_until[s].  If no id is allowed (the draw falls back to
+ * the first id of the range) the value is -INFINITY.  A slot that is not live, and a row whose slot is outside [0, slots), leave
+ * tok_lp and cum_lp untouched.  The reductions run thread -> wave -> workgroup in a fixed order: the same logits row gives the same
+ * bits whatever row, slot or grid it is drawn in.  Errors: those of rwkv7_sample_slots_f32, and RWKV7_EINVAL for a null lp,
+ * lp->tok_lp or lp->cum_lp; nothing is launched then.
+ * (Declared as a struct plus a typedef, which a C compiler reads like the one-piece typedefs above; its Python mirror,
+ * continuous.SlotLogprob, is checked against the compiler's layout in tests/test_best_of_abi.py.) */
+struct rwkv7_slot_logprob {
+    float *tok_lp;              /* [slots][seq_ld] log-probability of every drawn id */
+    double *cum_lp;             /* [slots] running sum of the slot's tok_lp, in step order */
+};
+typedef struct rwkv7_slot_logprob rwkv7_slot_logprob;
+int rwkv7_sample_slots_lp_f32(int rows, const float *logits, long ld, const int *row_slot, const int *allow_lo, const int *allow_hi,
+                              const int *suppress, int nsuppress, int max_domain, const rwkv7_slot_state *st,
+                              const rwkv7_slot_logprob *lp, rwkv7_stream_t stream);
 int rwkv7_ras_step_f32(int V, const float *logits, long *tok, long *recent, long *ptr, long *step_i, long n_ignore, int eos, float top_p,
                        int top_k, int win_size, float tau_r, unsigned long long seed, rwkv7_stream_t stream);
 

@@ -45,6 +45,29 @@ class Request:
     top_k: int = 0
     top_p: float = 1.0
     seed: int = 0
+    group_size: int = 1             # candidates of one prompt that are admitted together (GroupScheduler); 1: a request of its own
+    leader: Optional[int] = None    # handle of the group's first candidate, whose prefill this one shares; None: it prefills itself
+
+
+def candidate_seed(seed: int, i: int) -> int:
+    """The Philox key of candidate i of submit_n(..., seed=seed): (seed + i) mod 2^64.  Candidate i draws what a stand-alone
+    submit(..., seed=candidate_seed(seed, i)) draws."""
+    return (int(seed) + int(i)) & ((1 << 64) - 1)
+
+
+def rank_candidates(cum_lp, lengths, length_normalize: bool = True) -> List[int]:
+    """Candidate indices, best first: by the mean log-probability per generated id (length_normalize) or by the sum, largest first;
+    ties go to the lower index.  cum_lp / lengths: one number per candidate (sequences, numpy arrays or tensors of any device; they
+    are small, the ranking runs on the host)."""
+    lp = [float(v) for v in (cum_lp.tolist() if hasattr(cum_lp, "tolist") else cum_lp)]
+    ln = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+    if len(lp) != len(ln):
+        raise ValueError(f"{len(lp)} log-probabilities for {len(ln)} lengths")
+    if any(n < 1 for n in ln):
+        raise ValueError(f"every candidate has at least one id, got lengths {ln}")
+    score = [v / n for v, n in zip(lp, ln)] if length_normalize else lp
+    score = [float("-inf") if s != s else s for s in score]   # a NaN ranks with the impossible candidates
+    return sorted(range(len(lp)), key=lambda i: (-score[i], i))
 
 
 class SlotScheduler:
@@ -168,6 +191,35 @@ class OverlapScheduler(SlotScheduler):
         return not self.pending and not self.busy and not self.staged
 
 
+class GroupScheduler(SlotScheduler):
+    """SlotScheduler whose queue may hold GROUPS: n candidates of one prompt (ContinuousDecoder.submit_n) that are admitted together
+    or not at all, because the prompt is prefilled once and its cache row copied to the siblings.  Admission stays FIFO: a group at
+    the head of the queue waits until n slots are free and holds back everything behind it.  A request outside a group is a group of
+    one, and for those admit() is SlotScheduler's."""
+
+    def submit_group(self, n: int, seeds: Sequence[int], **fields) -> List[int]:
+        """Queue n candidates of one prompt, candidate i with seeds[i]: their handles in candidate order."""
+        if n < 1 or len(seeds) != n:
+            raise ValueError(f"n = {n} with {len(seeds)} seeds: n must be >= 1, one seed per candidate")
+        if n > self.slots:
+            raise ValueError(f"a group of {n} candidates can never be admitted into {self.slots} slots")
+        first = self.submit(seed=seeds[0], group_size=n, **fields)
+        return [first] + [self.submit(seed=s, group_size=n, leader=first, **fields) for s in seeds[1:]]
+
+    def admit(self) -> List[Tuple[int, Request]]:
+        """Pending groups in FIFO order into the free slots, each whole or not at all: [(slot, request)], a group's candidates in
+        order and its first candidate (leader None) ahead of those that name it."""
+        out = []
+        while self.pending and len(self.free) >= self.pending[0].group_size:
+            for _ in range(self.pending[0].group_size):
+                slot = self.free.pop(0)
+                req = self.pending.popleft()
+                self.busy[slot] = req
+                self.remaining[slot] = req.max_new_tokens - 1
+                out.append((slot, req))
+        return out
+
+
 class SlotState(ctypes.Structure):
     """rwkv7_slot_state (include/rwkv7_hip.h)."""
     _fields_ = [("step", ctypes.c_void_p), ("limit", ctypes.c_void_p), ("min_until", ctypes.c_void_p), ("seed", ctypes.c_void_p),
@@ -177,15 +229,25 @@ class SlotState(ctypes.Structure):
                 ("top_k_max", ctypes.c_int), ("eos", ctypes.c_long)]
 
 
+class SlotLogprob(ctypes.Structure):
+    """rwkv7_slot_logprob (include/rwkv7_hip.h)."""
+    _fields_ = [("tok_lp", ctypes.c_void_p), ("cum_lp", ctypes.c_void_p)]
+
+
 def sample_slots(logits: torch.Tensor, st: SlotState, row_slot: Optional[torch.Tensor] = None, allow_lo=None, allow_hi=None,
-                 suppress=None, max_domain: Optional[int] = None):
+                 suppress=None, max_domain: Optional[int] = None, lp: Optional[SlotLogprob] = None):
     """rwkv7_sample_slots_f32 on the current stream: logits fp32 [rows, >= max_domain] (unit column stride); row_slot int32 [rows] or
-    None (row r is slot r); allow_lo / allow_hi int32 [1] device tensors or None; suppress int32 device tensor or None."""
+    None (row r is slot r); allow_lo / allow_hi int32 [1] device tensors or None; suppress int32 device tensor or None.  With lp
+    (tok_lp fp32 [slots, seq_ld], cum_lp fp64 [slots]): rwkv7_sample_slots_lp_f32, the same draw plus the drawn ids' log-probabilities."""
     assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
     if row_slot is not None:
         assert row_slot.dtype == torch.int32 and row_slot.is_contiguous() and row_slot.numel() == logits.shape[0]
-    _lib.call("rwkv7_sample_slots_f32", logits, logits.shape[0], logits, logits.stride(0), row_slot, allow_lo, allow_hi, suppress,
-              0 if suppress is None else suppress.numel(), int(logits.shape[1] if max_domain is None else max_domain), ctypes.byref(st))
+    args = (logits.shape[0], logits, logits.stride(0), row_slot, allow_lo, allow_hi, suppress, 0 if suppress is None else suppress.numel(),
+            int(logits.shape[1] if max_domain is None else max_domain), ctypes.byref(st))
+    if lp is None:
+        _lib.call("rwkv7_sample_slots_f32", logits, *args)
+    else:
+        _lib.call("rwkv7_sample_slots_lp_f32", logits, *args, ctypes.byref(lp))
 
 
 class ContinuousDecoder:
@@ -207,17 +269,26 @@ class ContinuousDecoder:
     the first ids.  Until then a reserved slot is an idle slot: the step overwrites its rows with stale values and the commit
     replaces all of them.  Only one group is in flight at a time; every decision reads host counters, never the device, so a
     submission sequence gives the same schedule on every run.  Every bucket is captured at construction.  Ids equal
-    admission="graph"'s for the same pack composition; admission_log lists per group (replays at launch, replays at commit, [handles])."""
+    admission="graph"'s for the same pack composition; admission_log lists per group (replays at launch, replays at commit, [handles]).
+
+    Best-of-n: submit_n(n, ...) queues n candidates of one prompt, admitted together (GroupScheduler), the prompt prefilled once and
+    its cache row copied to the siblings' rows (_fan_out); logprobs=True makes the captured step and the admission draw call
+    rwkv7_sample_slots_lp_f32, which also writes every drawn id's log-probability (tok_lp [slots, cap] fp32) and the running fp64
+    sum (cum_lp [slots]); take_logprobs(handle) hands them out once the handle has been returned, rank_candidates orders them.
+    logprobs=True changes no id; with logprobs=False and no submit_n every code path and launch is the one of before."""
+
+    logprobs = False   # the default of the constructor's switch; nothing below looks at tok_lp / cum_lp without it
+    lp = None          # SlotLogprob with logprobs=True: the draws go through rwkv7_sample_slots_lp_f32
 
     def __init__(self, model, slots: int = 32, max_new_tokens_cap: int = 3000, eos_token_id: Optional[int] = None,
                  pad_token_id: Optional[int] = None, suppress_tokens: Optional[Sequence[int]] = None, check_every: int = 16,
                  admission: str = "eager", prefill_max_seqs: int = 8, prefill_buckets: Sequence[int] = (256, 512, 1024, 2048, 4096),
-                 overlap_replays: int = 8):
+                 overlap_replays: int = 8, logprobs: bool = False):
         if admission not in ("eager", "graph", "overlap"):
             raise ValueError(f"admission = {admission!r}: 'eager', 'graph' or 'overlap'")
         if overlap_replays < 0:
             raise ValueError("overlap_replays must be >= 0")
-        self.admission, self.overlap_replays = admission, int(overlap_replays)
+        self.admission, self.overlap_replays, self.logprobs = admission, int(overlap_replays), bool(logprobs)
         check_slots(slots)   # 1..32, or 64 / 96 / 128: ValueError before anything touches the device
         if max_new_tokens_cap < 1 or check_every < 1:
             raise ValueError("max_new_tokens_cap and check_every must be >= 1")
@@ -276,8 +347,14 @@ class ContinuousDecoder:
         st.emb, st.x, st.D, st.slots, st.top_k_max = emb_w.data_ptr(), self.x.data_ptr(), D, S, MAX_TOP_K
         st.eos = -1 if self.eos is None else self.eos
         self.st = st
+        if self.logprobs:   # what rwkv7_sample_slots_lp_f32 writes next to seq / step
+            self.tok_lp = torch.zeros(S, self.cap, dtype=torch.float32, device=dev)
+            self.cum_lp = torch.zeros(S, dtype=torch.float64, device=dev)
+            self.lp = SlotLogprob(self.tok_lp.data_ptr(), self.cum_lp.data_ptr())
+        self._lp_done: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}   # handle -> (tok_lp[:n], cum_lp) until take_logprobs()
+        self._fan_tbl = None   # submit_n: the cache's own field table, source and destination of the fan-out copy
 
-        self.sched = OverlapScheduler(slots) if admission == "overlap" else SlotScheduler(slots)
+        self.sched = OverlapScheduler(slots) if admission == "overlap" else GroupScheduler(slots)
         self.dstep = step_for(m.model, m.lm_head, self.cache)
         # capture the step.  Every slot is idle (live = 0): the draw writes nothing, and the warm-up's change to the state of idle
         # rows does not matter (admission resets a row before it is used)
@@ -299,13 +376,49 @@ class ContinuousDecoder:
             self._init_overlap(int(prefill_max_seqs), prefill_buckets)
 
     def _step(self):
-        sample_slots(self.dstep(self.x), self.st, None, self.allow_lo, self.allow_hi, self.suppress, self.max_domain)
+        sample_slots(self.dstep(self.x), self.st, None, self.allow_lo, self.allow_hi, self.suppress, self.max_domain, self.lp)
 
     # ---- public interface ----------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def submit(self, input_ids=None, inputs_embeds=None, max_new_tokens: int = 256, min_new_tokens: int = 0, do_sample: bool = False,
                temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: Optional[int] = None) -> int:
         """Queue one request (a prompt of T ids [T] / [1, T] or embeddings [T, D] / [1, T, D]); returns its handle.  Non-blocking."""
+        seed = int(fresh_seed() if seed is None else seed) & ((1 << 64) - 1)
+        return self.sched.submit(seed=seed, **self._request_fields(input_ids, inputs_embeds, max_new_tokens, min_new_tokens, do_sample,
+                                                                   temperature, top_k, top_p))
+
+    @torch.no_grad()
+    def submit_n(self, n: int, input_ids=None, inputs_embeds=None, max_new_tokens: int = 256, min_new_tokens: int = 0,
+                 do_sample: bool = False, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: Optional[int] = None) -> List[int]:
+        """Queue n candidates of ONE prompt (submit()'s arguments): their handles in candidate order.  Candidate i draws with the key
+        candidate_seed(seed, i) and is, id for id, the request submit(..., seed=candidate_seed(seed, i)) would be.  The group is admitted
+        whole, when n slots are free: the prompt is prefilled once and its cache row copied to the other candidates' rows.
+        n > slots: ValueError.  n > 1 with admission="overlap": ValueError (the staging index arrays hold one entry per prompt)."""
+        n = int(n)
+        if n < 1 or n > self.slots:
+            raise ValueError(f"n = {n} candidates outside 1..{self.slots} (slots): a group is admitted whole")
+        if n > 1 and self.admission == "overlap":
+            raise ValueError("submit_n with n > 1 is not supported with admission='overlap': its staging rows and index arrays are sized "
+                             "to prompts; use admission='eager' or 'graph'")
+        fields = self._request_fields(input_ids, inputs_embeds, max_new_tokens, min_new_tokens, do_sample, temperature, top_k, top_p)
+        seed = int(fresh_seed() if seed is None else seed) & ((1 << 64) - 1)
+        if n == 1:
+            return [self.sched.submit(seed=seed, **fields)]
+        return self.sched.submit_group(n, [candidate_seed(seed, i) for i in range(n)], **fields)
+
+    def take_logprobs(self, handle: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(tok_lp [n] fp32, cum_lp fp64 scalar) of a request that step() / run() has returned, both on the device: the log-probability
+        of each of its n ids under the raw logits (temperature 1, before top-k / top-p, over the ids the draw could produce) and their
+        sum, added in step order in fp64.  Needs logprobs=True; a handle's result can be taken once."""
+        if not self.logprobs:
+            raise ValueError("take_logprobs needs ContinuousDecoder(..., logprobs=True)")
+        try:
+            return self._lp_done.pop(handle)
+        except KeyError:
+            raise KeyError(f"handle {handle}: not finished yet (step() / run() has not returned it), unknown, or already taken") from None
+
+    def _request_fields(self, input_ids, inputs_embeds, max_new_tokens, min_new_tokens, do_sample, temperature, top_k, top_p) -> dict:
+        """submit()'s argument checks and the prompt's embeddings: Request's fields but the handle and the seed."""
         if (input_ids is None) == (inputs_embeds is None):
             raise ValueError("pass exactly one of input_ids or inputs_embeds")
         if not 1 <= int(max_new_tokens) <= self.cap:
@@ -321,9 +434,8 @@ class ContinuousDecoder:
             e = inputs_embeds.reshape(-1, inputs_embeds.shape[-1]).to(self.device, self.model.dtype)
         if e.shape[0] < 1 or e.shape[1] != self.model.config.hidden_size:
             raise ValueError(f"prompt of shape {tuple(e.shape)}")
-        seed = int(fresh_seed() if seed is None else seed) & ((1 << 64) - 1)
-        return self.sched.submit(embeds=e.detach(), max_new_tokens=int(max_new_tokens), min_new_tokens=int(min_new_tokens or 0),
-                                 do_sample=bool(do_sample), temperature=float(temperature or 1.0), top_k=top_k, top_p=top_p, seed=seed)
+        return dict(embeds=e.detach(), max_new_tokens=int(max_new_tokens), min_new_tokens=int(min_new_tokens or 0),
+                    do_sample=bool(do_sample), temperature=float(temperature or 1.0), top_k=top_k, top_p=top_p)
 
     @torch.no_grad()
     def step(self) -> List[Tuple[int, torch.Tensor]]:
@@ -370,6 +482,8 @@ class ContinuousDecoder:
             req = self.sched.retire(s)
             n = req.max_new_tokens if steps is None else int(steps[s])
             out.append((req.handle, self.seq[s, :n].clone()))
+            if self.logprobs:
+                self._lp_done[req.handle] = (self.tok_lp[s, :n].clone(), self.cum_lp[s].clone())
         return out
 
     def _admit(self):
@@ -377,10 +491,12 @@ class ContinuousDecoder:
         if not took:
             return
         m, dev = self.model, self.device
-        slots = [s for s, _ in took]
+        # the requests that prefill: all of them, but for the candidates of a submit_n group after its first, which get a copy of its rows
+        heads = [(s, r) for s, r in took if r.leader is None]
+        slots = [s for s, _ in heads]
         if self.prefill is not None:
-            return self._admit_graph(took, slots)
-        lens = [r.embeds.shape[0] for _, r in took]
+            return self._admit_graph(took, heads, slots)
+        lens = [r.embeds.shape[0] for _, r in heads]
         cu = [0]
         for n in lens:
             cu.append(cu[-1] + n)
@@ -389,20 +505,45 @@ class ContinuousDecoder:
             st.att_x_prev.index_fill_(0, rows64, 0)
             st.att_kv.index_fill_(0, rows64, 0)
             st.ffn_x_prev.index_fill_(0, rows64, 0)
-        packed = torch.cat([r.embeds for _, r in took], 0).unsqueeze(0)
+        packed = torch.cat([r.embeds for _, r in heads], 0).unsqueeze(0)
         cu_t = torch.tensor(cu, dtype=torch.int32)
         h = m.model(inputs_embeds=packed, cu_seqlens=cu_t, past_key_values=self.cache, cache_rows=torch.tensor(slots)).last_hidden_state
         last = torch.tensor([c - 1 for c in cu[1:]], dtype=torch.int64).to(dev, non_blocking=True)
         logits = m.lm_head(h[0].index_select(0, last)).float()
+        if len(heads) < len(took):
+            logits, slots = self._fan_out(took, heads, logits)
+            rows64 = torch.tensor(slots, dtype=torch.int64).to(dev, non_blocking=True)
         self._admit_draw(took, logits, rows64, torch.tensor(slots, dtype=torch.int32).to(dev, non_blocking=True))
 
-    def _admit_graph(self, took, slots):
+    def _admit_graph(self, took, heads, slots):
         """Admission through PackedPrefill: the rows are reset by the kernels (zero marks), the layout goes over as one pinned index
         block per replay, and nothing is read back."""
-        h_last = self.prefill.run([r.embeds for _, r in took], slots, fresh=True)
+        h_last = self.prefill.run([r.embeds for _, r in heads], slots, fresh=True)
         logits = self.model.lm_head(h_last).float()
+        if len(heads) < len(took):
+            logits, slots = self._fan_out(took, heads, logits)
         row_slot = torch.tensor(slots, dtype=torch.int32).pin_memory().to(self.device, non_blocking=True)
         self._admit_draw(took, logits, row_slot.long(), row_slot)
+
+    def _fan_out(self, took, heads, logits):
+        """submit_n: the prefilled rows of the groups' first candidates -> their siblings' rows, every field of every layer, for all groups
+        admitted together in ONE rwkv7_cache_rows_commit_bf16 launch over the cache's own field table (a repeated source row fans out; no
+        row is both read and written: sources are first candidates, destinations are not).  Returns (one logits row per admitted
+        request -- its prompt's, gathered --, every admitted slot in `took` order)."""
+        from .prefill import cache_field_table, cache_rows_commit, check_commit_rows
+        dev, cfg = self.device, self.model.config
+        slot_of = {r.handle: s for s, r in heads}
+        row_of = {r.handle: i for i, (_, r) in enumerate(heads)}
+        sibs = [(slot_of[r.leader], s) for s, r in took if r.leader is not None]
+        src, dst = check_commit_rows([a for a, _ in sibs], [b for _, b in sibs], self.slots, self.slots)
+        if set(src) & set(dst):
+            raise RuntimeError(f"fan-out rows {src} -> {dst}: a row is both read and written")
+        if self._fan_tbl is None:
+            self._fan_tbl = cache_field_table(self.cache)
+        rows = torch.tensor([src, dst], dtype=torch.int32).to(dev, non_blocking=True)
+        cache_rows_commit(self._fan_tbl, self._fan_tbl, rows[0], rows[1], len(sibs), len(self.cache), cfg.hidden_size, cfg.num_heads)
+        pick = torch.tensor([row_of[r.handle if r.leader is None else r.leader] for _, r in took], dtype=torch.int64).to(dev, non_blocking=True)
+        return logits.index_select(0, pick), [s for s, _ in took]
 
     # ---- admission="overlap" -------------------------------------------------------------------------------------------------
     def _init_overlap(self, max_seqs, buckets):
@@ -522,4 +663,6 @@ class ContinuousDecoder:
             self._par_dev[k].copy_(v.pin_memory(), non_blocking=True)
         self.step_t.index_fill_(0, rows64, 0)
         self.live.index_fill_(0, rows64, 1)
-        sample_slots(logits, self.st, row_slot, self.allow_lo, self.allow_hi, self.suppress, self.max_domain)
+        if self.logprobs:
+            self.cum_lp.index_fill_(0, rows64, 0)
+        sample_slots(logits, self.st, row_slot, self.allow_lo, self.allow_hi, self.suppress, self.max_domain, self.lp)

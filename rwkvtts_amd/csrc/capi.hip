@@ -88,6 +88,8 @@ int wgrad_mid_bf16(long, int, int, int, const void *, const void *, float *, hip
 int sample_rows_f32(int, int, const float *, long, const int *, const int *, const int *, const int *, const int *, int, int, int, int, float,
                     float, unsigned long long, const long *, long *, const void *, int, long, hipStream_t);
 int sample_slots_f32(int, const float *, long, const int *, const int *, const int *, const int *, int, int, const void *, hipStream_t);
+int sample_slots_lp_f32(int, const float *, long, const int *, const int *, const int *, const int *, int, int, const void *, float *, double *,
+                        hipStream_t);
 int ras_step_f32(int, const float *, long *, long *, long *, long *, long, int, float, int, int, float, unsigned long long, hipStream_t);
 int xy_frame_step(int, int, int, long, long, long, long, long, const long *, int, int, const long *, long *, long *, long *, long *, long *,
                   unsigned char *, long *, hipStream_t);
@@ -928,16 +930,28 @@ int rwkv7_sample_rows_tail_f32(int rows, const float *logits, long ld, const int
     return rwkv7::sample_rows_f32(rows, 1, logits, ld, seg_off, seg_len, allow_lo, allow_hi, suppress, nsuppress, max_domain, do_sample, top_k,
                                   top_p, temperature, seed, step, out, tail, min_eos_id, min_eos_until, (hipStream_t)stream);
 }
+// what rwkv7_sample_slots_f32 and rwkv7_sample_slots_lp_f32 both refuse before a launch
+static bool sample_slots_args_ok(int rows, const float *logits, const int *allow_lo, const int *allow_hi, const int *suppress, int nsuppress,
+                                 int max_domain, const rwkv7_slot_state *st) {
+    if (rows <= 0 || !st || !logits || max_domain <= 0 || nsuppress < 0 || (nsuppress > 0 && !suppress) || (!allow_lo != !allow_hi))
+        return false;
+    return !(any_null({(const void *)st->step, (const void *)st->limit, (const void *)st->min_until, (const void *)st->seed,
+                       (const void *)st->inv_temp, (const void *)st->top_k, (const void *)st->top_p, (const void *)st->do_sample,
+                       (const void *)st->live, (const void *)st->ids, (const void *)st->seq}) ||
+             st->seq_ld <= 0 || st->slots <= 0 || (st->emb && (!st->x || st->D <= 0)));
+}
 int rwkv7_sample_slots_f32(int rows, const float *logits, long ld, const int *row_slot, const int *allow_lo, const int *allow_hi,
                            const int *suppress, int nsuppress, int max_domain, const rwkv7_slot_state *st, rwkv7_stream_t stream) {
-    if (rows <= 0 || !st || !logits || max_domain <= 0 || nsuppress < 0 || (nsuppress > 0 && !suppress) || (!allow_lo != !allow_hi))
-        return RWKV7_EINVAL;
-    if (any_null({(const void *)st->step, (const void *)st->limit, (const void *)st->min_until, (const void *)st->seed,
-                  (const void *)st->inv_temp, (const void *)st->top_k, (const void *)st->top_p, (const void *)st->do_sample,
-                  (const void *)st->live, (const void *)st->ids, (const void *)st->seq}) ||
-        st->seq_ld <= 0 || st->slots <= 0 || (st->emb && (!st->x || st->D <= 0)))
-        return RWKV7_EINVAL;
+    if (!sample_slots_args_ok(rows, logits, allow_lo, allow_hi, suppress, nsuppress, max_domain, st)) return RWKV7_EINVAL;
     return rwkv7::sample_slots_f32(rows, logits, ld, row_slot, allow_lo, allow_hi, suppress, nsuppress, max_domain, st, (hipStream_t)stream);
+}
+int rwkv7_sample_slots_lp_f32(int rows, const float *logits, long ld, const int *row_slot, const int *allow_lo, const int *allow_hi,
+                              const int *suppress, int nsuppress, int max_domain, const rwkv7_slot_state *st, const rwkv7_slot_logprob *lp,
+                              rwkv7_stream_t stream) {
+    if (!sample_slots_args_ok(rows, logits, allow_lo, allow_hi, suppress, nsuppress, max_domain, st)) return RWKV7_EINVAL;
+    if (!lp || !lp->tok_lp || !lp->cum_lp) return RWKV7_EINVAL;
+    return rwkv7::sample_slots_lp_f32(rows, logits, ld, row_slot, allow_lo, allow_hi, suppress, nsuppress, max_domain, st, lp->tok_lp,
+                                      lp->cum_lp, (hipStream_t)stream);
 }
 int rwkv7_ras_step_f32(int V, const float *logits, long *tok, long *recent, long *ptr, long *step_i, long n_ignore, int eos, float top_p,
                        int top_k, int win_size, float tau_r, unsigned long long seed, rwkv7_stream_t stream) {

@@ -18,6 +18,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "sampling_common.h"
 
 namespace rwkv7 {
@@ -151,10 +153,30 @@ struct SlotState {
 // launch (workgroup 0) with the slot's key, step counter, parameters and min-EOS bound, so a request's ids do not depend on the slot
 // it occupies or on when it was admitted; then the slot's bookkeeping (output column, next id, its embedding row, step, live flag).
 // The body repeats sample_rows_kernel's draw instead of sharing it so that the existing kernels stay byte-for-byte as they were.
-template <int EPT>
+//
+// LP (rwkv7_sample_slots_lp_f32): the log-probability of the drawn id as well.  Everything under `if constexpr (LP)` is extra; with
+// LP = false the body is the draw as it always was.  The probability is the one of the RAW logits (temperature 1, no top-k / top-p)
+// over the ids the draw could produce at this step -- the allowed range minus `suppress`, minus EOS while it is barred -- so a second
+// copy of the row stays unscaled in registers until its maximum and its exp-sum are known, which is before select_bins needs the
+// registers for its bins.  Both reductions go thread -> wave butterfly -> the four waves in fixed order: the value depends on the
+// row's contents and the thread layout only, never on the row, the slot or the grid.
+struct SlotStateLp : SlotState {
+    float *tok_lp;    // [slots][seq_ld]
+    double *cum_lp;   // [slots]
+};
+__device__ __forceinline__ float block_fmax(float v, SmpShared &sm) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sm.red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(sm.red[0], sm.red[1]), fmaxf(sm.red[2], sm.red[3]));
+}
+template <int EPT, bool LP>
 __global__ __launch_bounds__(kSmpThreads) void sample_slots_kernel(const float *__restrict__ logits, long ld, const int *__restrict__ row_slot,
                                                                    const int *__restrict__ allow_lo, const int *__restrict__ allow_hi,
-                                                                   const int *__restrict__ suppress, int nsuppress, int max_domain, SlotState st) {
+                                                                   const int *__restrict__ suppress, int nsuppress, int max_domain,
+                                                                   typename std::conditional<LP, SlotStateLp, SlotState>::type st) {
     __shared__ SmpShared sm;
     const int row = blockIdx.x, tid = threadIdx.x;
     const int s = row_slot ? row_slot[row] : row;
@@ -168,19 +190,39 @@ __global__ __launch_bounds__(kSmpThreads) void sample_slots_kernel(const float *
     const int lo = allow_lo ? max(allow_lo[0], 0) : 0, hi = allow_hi ? min(allow_hi[0], lo + max_domain) : max_domain;
     const int m = hi - lo;
     Vals<EPT> x;
+    Vals<LP ? EPT : 1> raw;   // LP: the same elements at temperature 1
 #pragma unroll
     for (int e = 0; e < EPT; e++) {
         const int j = tid + kSmpThreads * e;
         const float t = xg[lo + min(j, m - 1)];
         x.v[e] = j < m ? t * inv_temp : -INFINITY;
+        if constexpr (LP) raw.v[e] = j < m ? t : -INFINITY;
     }
     for (int t = 0; t < nsuppress; t++) {
         const int sidx = suppress[t] - lo;
-        if (sidx >= 0 && sidx < m && (sidx & (kSmpThreads - 1)) == tid) x.drop(sidx);
+        if (sidx >= 0 && sidx < m && (sidx & (kSmpThreads - 1)) == tid) {
+            x.drop(sidx);
+            if constexpr (LP) raw.drop(sidx);
+        }
     }
     if (st.eos >= 0 && step < st.min_until[s]) {
         const long sidx = st.eos - lo;
-        if (sidx >= 0 && sidx < m && (sidx & (kSmpThreads - 1)) == tid) x.drop((int)sidx);
+        if (sidx >= 0 && sidx < m && (sidx & (kSmpThreads - 1)) == tid) {
+            x.drop((int)sidx);
+            if constexpr (LP) raw.drop((int)sidx);
+        }
+    }
+    float lp_max = 0.f, lp_logz = 0.f;   // LP: max and log sum exp(. - max) over the ids that were not dropped
+    if constexpr (LP) {
+        float mx = raw.v[0];
+#pragma unroll
+        for (int e = 1; e < EPT; e++) mx = fmaxf(mx, raw.v[e]);
+        lp_max = block_fmax(mx, sm);
+        float z = 0.f;
+#pragma unroll
+        for (int e = 0; e < EPT; e++) z += __expf(raw.v[e] - lp_max);   // a dropped id: exp(-inf) = 0
+        lp_logz = __logf(block_sum(z, sm));
+        __syncthreads();   // sm.red is free again: select_bins writes it without a barrier of its own
     }
     int choice;
     if (!do_sample) {
@@ -221,6 +263,12 @@ __global__ __launch_bounds__(kSmpThreads) void sample_slots_kernel(const float *
         st.ids[s] = id;
         st.step[s] = step + 1;
         st.live[s] = id != st.eos && step + 1 < st.limit[s];
+        if constexpr (LP) {
+            // nothing allowed (every id dropped or -inf; the id is the fall-back): -inf, not the NaN of (-inf) - (-inf)
+            const float lp = lp_max == -INFINITY ? -INFINITY : (xg[id] - lp_max) - lp_logz;
+            if (step >= 0 && step < st.seq_ld) st.tok_lp[(long)s * st.seq_ld + step] = lp;
+            st.cum_lp[s] += (double)lp;   // one workgroup owns the slot: a plain read, add, store
+        }
     }
     if (st.emb) {
         const uint16_t *src = st.emb + id * st.D;
@@ -442,11 +490,29 @@ int sample_slots_f32(int rows, const float *logits, long ld, const int *row_slot
     (void)hipGetLastError();
     const dim3 grid(rows), block(kSmpThreads);
     if (max_domain <= kEptS * kSmpThreads)
-        sample_slots_kernel<kEptS><<<grid, block, 0, stream>>>(logits, ld, row_slot, allow_lo, allow_hi, suppress, nsuppress, max_domain, st);
+        sample_slots_kernel<kEptS, false><<<grid, block, 0, stream>>>(logits, ld, row_slot, allow_lo, allow_hi, suppress, nsuppress, max_domain, st);
     else if (max_domain <= kEptM * kSmpThreads)
-        sample_slots_kernel<kEptM><<<grid, block, 0, stream>>>(logits, ld, row_slot, allow_lo, allow_hi, suppress, nsuppress, max_domain, st);
+        sample_slots_kernel<kEptM, false><<<grid, block, 0, stream>>>(logits, ld, row_slot, allow_lo, allow_hi, suppress, nsuppress, max_domain, st);
     else
-        sample_slots_kernel<kEptL><<<grid, block, 0, stream>>>(logits, ld, row_slot, allow_lo, allow_hi, suppress, nsuppress, max_domain, st);
+        sample_slots_kernel<kEptL, false><<<grid, block, 0, stream>>>(logits, ld, row_slot, allow_lo, allow_hi, suppress, nsuppress, max_domain, st);
+    return (int)hipGetLastError();
+}
+
+int sample_slots_lp_f32(int rows, const float *logits, long ld, const int *row_slot, const int *allow_lo, const int *allow_hi,
+                        const int *suppress, int nsuppress, int max_domain, const void *st_, float *tok_lp, double *cum_lp, hipStream_t stream) {
+    SlotStateLp st;
+    static_cast<SlotState &>(st) = *(const SlotState *)st_;
+    st.tok_lp = tok_lp;
+    st.cum_lp = cum_lp;
+    if (max_domain > kSmpMaxN || nsuppress > 256 || st.top_k_max < 0 || st.top_k_max > 64 || (st.emb && st.D % 8 != 0)) return -4;
+    (void)hipGetLastError();
+    const dim3 grid(rows), block(kSmpThreads);
+    if (max_domain <= kEptS * kSmpThreads)
+        sample_slots_kernel<kEptS, true><<<grid, block, 0, stream>>>(logits, ld, row_slot, allow_lo, allow_hi, suppress, nsuppress, max_domain, st);
+    else if (max_domain <= kEptM * kSmpThreads)
+        sample_slots_kernel<kEptM, true><<<grid, block, 0, stream>>>(logits, ld, row_slot, allow_lo, allow_hi, suppress, nsuppress, max_domain, st);
+    else
+        sample_slots_kernel<kEptL, true><<<grid, block, 0, stream>>>(logits, ld, row_slot, allow_lo, allow_hi, suppress, nsuppress, max_domain, st);
     return (int)hipGetLastError();
 }
 
