@@ -14,6 +14,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launchers.h"
+
 namespace rwkv7 {
 
 constexpr int kDigestTile = 8192;   // words per workgroup of stage 1: FIXED, as in grad_ops.hip (rwkv7_buf_digest_workspace_bytes)

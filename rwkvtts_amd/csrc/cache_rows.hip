@@ -11,6 +11,8 @@
 // negative index of either kind skips the entry.  Destination rows must be distinct among the active entries.
 #include <hip/hip_runtime.h>
 
+#include "launchers.h"
+
 namespace rwkv7 {
 
 constexpr int kCommitThreads = 256, kCommitVecs = 4;

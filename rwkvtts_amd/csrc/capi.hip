@@ -1,136 +1,16 @@
 // rwkvtts_amd/csrc/capi.hip -- extern "C" surface of librwkv7_hip.so (declared in include/rwkv7_hip.h).
 // Argument checking mirrors the reference's asserts (wkv7_cuda.cu:136, rwkv7_state_fwd_fp16.cu:61,
 // rwkv_s2s_single_ffn.py:19-21) but reports through the return code instead of aborting the process.
+// The launchers it calls are declared in launchers.h.  The entries of the fused row stages (rwkv7_mix_*, rwkv7_add_ln_*,
+// rwkv7_tmix_*, rwkv7_relusq_*) are not here: each is one checked launcher beside its kernel, at the end of elementwise.hip.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #include "../../include/rwkv7_hip.h"
+#include "launchers.h"
+#include "ln_row.h"   // row_width_ok
 
-namespace rwkv7 {
-int wkv_fwd_bf16(int, int, int, const void *, const void *, const void *, const void *, const void *, const void *,
-                 void *, float *, float *, float *, int, hipStream_t);
-int wkv_fwd_f32(int, int, int, const void *, const void *, const void *, const void *, const void *, const void *,
-                void *, float *, float *, float *, int, hipStream_t);
-int wkv_bwd_bf16(int, int, int, const void *, const void *, const void *, const void *, const void *, const void *,
-                 const void *, const float *, const float *, void *, void *, void *, void *, void *, void *,
-                 hipStream_t);
-int wkv_bwd_f32(int, int, int, const void *, const void *, const void *, const void *, const void *, const void *,
-                const void *, const float *, const float *, void *, void *, void *, void *, void *, void *,
-                hipStream_t);
-
-int wkv_bwd_split_bf16(int, int, int, const void *, const void *, const void *, const void *, const void *, const void *,
-                       const void *, const float *, const float *, void *const *, void *const *, void *const *, void *,
-                       void *const *, void *const *, int, hipStream_t);
-int wkv_bwd_split_f32(int, int, int, const void *, const void *, const void *, const void *, const void *, const void *,
-                      const void *, const float *, const float *, void *const *, void *const *, void *const *, void *,
-                      void *const *, void *const *, int, hipStream_t);
-int chunk_prep_bf16(int, int, int, const void *, const void *, const void *, float *, hipStream_t);
-int chunk_prep_f32(int, int, int, const void *, const void *, const void *, float *, hipStream_t);
-int chunk_fwd_bf16(int, int, int, const void *, const void *, const void *, const void *, const void *, const void *,
-                   const float *, void *, float *, void *, const int *, int, hipStream_t);
-int chunk_fwd_f32(int, int, int, const void *, const void *, const void *, const void *, const void *, const void *,
-                  const float *, void *, float *, void *, const int *, int, hipStream_t);
-int chunk_debug_mma(const float *, const float *, float *, float *, hipStream_t);
-int chunk_debug_tr16(const uint16_t *, const int *, uint16_t *, hipStream_t);
-int gemv32_bf16(int, int, int, const void *, const void *, const void *, void *, hipStream_t);
-int ce_fwd_bwd(long, int, long, void *, const long *, long, float, float *, float, hipStream_t);
-int kl_acc_fwd_bwd(long, int, long, const void *, void *, const long *, long, float, float, float, float *, int *, hipStream_t);
-int head_eval(long, int, long, const void *, const long *, long, int, float, float, float *, int *, int *, hipStream_t);
-int seq_scores(long, const long *, const float *, const int *, const long *, long, double *, long *, long *, float *, long *, hipStream_t);
-int adamw_step(long, float *, const void *, float *, float *, void *, const uint8_t *, const float *, const float *, float, float, float, float,
-               float, float, float, hipStream_t);
-int adamw_clip_step(long, float *, const void *, float *, float *, void *, const uint8_t *, const float *, const float *, const float *,
-                    float, float, float, float, float, float, float, float, hipStream_t);
-int grad_sumsq_bf16(long, const void *, float *, float *, int, hipStream_t);
-int grad_accum_bf16(long, float *, const void *, int, hipStream_t);
-int grad_fold_bf16(long, const float *, void *, float, hipStream_t);
-long buf_digest_tiles(long);
-int buf_digest_u32(long, long, const void *, void *, unsigned long long *, unsigned long long *, int, hipStream_t);
-int lora32_bf16(int, int, int, int, int, const void *, const void *, const void *, const void *, void *, hipStream_t);
-int chunk_bseq_bf16(int, int, int, const void *, const void *, const void *, const void *, const void *, const float *, void *,
-                    float *, const int *, int, hipStream_t);
-int chunk_bseq_state_seq_bf16(int, int, int, const void *, const void *, const void *, const void *, const void *, const float *,
-                              void *, float *, const int *, int, const float *, float *, hipStream_t);
-int chunk_fwd9_state_seq_bf16(int, int, int, const void *, const void *, const void *, const void *, const void *, const void *,
-                              const float *, void *, float *, void *, const int *, int, const float *, float *, hipStream_t);
-int gemm_nt4_bf16(int, int, int, const void *, const void *, void *, const void *, int, hipStream_t);
-struct MixLoraDesc {
-    int nb;
-    int r[4], off[4];
-    int act[4];
-    const void *w1[4];
-    const void *mu[4];
-    void *out[4];
-    void *out2[4];
-};
-int mix_lora_wcat_fwd(const MixLoraDesc &, int, int, void *, hipStream_t);
-int mix_lora_wcat_bwd(const MixLoraDesc &, int, int, const void *, hipStream_t);
-int mix_lora_combine_fwd(const MixLoraDesc &, long, int, int, const void *, const void *, hipStream_t);
-int mix_lora_combine_bwd(const MixLoraDesc &, long, int, int, const void *, void *, hipStream_t);
-struct LoraDownDesc {
-    int nb;
-    int r[4], off[4];
-    int act[4];
-    const void *w1[4];
-    const void *mu[4];
-    void *out[4];
-    int tile0[5];
-};
-int lora_down_pack(const LoraDownDesc &, int, int, void *, hipStream_t);
-int lora_down_fwd(LoraDownDesc &, int, long, int, int, const void *, const void *, const void *, hipStream_t);
-int chunk_bwd_out10_bf16(int, int, int, const void *, const void *, const void *, const void *, const void *, const void *, const void *,
-                         const void *, const float *, const float *, const void *, void *, void *, void *, void *, void *, void *, hipStream_t);
-int sum_slabs_bf16(long, int, const float *, void *, int, hipStream_t);
-int transpose_bf16(int, int, const void *, void *, hipStream_t);
-int gather_rows16(long, int, const void *, const int *, void *, hipStream_t);
-int wgrad_skinny_bf16(long, int, int, int, const void *, const void *, float *, hipStream_t);
-int wgrad_mid_bf16(long, int, int, int, const void *, const void *, float *, hipStream_t);
-int sample_rows_f32(int, int, const float *, long, const int *, const int *, const int *, const int *, const int *, int, int, int, int, float,
-                    float, unsigned long long, const long *, long *, const void *, int, long, hipStream_t);
-int sample_slots_f32(int, const float *, long, const int *, const int *, const int *, const int *, int, int, const void *, hipStream_t);
-int sample_slots_lp_f32(int, const float *, long, const int *, const int *, const int *, const int *, int, int, const void *, float *, double *,
-                        hipStream_t);
-int ras_step_f32(int, const float *, long *, long *, long *, long *, long, int, float, int, int, float, unsigned long long, hipStream_t);
-int xy_frame_step(int, int, int, long, long, long, long, long, const long *, int, int, const long *, long *, long *, long *, long *, long *,
-                  unsigned char *, long *, hipStream_t);
-int xy_embed_bf16(int, int, int, const void *const *, const long *, void *, hipStream_t);
-int xy_slots_draw_f32(int, const float *, long, const int *, const int *, const int *, const int *, const int *, int, const void *, hipStream_t);
-int xy_slots_frame_bf16(int, const int *, const void *, hipStream_t);
-int ras_slots_f32(int, int, const float *, long, const int *, const void *, hipStream_t);
-int decode_layer_ptrs();
-size_t decode_workspace_bytes(int, int, int, int, int, int, int, int, int);
-int decode_step_bf16(int, int, int, int, int, int, int, int, int, int, float, float, const void *const *, const void *const *, const void *,
-                     const void *, const void *, const void *, const void *, float *, void *, int, hipStream_t);
-size_t decode_wide_workspace_bytes(int, int, int, int, int, int, int, int, int);
-int decode_step_wide_bf16(int, int, int, int, int, int, int, int, int, int, float, float, const void *const *, const void *const *,
-                          const void *, const void *, const void *, const void *, const void *, float *, void *, hipStream_t);
-struct bf16_t;
-template <typename T> int mix_fwd(int, int, int, int, const void *, const void *, const void *, const void *, void *, int, hipStream_t);
-template <typename T> int mix_bwd(int, int, int, int, const void *const *, const void *, const void *, const void *, const void *, void *, float *, int, int, hipStream_t);
-template <typename T> int tmix_prepare_fwd(long, int, const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *, void *, void *, void *, void *, void *, int, hipStream_t);
-template <typename T> int tmix_prepare_bwd(long, int, const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *, void *, void *, void *, void *, void *, void *, float *, int, hipStream_t);
-template <typename T> int tmix_prepare_bwd_sum(long, int, const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *const *, int, void *, void *, void *, void *, void *, void *, void *, float *, int, hipStream_t);
-template <typename T> int tmix_post_fwd(long, int, const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *, float, void *, int, hipStream_t);
-template <typename T> int tmix_post_bwd(long, int, const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *, const void *, float, void *, void *, void *, void *, void *, float *, float *, int, hipStream_t);
-template <typename T> int add_ln_fwd(long, int, const void *, const void *, const void *, const void *, float, void *, void *, float *, float *, int, hipStream_t);
-template <typename T> int add_ln_bwd(long, int, const void *, const void *, const void *, const float *, const float *, const void *, void *, float *, int, hipStream_t);
-template <typename T> int add_ln_mix_fwd(int, int, int, int, void *, const void *, const void *, const void *, const void *, float, const void *, const void *, void *, void *, float *, float *, int, int, hipStream_t);
-template <typename T> int mix_add_ln_bwd(int, int, int, int, const void *const *, const void *, const void *, const float *, const float *, const void *, const void *, const void *, const void *, void *, float *, int, int, hipStream_t);
-int add_ln_mix_rows_fwd_bf16(int, int, int, const void *, const void *, const void *, const void *, float, const void *, const void *, const int *, const int *, const void *, void *, void *, void *, int, int, hipStream_t);
-int chunk_fwd9_state_rows_bf16(int, int, const void *, const void *, const void *, const void *, const void *, const void *, const float *, void *, const int *, int, float *, const int *, hipStream_t);
-int cache_rows_commit_bf16(int, int, const void *const *, void *const *, const int *, const int *, int, int, hipStream_t);
-template <typename T> int relusq_fwd(long, const void *, void *, hipStream_t);
-template <typename T> int relusq_bwd(long, const void *, const void *, void *, hipStream_t);
-template <typename T> int relusq_bwd_s(long, const void *, const void *, void *, hipStream_t);
-}  // namespace rwkv7
-
-namespace {
-inline bool any_null(std::initializer_list<const void *> ps) {
-    for (const void *p : ps)
-        if (!p) return true;
-    return false;
-}
-}  // namespace
+using rwkv7::any_null;
 
 extern "C" {
 
@@ -265,196 +145,6 @@ int rwkv7_wkv_state_fwd_variant_bf16(int B, int T, int C, int H, float *state, c
 }
 
 
-// ---- fused elementwise stages ----------------------------------------------------------------------------------
-#define SHAPE_OK(D) ((D) > 0 && (D) % 64 == 0 && (D) <= 4096)  /* D/8 threads per row, kEwMaxThreads = 512 */
-#define EW_DEFINE(SFX, TY)                                                                                           \
-    int rwkv7_mix_fwd_##SFX(int B, int T, int D, int nmix, const void *x, const void *x_prev, const void *mask,       \
-                            const void *params, void *out, int nblocks, rwkv7_stream_t stream) {                      \
-        if (B <= 0 || T <= 0 || nblocks <= 0 || any_null({x, params, out})) return RWKV7_EINVAL;                      \
-        if (!SHAPE_OK(D) || (nmix != 1 && nmix != 3 && nmix != 6)) return RWKV7_ESHAPE;                                            \
-        return rwkv7::mix_fwd<TY>(B, T, D, nmix, x, x_prev, mask, params, out, nblocks, (hipStream_t)stream);         \
-    }                                                                                                                 \
-    int rwkv7_mix_bwd_##SFX(int B, int T, int D, int nmix, const void *const *g, const void *x, const void *x_prev,   \
-                            const void *mask, const void *params, void *dx, float *dpart, int nblocks,                \
-                            int run_len, rwkv7_stream_t stream) {                                                     \
-        if (B <= 0 || T <= 0 || nblocks <= 0 || run_len <= 0 || any_null({g, x, params, dx, dpart}))                  \
-            return RWKV7_EINVAL;                                                                                      \
-        if (!SHAPE_OK(D) || (nmix != 1 && nmix != 3 && nmix != 6)) return RWKV7_ESHAPE;                                            \
-        for (int i = 0; i < nmix; i++)                                                                                \
-            if (!g[i]) return RWKV7_EINVAL;                                                                           \
-        return rwkv7::mix_bwd<TY>(B, T, D, nmix, g, x, x_prev, mask, params, dx, dpart, nblocks, run_len,            \
-                                  (hipStream_t)stream); \
-    }                                                                                                                 \
-    int rwkv7_tmix_prepare_fwd_##SFX(long rows, int D, const void *w_pre, const void *k, const void *v,               \
-                                     const void *a_pre, const void *v_pre, const void *v_first, const void *mask,     \
-                                     const void *k_k, const void *k_a, void *w, void *k2, void *v2, void *ain,        \
-                                     void *bin, int nblocks, rwkv7_stream_t stream) {                                 \
-        if (rows <= 0 || nblocks <= 0 || any_null({w_pre, k, v, a_pre, k_k, k_a, w, k2, v2, ain, bin}))               \
-            return RWKV7_EINVAL;                                                                                      \
-        if ((v_pre == nullptr) != (v_first == nullptr)) return RWKV7_EINVAL;                                          \
-        if (!SHAPE_OK(D)) return RWKV7_ESHAPE;                                                                        \
-        return rwkv7::tmix_prepare_fwd<TY>(rows, D, w_pre, k, v, a_pre, v_pre, v_first, mask, k_k, k_a, w, k2, v2,    \
-                                           ain, bin, nblocks, (hipStream_t)stream);                                   \
-    }                                                                                                                 \
-    int rwkv7_tmix_prepare_bwd_##SFX(long rows, int D, const void *w_pre, const void *k, const void *v,               \
-                                     const void *a_pre, const void *v_pre, const void *v_first, const void *mask,     \
-                                     const void *k_k, const void *k_a, const void *d_w, const void *d_k2,             \
-                                     const void *d_v2, const void *d_ain, const void *d_bin, void *d_wpre, void *d_k, \
-                                     void *d_v, void *d_apre, void *d_vpre, void *d_vfirst, float *dpart,             \
-                                     int nblocks, rwkv7_stream_t stream) {                                            \
-        if (rows <= 0 || nblocks <= 0 ||                                                                              \
-            any_null({w_pre, k, v, a_pre, k_k, k_a, d_w, d_k2, d_v2, d_ain, d_bin, d_wpre, d_k, d_v, d_apre, dpart})) \
-            return RWKV7_EINVAL;                                                                                      \
-        if ((v_pre == nullptr) != (v_first == nullptr)) return RWKV7_EINVAL;                                          \
-        if (v_pre && (!d_vpre || !d_vfirst)) return RWKV7_EINVAL;                                                     \
-        if (!SHAPE_OK(D)) return RWKV7_ESHAPE;                                                                        \
-        return rwkv7::tmix_prepare_bwd<TY>(rows, D, w_pre, k, v, a_pre, v_pre, v_first, mask, k_k, k_a, d_w, d_k2,    \
-                                           d_v2, d_ain, d_bin, d_wpre, d_k, d_v, d_apre, d_vpre, d_vfirst, dpart,     \
-                                           nblocks, (hipStream_t)stream);                                             \
-    }                                                                                                                 \
-    int rwkv7_tmix_prepare_bwd_sum_##SFX(long rows, int D, const void *w_pre, const void *k, const void *v,           \
-                                         const void *a_pre, const void *v_pre, const void *v_first, const void *mask, \
-                                         const void *k_k, const void *k_a, const void *const *gsum, void *d_wpre,     \
-                                         void *d_k, void *d_v, void *d_apre, void *d_vpre, void *d_vfirst, void *d_r, \
-                                         float *dpart, int nblocks, rwkv7_stream_t stream) {                          \
-        if (rows <= 0 || nblocks <= 0 ||                                                                              \
-            any_null({w_pre, k, v, a_pre, k_k, k_a, (const void *)gsum, d_wpre, d_k, d_v, d_apre, d_r, dpart}))       \
-            return RWKV7_EINVAL;                                                                                      \
-        for (int i = 0; i < 14; i++) /* the second partials {1,3,8,10,12} may be NULL */                              \
-            if (!gsum[i] && i != 1 && i != 3 && i != 8 && i != 10 && i != 12) return RWKV7_EINVAL;                    \
-        if ((v_pre == nullptr) != (v_first == nullptr)) return RWKV7_EINVAL;                                          \
-        if (v_pre && (!d_vpre || !d_vfirst)) return RWKV7_EINVAL;                                                     \
-        if (!SHAPE_OK(D)) return RWKV7_ESHAPE;                                                                        \
-        return rwkv7::tmix_prepare_bwd_sum<TY>(rows, D, w_pre, k, v, a_pre, v_pre, v_first, mask, k_k, k_a, gsum, 15, \
-                                               d_wpre, d_k, d_v, d_apre, d_vpre, d_vfirst, d_r, dpart, nblocks,       \
-                                               (hipStream_t)stream);                                                  \
-    }                                                                                                                 \
-    int rwkv7_tmix_prepare_bwd_sum_compact_##SFX(long rows, int D, const void *w_pre, const void *k, const void *v,   \
-                                         const void *a_pre, const void *v_pre, const void *v_first, const void *mask, \
-                                         const void *k_k, const void *k_a, const void *const *gsum, void *d_wpre,     \
-                                         void *d_k, void *d_v, void *d_apre, void *d_vpre, void *d_vfirst, void *d_r, \
-                                         float *dpart, int nblocks, rwkv7_stream_t stream) {                          \
-        if (rows <= 0 || nblocks <= 0 ||                                                                              \
-            any_null({w_pre, k, v, a_pre, k_k, k_a, (const void *)gsum, d_wpre, d_k, d_v, d_apre, d_r, dpart}))       \
-            return RWKV7_EINVAL;                                                                                      \
-        /* gsum: 19 pointers; {0,2,5,7,9,11} and the hand-off {15..18} are required, the post tensors {4,6,13} are unused */ \
-        for (int i : {0, 2, 5, 7, 9, 11, 15, 16, 17, 18})                                                             \
-            if (!gsum[i]) return RWKV7_EINVAL;                                                                        \
-        if ((v_pre == nullptr) != (v_first == nullptr)) return RWKV7_EINVAL;                                          \
-        if (v_pre && (!d_vpre || !d_vfirst)) return RWKV7_EINVAL;                                                     \
-        if (!SHAPE_OK(D)) return RWKV7_ESHAPE;                                                                        \
-        return rwkv7::tmix_prepare_bwd_sum<TY>(rows, D, w_pre, k, v, a_pre, v_pre, v_first, mask, k_k, k_a, gsum, 19, \
-                                               d_wpre, d_k, d_v, d_apre, d_vpre, d_vfirst, d_r, dpart, nblocks,       \
-                                               (hipStream_t)stream);                                                  \
-    }                                                                                                                 \
-    int rwkv7_add_ln_fwd_##SFX(long rows, int D, const void *x, const void *branch, const void *gamma,                \
-                               const void *beta, float eps, void *x_out, void *h, float *mean, float *rstd,           \
-                               int nblocks, rwkv7_stream_t stream) {                                                  \
-        if (rows <= 0 || nblocks <= 0 || any_null({x, gamma, h, (const void *)mean, (const void *)rstd}))             \
-            return RWKV7_EINVAL;                                                                                      \
-        if (branch && !x_out) return RWKV7_EINVAL;                                                                    \
-        if (!SHAPE_OK(D)) return RWKV7_ESHAPE;                                                                        \
-        return rwkv7::add_ln_fwd<TY>(rows, D, x, branch, gamma, beta, eps, x_out, h, mean, rstd, nblocks,             \
-                                     (hipStream_t)stream);                                                            \
-    }                                                                                                                 \
-    int rwkv7_add_ln_bwd_##SFX(long rows, int D, const void *dh, const void *d_resid, const void *x1,                 \
-                               const float *mean, const float *rstd, const void *gamma, void *dx, float *dpart,       \
-                               int nblocks, rwkv7_stream_t stream) {                                                  \
-        if (rows <= 0 || nblocks <= 0 ||                                                                              \
-            any_null({dh, x1, (const void *)mean, (const void *)rstd, gamma, dx, (const void *)dpart}))               \
-            return RWKV7_EINVAL;                                                                                      \
-        if (!SHAPE_OK(D)) return RWKV7_ESHAPE;                                                                        \
-        return rwkv7::add_ln_bwd<TY>(rows, D, dh, d_resid, x1, mean, rstd, gamma, dx, dpart, nblocks,                 \
-                                     (hipStream_t)stream);                                                            \
-    }                                                                                                                 \
-    int rwkv7_add_ln_mix_fwd_##SFX(int B, int T, int D, int nmix, const void *x, const void *branch, const void *gamma, \
-                                   const void *beta, float eps, const void *mask, const void *params, void *x_out,   \
-                                   void *out, float *mean, float *rstd, int nblocks, int run_len,                     \
-                                   rwkv7_stream_t stream) {                                                           \
-        if (B <= 0 || T <= 0 || nblocks <= 0 || run_len <= 0 ||                                                       \
-            any_null({x, gamma, params, out, (const void *)mean, (const void *)rstd}))                                \
-            return RWKV7_EINVAL;                                                                                      \
-        if (branch && !x_out) return RWKV7_EINVAL;                                                                    \
-        if (!SHAPE_OK(D) || (nmix != 1 && nmix != 3 && nmix != 6)) return RWKV7_ESHAPE;                               \
-        return rwkv7::add_ln_mix_fwd<TY>(B, T, D, nmix, nullptr, x, branch, gamma, beta, eps, mask, params, x_out,    \
-                                         out, mean, rstd, nblocks, run_len, (hipStream_t)stream);                     \
-    }                                                                                                                 \
-    int rwkv7_add_ln_mix_fwd_h_##SFX(int B, int T, int D, int nmix, const void *x, const void *branch,                \
-                                     const void *gamma, const void *beta, float eps, const void *mask,                \
-                                     const void *params, void *x_out, void *out, void *h, float *mean, float *rstd,   \
-                                     int nblocks, int run_len, rwkv7_stream_t stream) {                               \
-        if (B <= 0 || T <= 0 || nblocks <= 0 || run_len <= 0 ||                                                       \
-            any_null({x, gamma, params, out, (const void *)h, (const void *)mean, (const void *)rstd}))                \
-            return RWKV7_EINVAL;                                                                                      \
-        if (branch && !x_out) return RWKV7_EINVAL;                                                                    \
-        if (!SHAPE_OK(D) || (nmix != 1 && nmix != 3 && nmix != 6)) return RWKV7_ESHAPE;                               \
-        return rwkv7::add_ln_mix_fwd<TY>(B, T, D, nmix, h, x, branch, gamma, beta, eps, mask, params, x_out, out,     \
-                                         mean, rstd, nblocks, run_len, (hipStream_t)stream);                          \
-    }                                                                                                                 \
-    int rwkv7_mix_add_ln_bwd_##SFX(int B, int T, int D, int nmix, const void *const *g, const void *d_resid,          \
-                                   const void *x1, const float *mean, const float *rstd, const void *gamma,           \
-                                   const void *beta, const void *mask, const void *params, void *dx, float *dpart,    \
-                                   int nblocks, int run_len, rwkv7_stream_t stream) {                                 \
-        if (B <= 0 || T <= 0 || nblocks <= 0 || run_len <= 0 ||                                                       \
-            any_null({(const void *)g, x1, (const void *)mean, (const void *)rstd, gamma, params, dx,                 \
-                      (const void *)dpart}))                                                                          \
-            return RWKV7_EINVAL;                                                                                      \
-        if (!SHAPE_OK(D) || (nmix != 1 && nmix != 6)) return RWKV7_ESHAPE;                                            \
-        for (int i = 0; i < nmix; i++)                                                                                \
-            if (!g[i]) return RWKV7_EINVAL;                                                                           \
-        return rwkv7::mix_add_ln_bwd<TY>(B, T, D, nmix, g, d_resid, x1, mean, rstd, gamma, beta, mask, params, dx,    \
-                                         dpart, nblocks, run_len, (hipStream_t)stream);                               \
-    }                                                                                                                 \
-    int rwkv7_tmix_post_fwd_##SFX(long rows, int D, const void *y, const void *r, const void *k, const void *v,       \
-                                  const void *g, const void *gn_w, const void *gn_b, const void *r_k, float eps,      \
-                                  void *out, int nblocks, rwkv7_stream_t stream) {                                    \
-        if (rows <= 0 || nblocks <= 0 || any_null({y, r, k, v, g, gn_w, gn_b, r_k, out})) return RWKV7_EINVAL;        \
-        if (!SHAPE_OK(D)) return RWKV7_ESHAPE;                                                                        \
-        return rwkv7::tmix_post_fwd<TY>(rows, D, y, r, k, v, g, gn_w, gn_b, r_k, eps, out, nblocks,                   \
-                                        (hipStream_t)stream);                                                         \
-    }                                                                                                                 \
-    int rwkv7_tmix_post_bwd_##SFX(long rows, int D, const void *dout, const void *y, const void *r, const void *k,    \
-                                  const void *v, const void *g, const void *gn_w, const void *gn_b, const void *r_k,  \
-                                  float eps, void *d_y, void *d_r, void *d_k, void *d_v, void *d_g, float *dpart,     \
-                                  int nblocks, rwkv7_stream_t stream) {                                               \
-        if (rows <= 0 || nblocks <= 0 ||                                                                              \
-            any_null({dout, y, r, k, v, g, gn_w, gn_b, r_k, d_y, d_r, d_k, d_v, d_g, dpart}))                         \
-            return RWKV7_EINVAL;                                                                                      \
-        if (!SHAPE_OK(D)) return RWKV7_ESHAPE;                                                                        \
-        return rwkv7::tmix_post_bwd<TY>(rows, D, dout, y, r, k, v, g, gn_w, gn_b, r_k, eps, d_y, d_r, d_k, d_v, d_g,  \
-                                        dpart, nullptr, nblocks, (hipStream_t)stream);                                \
-    }                                                                                                                 \
-    int rwkv7_tmix_post_bwd_compact_##SFX(long rows, int D, const void *dout, const void *y, const void *r,           \
-                                  const void *k, const void *v, const void *g, const void *gn_w, const void *gn_b,    \
-                                  const void *r_k, float eps, void *d_y, void *dt, void *d_g, float *hscal,           \
-                                  float *dpart, int nblocks, rwkv7_stream_t stream) {                                 \
-        if (rows <= 0 || nblocks <= 0 ||                                                                              \
-            any_null({dout, y, r, k, v, g, gn_w, gn_b, r_k, d_y, dt, d_g, (const void *)hscal, (const void *)dpart})) \
-            return RWKV7_EINVAL;                                                                                      \
-        if (!SHAPE_OK(D)) return RWKV7_ESHAPE;                                                                        \
-        return rwkv7::tmix_post_bwd<TY>(rows, D, dout, y, r, k, v, g, gn_w, gn_b, r_k, eps, d_y, nullptr, nullptr,    \
-                                        dt, d_g, dpart, hscal, nblocks, (hipStream_t)stream);                         \
-    }                                                                                                                 \
-    int rwkv7_relusq_fwd_##SFX(long n, const void *x, void *y, rwkv7_stream_t stream) {                               \
-        if (n <= 0 || any_null({x, y})) return RWKV7_EINVAL;                                                          \
-        if (n % 8 != 0) return RWKV7_ESHAPE;                                                                          \
-        return rwkv7::relusq_fwd<TY>(n, x, y, (hipStream_t)stream);                                                   \
-    }                                                                                                                 \
-    int rwkv7_relusq_bwd_##SFX(long n, const void *x, const void *dy, void *dx, rwkv7_stream_t stream) {              \
-        if (n <= 0 || any_null({x, dy, dx})) return RWKV7_EINVAL;                                                     \
-        if (n % 8 != 0) return RWKV7_ESHAPE;                                                                          \
-        return rwkv7::relusq_bwd<TY>(n, x, dy, dx, (hipStream_t)stream);                                              \
-    }                                                                                                                 \
-    int rwkv7_relusq_bwd_s_##SFX(long n, const void *s, const void *dy, void *dx, rwkv7_stream_t stream) {            \
-        if (n <= 0 || any_null({s, dy, dx})) return RWKV7_EINVAL;                                                     \
-        if (n % 8 != 0) return RWKV7_ESHAPE;                                                                          \
-        return rwkv7::relusq_bwd_s<TY>(n, s, dy, dx, (hipStream_t)stream);                                            \
-    }
-
-EW_DEFINE(bf16, rwkv7::bf16_t)
-EW_DEFINE(f32, float)
-
-
 // ---- chunked (MFMA) WKV7 -----------------------------------------------------------------------------------------
 #define CHUNK_DEFINE(SFX)                                                                                          \
     int rwkv7_wkv_chunk_prep_##SFX(int B, int T, int H, const void *w, const void *a, const void *b, float *tinv,   \
@@ -526,7 +216,7 @@ int rwkv7_add_ln_mix_rows_fwd_bf16(int T, int D, int nmix, const void *x, const 
         any_null({x, gamma, params, out, (const void *)prev_src, (const void *)last_dst, (const void *)x_prev}))
         return RWKV7_EINVAL;
     if (branch && !x_out) return RWKV7_EINVAL;
-    if (!SHAPE_OK(D) || (nmix != 1 && nmix != 6) || T % 32 != 0) return RWKV7_ESHAPE;
+    if (!rwkv7::row_width_ok(D) || T % 32 != 0) return RWKV7_ESHAPE;   // and for an nmix outside {1, 6}, from the launcher
     return rwkv7::add_ln_mix_rows_fwd_bf16(T, D, nmix, x, branch, gamma, beta, eps, mask, params, prev_src, last_dst,
                                            x_prev_rd ? x_prev_rd : x_prev, x_prev, x_out, out, nblocks, run_len, (hipStream_t)stream);
 }
@@ -705,8 +395,7 @@ int rwkv7_lora_down_fwd_bf16(int nb, const int *ranks, const int *acts, long M, 
         d.mu[i] = mu[i];
         d.out[i] = out[i];
     }
-    const int rc = rwkv7::lora_down_fwd(d, R, M, T, D, x, mask, packed, (hipStream_t)stream);
-    return rc == -4 ? RWKV7_ESHAPE : rc;
+    return rwkv7::lora_down_fwd(d, R, M, T, D, x, mask, packed, (hipStream_t)stream);
 }
 int rwkv7_gemv32_bf16(int M, int N, int K, const void *x, const void *w, const void *bias, void *y, rwkv7_stream_t stream) {
     if (any_null({x, w, y})) return RWKV7_EINVAL;

@@ -37,6 +37,7 @@
 // The phase bodies, the per-phase kernels and the workspace layout live in decode_step_phases.h, templated on the number of 32-row
 // tiles RT: this file instantiates RT = 1 (and holds the lab build's persistent kernel); decode_step_wide.hip runs B = 33 .. 128
 // through RT = 2, 3, 4.
+#include "launchers.h"
 #include "decode_step_phases.h"
 
 namespace rwkv7 {

@@ -13,6 +13,7 @@
 //
 // Rounds of loads: 8 k-steps in flight (one tile: 16).  Registers / LDS per instantiation: DESIGN.md 7.2.  There is no persistent
 // variant.
+#include "launchers.h"
 #include "decode_step_phases.h"
 
 namespace rwkv7 {

@@ -12,6 +12,7 @@
 // per-head reductions (l2 norm, GroupNorm moments, bonus dot product) are 8-lane DPP sums, no LDS.
 // Parameter gradients are accumulated per thread over the rows a workgroup walks and written as per-workgroup
 // partials [nblocks, P, D] (fp32); the host sums the partials (deterministic, no atomics).
+#include "launchers.h"
 #include "adamw_body.h"
 #include "ln_row.h"
 
@@ -1298,246 +1299,298 @@ int gather_rows16(long n_out, int D, const void *src, const int *idx, void *out,
     return (int)hipGetLastError();
 }
 
-static inline int finish() { return (int)hipGetLastError(); }
-
+// ------------------------------------------------------------------------------------------------------
+// Host side of the fused row stages: ONE launcher per stage.  It refuses what include/rwkv7_hip.h says the entry refuses (before
+// any launch), picks the instantiation and launches (launch_rows / for_nmix, ln_row.h).  The extern "C" entries for bf16 and fp32
+// are stamped from these templates at the end of the file.
+// ------------------------------------------------------------------------------------------------------
 template <typename T>
-int mix_fwd(int B, int T_, int D, int nmix, const void *x, const void *x_prev, const void *mask, const void *params,
-            void *out, int nblocks, hipStream_t st) {
-    (void)hipGetLastError();
-    const dim3 grid(nblocks), block(D / 8);
-    if (nmix == 6)
-        hipLaunchKernelGGL((mix_fwd_kernel<T, 6>), grid, block, 0, st, B, T_, D, (const T *)x, (const T *)x_prev,
+int mix_fwd(int B, int T_, int D, int nmix, const void *x, const void *x_prev, const void *mask, const void *params, void *out,
+            int nblocks, hipStream_t st) {
+    if (B <= 0 || T_ <= 0 || nblocks <= 0 || any_null({x, params, out})) return RWKV7_EINVAL;
+    if (!row_width_ok(D)) return RWKV7_ESHAPE;
+    // nmix = 3: x_r, x_k, x_v only, the low-rank branches take their inputs through the lerp (fused.mix_lora)
+    return for_nmix<1, 3, 6>(nmix, [&](auto n) {
+        return launch_rows(mix_fwd_kernel<T, decltype(n)::value>, nblocks, D, st, B, T_, D, (const T *)x, (const T *)x_prev,
                            (const T *)mask, (const T *)params, (T *)out);
-    else if (nmix == 3)   // x_r, x_k, x_v only: the low-rank branches take their inputs through the lerp (fused.mix_lora)
-        hipLaunchKernelGGL((mix_fwd_kernel<T, 3>), grid, block, 0, st, B, T_, D, (const T *)x, (const T *)x_prev,
-                           (const T *)mask, (const T *)params, (T *)out);
-    else
-        hipLaunchKernelGGL((mix_fwd_kernel<T, 1>), grid, block, 0, st, B, T_, D, (const T *)x, (const T *)x_prev,
-                           (const T *)mask, (const T *)params, (T *)out);
-    return finish();
+    });
+}
+// the NMIX gradient pointers of a backward as the kernel takes them; false when one of them is NULL
+template <int NMIX>
+bool mix_grads(const void *const *g, MixGrads<NMIX> &gs) {
+    for (int i = 0; i < NMIX; i++)
+        if (!(gs.g[i] = g[i])) return false;
+    return true;
 }
 template <typename T>
 int mix_bwd(int B, int T_, int D, int nmix, const void *const *g, const void *x, const void *x_prev, const void *mask,
             const void *params, void *dx, float *dpart, int nblocks, int run_len, hipStream_t st) {
-    (void)hipGetLastError();
-    const dim3 grid(nblocks), block(D / 8);
-    if (nmix == 6) {
-        MixGrads<6> gs;
-        for (int i = 0; i < 6; i++) gs.g[i] = g[i];
-        hipLaunchKernelGGL((mix_bwd_kernel<T, 6>), grid, block, 0, st, B, T_, D, run_len, gs, (const T *)x,
-                           (const T *)x_prev,
+    if (B <= 0 || T_ <= 0 || nblocks <= 0 || run_len <= 0 || any_null({g, x, params, dx, dpart})) return RWKV7_EINVAL;
+    if (!row_width_ok(D)) return RWKV7_ESHAPE;
+    return for_nmix<1, 3, 6>(nmix, [&](auto n) {
+        MixGrads<decltype(n)::value> gs;
+        if (!mix_grads(g, gs)) return RWKV7_EINVAL;
+        return launch_rows(mix_bwd_kernel<T, decltype(n)::value>, nblocks, D, st, B, T_, D, run_len, gs, (const T *)x, (const T *)x_prev,
                            (const T *)mask, (const T *)params, (T *)dx, dpart);
-    } else if (nmix == 3) {
-        MixGrads<3> gs;
-        for (int i = 0; i < 3; i++) gs.g[i] = g[i];
-        hipLaunchKernelGGL((mix_bwd_kernel<T, 3>), grid, block, 0, st, B, T_, D, run_len, gs, (const T *)x,
-                           (const T *)x_prev,
-                           (const T *)mask, (const T *)params, (T *)dx, dpart);
-    } else {
-        MixGrads<1> gs;
-        gs.g[0] = g[0];
-        hipLaunchKernelGGL((mix_bwd_kernel<T, 1>), grid, block, 0, st, B, T_, D, run_len, gs, (const T *)x,
-                           (const T *)x_prev,
-                           (const T *)mask, (const T *)params, (T *)dx, dpart);
-    }
-    return finish();
+    });
 }
+// h_out: the fwd_h entries' extra output (want_h), NULL for the plain ones
 template <typename T>
-int add_ln_mix_fwd(int B, int T_, int D, int nmix, void *h_out, const void *x, const void *branch, const void *gamma, const void *beta, float eps,
-                   const void *mask, const void *params, void *x_out, void *out, float *mean, float *rstd, int nblocks, int run_len,
-                   hipStream_t st) {
-    (void)hipGetLastError();
-    const dim3 grid(nblocks), block(D / 8);
-    if (nmix == 6)
-        hipLaunchKernelGGL((add_ln_mix_fwd_kernel<T, 6>), grid, block, 0, st, B, T_, D, run_len, (const T *)x, (const T *)branch,
-                           (const T *)gamma, (const T *)beta, eps, (const T *)mask, (const T *)params, (T *)x_out, (T *)out, mean, rstd, (T *)h_out);
-    else if (nmix == 3)   // x_r, x_k, x_v: the time-mix side when the low-rank branches go through the lerp (fused.add_layer_norm_mix_lora)
-        hipLaunchKernelGGL((add_ln_mix_fwd_kernel<T, 3>), grid, block, 0, st, B, T_, D, run_len, (const T *)x, (const T *)branch,
-                           (const T *)gamma, (const T *)beta, eps, (const T *)mask, (const T *)params, (T *)x_out, (T *)out, mean, rstd, (T *)h_out);
-    else
-        hipLaunchKernelGGL((add_ln_mix_fwd_kernel<T, 1>), grid, block, 0, st, B, T_, D, run_len, (const T *)x, (const T *)branch,
-                           (const T *)gamma, (const T *)beta, eps, (const T *)mask, (const T *)params, (T *)x_out, (T *)out, mean, rstd, (T *)h_out);
-    return finish();
+int add_ln_mix_fwd(int B, int T_, int D, int nmix, bool want_h, void *h_out, const void *x, const void *branch, const void *gamma,
+                   const void *beta, float eps, const void *mask, const void *params, void *x_out, void *out, float *mean, float *rstd,
+                   int nblocks, int run_len, hipStream_t st) {
+    if (B <= 0 || T_ <= 0 || nblocks <= 0 || run_len <= 0 || any_null({x, gamma, params, out, mean, rstd}) || (want_h && !h_out))
+        return RWKV7_EINVAL;
+    if (branch && !x_out) return RWKV7_EINVAL;
+    if (!row_width_ok(D)) return RWKV7_ESHAPE;
+    // nmix = 3: the time-mix side when the low-rank branches go through the lerp (fused.add_layer_norm_mix_lora)
+    return for_nmix<1, 3, 6>(nmix, [&](auto n) {
+        return launch_rows(add_ln_mix_fwd_kernel<T, decltype(n)::value>, nblocks, D, st, B, T_, D, run_len, (const T *)x,
+                           (const T *)branch, (const T *)gamma, (const T *)beta, eps, (const T *)mask, (const T *)params, (T *)x_out,
+                           (T *)out, mean, rstd, (T *)h_out);
+    });
 }
+// the one-pass backward has no nmix = 3 kernel: RWKV7_ESHAPE, as for any other count outside the list
 template <typename T>
 int mix_add_ln_bwd(int B, int T_, int D, int nmix, const void *const *g, const void *d_resid, const void *x1, const float *mean,
                    const float *rstd, const void *gamma, const void *beta, const void *mask, const void *params, void *dx, float *dpart,
                    int nblocks, int run_len, hipStream_t st) {
-    (void)hipGetLastError();
-    const dim3 grid(nblocks), block(D / 8);
-    if (nmix == 6) {
-        MixGrads<6> gs;
-        for (int i = 0; i < 6; i++) gs.g[i] = g[i];
-        hipLaunchKernelGGL((mix_add_ln_bwd_kernel<T, 6>), grid, block, 0, st, B, T_, D, run_len, gs, (const T *)d_resid, (const T *)x1,
-                           mean, rstd, (const T *)gamma, (const T *)beta, (const T *)mask, (const T *)params, (T *)dx, dpart);
-    } else {
-        MixGrads<1> gs;
-        gs.g[0] = g[0];
-        hipLaunchKernelGGL((mix_add_ln_bwd_kernel<T, 1>), grid, block, 0, st, B, T_, D, run_len, gs, (const T *)d_resid, (const T *)x1,
-                           mean, rstd, (const T *)gamma, (const T *)beta, (const T *)mask, (const T *)params, (T *)dx, dpart);
-    }
-    return finish();
+    if (B <= 0 || T_ <= 0 || nblocks <= 0 || run_len <= 0 || any_null({g, x1, mean, rstd, gamma, params, dx, dpart}))
+        return RWKV7_EINVAL;
+    if (!row_width_ok(D)) return RWKV7_ESHAPE;
+    return for_nmix<1, 6>(nmix, [&](auto n) {
+        MixGrads<decltype(n)::value> gs;
+        if (!mix_grads(g, gs)) return RWKV7_EINVAL;
+        return launch_rows(mix_add_ln_bwd_kernel<T, decltype(n)::value>, nblocks, D, st, B, T_, D, run_len, gs, (const T *)d_resid,
+                           (const T *)x1, mean, rstd, (const T *)gamma, (const T *)beta, (const T *)mask, (const T *)params, (T *)dx,
+                           dpart);
+    });
+}
+// v_pre / v_first: both NULL in layer 0 (no value residual), else both set, and then the backwards need d_vpre and d_vfirst; mask
+// may be NULL
+template <typename T>
+int tmix_prepare_fwd(long rows, int D, const void *w_pre, const void *k, const void *v, const void *a_pre, const void *v_pre,
+                     const void *v_first, const void *mask, const void *k_k, const void *k_a, void *w, void *k2, void *v2, void *ain,
+                     void *bin, int nblocks, hipStream_t st) {
+    if (rows <= 0 || nblocks <= 0 || any_null({w_pre, k, v, a_pre, k_k, k_a, w, k2, v2, ain, bin})) return RWKV7_EINVAL;
+    if ((v_pre == nullptr) != (v_first == nullptr)) return RWKV7_EINVAL;
+    if (!row_width_ok(D)) return RWKV7_ESHAPE;
+    return launch_rows(tmix_prepare_fwd_kernel<T>, nblocks, D, st, rows, D, (const T *)w_pre, (const T *)k, (const T *)v,
+                       (const T *)a_pre, (const T *)v_pre, (const T *)v_first, (const T *)mask, (const T *)k_k, (const T *)k_a, (T *)w,
+                       (T *)k2, (T *)v2, (T *)ain, (T *)bin);
 }
 template <typename T>
-int tmix_prepare_fwd(long rows, int D, const void *w_pre, const void *k, const void *v, const void *a_pre,
-                     const void *v_pre, const void *v_first, const void *mask, const void *k_k, const void *k_a,
-                     void *w, void *k2, void *v2, void *ain, void *bin, int nblocks, hipStream_t st) {
-    (void)hipGetLastError();
-    hipLaunchKernelGGL((tmix_prepare_fwd_kernel<T>), dim3(nblocks), dim3(D / 8), 0, st, rows, D, (const T *)w_pre,
-                       (const T *)k, (const T *)v, (const T *)a_pre, (const T *)v_pre, (const T *)v_first,
-                       (const T *)mask, (const T *)k_k, (const T *)k_a, (T *)w, (T *)k2, (T *)v2, (T *)ain, (T *)bin);
-    return finish();
-}
-template <typename T>
-int tmix_prepare_bwd(long rows, int D, const void *w_pre, const void *k, const void *v, const void *a_pre,
-                     const void *v_pre, const void *v_first, const void *mask, const void *k_k, const void *k_a,
-                     const void *d_w, const void *d_k2, const void *d_v2, const void *d_ain, const void *d_bin,
-                     void *d_wpre, void *d_k, void *d_v, void *d_apre, void *d_vpre, void *d_vfirst, float *dpart,
-                     int nblocks, hipStream_t st) {
-    (void)hipGetLastError();
-    hipLaunchKernelGGL((tmix_prepare_bwd_kernel<T, false>), dim3(nblocks), dim3(D / 8), 0, st, rows, D,
-                       (const T *)w_pre, (const T *)k, (const T *)v, (const T *)a_pre, (const T *)v_pre,
-                       (const T *)v_first, (const T *)mask, (const T *)k_k, (const T *)k_a, (const T *)d_w,
-                       (const T *)d_k2, (const T *)d_v2, (const T *)d_ain, (const T *)d_bin, (T *)d_wpre, (T *)d_k,
+int tmix_prepare_bwd(long rows, int D, const void *w_pre, const void *k, const void *v, const void *a_pre, const void *v_pre,
+                     const void *v_first, const void *mask, const void *k_k, const void *k_a, const void *d_w, const void *d_k2,
+                     const void *d_v2, const void *d_ain, const void *d_bin, void *d_wpre, void *d_k, void *d_v, void *d_apre,
+                     void *d_vpre, void *d_vfirst, float *dpart, int nblocks, hipStream_t st) {
+    if (rows <= 0 || nblocks <= 0 ||
+        any_null({w_pre, k, v, a_pre, k_k, k_a, d_w, d_k2, d_v2, d_ain, d_bin, d_wpre, d_k, d_v, d_apre, dpart}))
+        return RWKV7_EINVAL;
+    if ((v_pre == nullptr) != (v_first == nullptr)) return RWKV7_EINVAL;
+    if (v_pre && (!d_vpre || !d_vfirst)) return RWKV7_EINVAL;
+    if (!row_width_ok(D)) return RWKV7_ESHAPE;
+    return launch_rows(tmix_prepare_bwd_kernel<T, false>, nblocks, D, st, rows, D, (const T *)w_pre, (const T *)k, (const T *)v,
+                       (const T *)a_pre, (const T *)v_pre, (const T *)v_first, (const T *)mask, (const T *)k_k, (const T *)k_a,
+                       (const T *)d_w, (const T *)d_k2, (const T *)d_v2, (const T *)d_ain, (const T *)d_bin, (T *)d_wpre, (T *)d_k,
                        (T *)d_v, (T *)d_apre, (T *)d_vpre, (T *)d_vfirst, dpart, PrepBwdExtra<T>{});
-    return finish();
 }
-// gsum: HOST array of 15 device pointers {d_w a,b; d_k2 a,b,c; d_v2 a,b; d_ain a,b; d_bin a,b; d_r a,b,c; d_vfirst_in}
+// gsum: HOST array of ngsum device pointers.  ngsum = 15: {d_w a,b; d_k2 a,b,c; d_v2 a,b; d_ain a,b; d_bin a,b; d_r a,b,c;
+// d_vfirst_in}, the second partials {1, 3, 8, 10, 12} and d_vfirst_in may be NULL.  ngsum = 19 (the _compact entries): the same + the
+// compact hand-off {dt, r, r_k, hscal (fp32)} (see PrepBwdExtra), which is required; the post tensors {4, 6, 13} are unused then
 template <typename T>
-int tmix_prepare_bwd_sum(long rows, int D, const void *w_pre, const void *k, const void *v, const void *a_pre,
-                         const void *v_pre, const void *v_first, const void *mask, const void *k_k, const void *k_a,
-                         const void *const *gsum, int ngsum, void *d_wpre, void *d_k, void *d_v, void *d_apre, void *d_vpre,
-                         void *d_vfirst, void *d_r, float *dpart, int nblocks, hipStream_t st) {
-    (void)hipGetLastError();
-    const T *const *g = reinterpret_cast<const T *const *>(gsum);
-    // gsum[15..18] (compact hand-off, see PrepBwdExtra): dt, r, r_k, hscal (fp32); ngsum = 15 without them
-    PrepBwdExtra<T> ex{g[1], g[3], g[4], g[6], g[8], g[10], g[11], g[12], g[13], (T *)d_r, g[14],
-                       ngsum > 15 ? g[15] : nullptr, ngsum > 15 ? g[16] : nullptr, ngsum > 15 ? g[17] : nullptr,
-                       ngsum > 15 ? reinterpret_cast<const float *>(gsum[18]) : nullptr};
-    const bool one_set = !ex.d_w_b && !ex.d_k2_b && !ex.d_k2_c && !ex.d_v2_b && !ex.d_a_b && !ex.d_b_b && !ex.d_r_b && !ex.d_r_c;
-    if (one_set && ex.dt && ex.r && ex.r_k && ex.hscal && ex.d_r_a && (v_pre == nullptr) == (v_first == nullptr)) {
-        // what bf16 training launches: one gradient set from the chunked scan backward + the compact hand-off (loads hoisted)
-        if (v_pre)
-            hipLaunchKernelGGL((tmix_prepare_bwd_fast_kernel<T, true>), dim3(nblocks), dim3(D / 8), 0, st, rows, D, (const T *)w_pre,
-                               (const T *)k, (const T *)v, (const T *)a_pre, (const T *)v_pre, (const T *)v_first, (const T *)mask,
-                               (const T *)k_k, (const T *)k_a, g[0], g[2], g[5], g[7], g[9], (T *)d_wpre, (T *)d_k, (T *)d_v,
-                               (T *)d_apre, (T *)d_vpre, (T *)d_vfirst, dpart, ex.d_r_a, ex.d_r, ex.d_vfirst_in, ex.dt, ex.r, ex.r_k,
-                               ex.hscal);
-        else
-            hipLaunchKernelGGL((tmix_prepare_bwd_fast_kernel<T, false>), dim3(nblocks), dim3(D / 8), 0, st, rows, D, (const T *)w_pre,
-                               (const T *)k, (const T *)v, (const T *)a_pre, (const T *)v_pre, (const T *)v_first, (const T *)mask,
-                               (const T *)k_k, (const T *)k_a, g[0], g[2], g[5], g[7], g[9], (T *)d_wpre, (T *)d_k, (T *)d_v,
-                               (T *)d_apre, (T *)d_vpre, (T *)d_vfirst, dpart, ex.d_r_a, ex.d_r, ex.d_vfirst_in, ex.dt, ex.r, ex.r_k,
-                               ex.hscal);
-        return finish();
+int tmix_prepare_bwd_sum(long rows, int D, const void *w_pre, const void *k, const void *v, const void *a_pre, const void *v_pre,
+                         const void *v_first, const void *mask, const void *k_k, const void *k_a, const void *const *gsum, int ngsum,
+                         void *d_wpre, void *d_k, void *d_v, void *d_apre, void *d_vpre, void *d_vfirst, void *d_r, float *dpart,
+                         int nblocks, hipStream_t st) {
+    if (rows <= 0 || nblocks <= 0 || any_null({w_pre, k, v, a_pre, k_k, k_a, gsum, d_wpre, d_k, d_v, d_apre, d_r, dpart}))
+        return RWKV7_EINVAL;
+    const bool compact = ngsum > 15;
+    for (int i = 0; i < ngsum; i++) {
+        const bool second_partial = i == 1 || i == 3 || i == 8 || i == 10 || i == 12, post = i == 4 || i == 6 || i == 13;
+        if (!gsum[i] && !second_partial && i != 14 && !(compact && post)) return RWKV7_EINVAL;
     }
-    hipLaunchKernelGGL((tmix_prepare_bwd_kernel<T, true>), dim3(nblocks), dim3(D / 8), 0, st, rows, D,
-                       (const T *)w_pre, (const T *)k, (const T *)v, (const T *)a_pre, (const T *)v_pre,
-                       (const T *)v_first, (const T *)mask, (const T *)k_k, (const T *)k_a, g[0], g[2], g[5], g[7],
-                       g[9], (T *)d_wpre, (T *)d_k, (T *)d_v, (T *)d_apre, (T *)d_vpre, (T *)d_vfirst, dpart, ex);
-    return finish();
+    if ((v_pre == nullptr) != (v_first == nullptr)) return RWKV7_EINVAL;
+    if (v_pre && (!d_vpre || !d_vfirst)) return RWKV7_EINVAL;
+    if (!row_width_ok(D)) return RWKV7_ESHAPE;
+    const T *const *g = reinterpret_cast<const T *const *>(gsum);
+    PrepBwdExtra<T> ex{g[1], g[3], g[4], g[6], g[8], g[10], g[11], g[12], g[13], (T *)d_r, g[14],
+                       compact ? g[15] : nullptr, compact ? g[16] : nullptr, compact ? g[17] : nullptr,
+                       compact ? reinterpret_cast<const float *>(gsum[18]) : nullptr};
+    const bool one_set = !ex.d_w_b && !ex.d_k2_b && !ex.d_k2_c && !ex.d_v2_b && !ex.d_a_b && !ex.d_b_b && !ex.d_r_b && !ex.d_r_c;
+    if (one_set && ex.dt && ex.r && ex.r_k && ex.hscal && ex.d_r_a)
+        // what bf16 training launches: one gradient set from the chunked scan backward + the compact hand-off (loads hoisted)
+        return launch_rows(v_pre ? tmix_prepare_bwd_fast_kernel<T, true> : tmix_prepare_bwd_fast_kernel<T, false>, nblocks, D, st, rows,
+                           D, (const T *)w_pre, (const T *)k, (const T *)v, (const T *)a_pre, (const T *)v_pre, (const T *)v_first,
+                           (const T *)mask, (const T *)k_k, (const T *)k_a, g[0], g[2], g[5], g[7], g[9], (T *)d_wpre, (T *)d_k,
+                           (T *)d_v, (T *)d_apre, (T *)d_vpre, (T *)d_vfirst, dpart, ex.d_r_a, ex.d_r, ex.d_vfirst_in, ex.dt, ex.r,
+                           ex.r_k, ex.hscal);
+    return launch_rows(tmix_prepare_bwd_kernel<T, true>, nblocks, D, st, rows, D, (const T *)w_pre, (const T *)k, (const T *)v,
+                       (const T *)a_pre, (const T *)v_pre, (const T *)v_first, (const T *)mask, (const T *)k_k, (const T *)k_a, g[0],
+                       g[2], g[5], g[7], g[9], (T *)d_wpre, (T *)d_k, (T *)d_v, (T *)d_apre, (T *)d_vpre, (T *)d_vfirst, dpart, ex);
 }
 template <typename T>
-int tmix_post_fwd(long rows, int D, const void *y, const void *r, const void *k, const void *v, const void *g,
-                  const void *gn_w, const void *gn_b, const void *r_k, float eps, void *out, int nblocks,
-                  hipStream_t st) {
-    (void)hipGetLastError();
-    hipLaunchKernelGGL((tmix_post_fwd_kernel<T>), dim3(nblocks), dim3(D / 8), 0, st, rows, D, (const T *)y,
-                       (const T *)r, (const T *)k, (const T *)v, (const T *)g, (const T *)gn_w, (const T *)gn_b,
-                       (const T *)r_k, eps, (T *)out);
-    return finish();
+int tmix_post_fwd(long rows, int D, const void *y, const void *r, const void *k, const void *v, const void *g, const void *gn_w,
+                  const void *gn_b, const void *r_k, float eps, void *out, int nblocks, hipStream_t st) {
+    if (rows <= 0 || nblocks <= 0 || any_null({y, r, k, v, g, gn_w, gn_b, r_k, out})) return RWKV7_EINVAL;
+    if (!row_width_ok(D)) return RWKV7_ESHAPE;
+    return launch_rows(tmix_post_fwd_kernel<T>, nblocks, D, st, rows, D, (const T *)y, (const T *)r, (const T *)k, (const T *)v,
+                       (const T *)g, (const T *)gn_w, (const T *)gn_b, (const T *)r_k, eps, (T *)out);
+}
+// compact (the _compact entries): d_v receives dt and hscal is written, d_r / d_k are not (NULL); otherwise hscal is NULL
+template <typename T>
+int tmix_post_bwd(long rows, int D, bool compact, const void *dout, const void *y, const void *r, const void *k, const void *v,
+                  const void *g, const void *gn_w, const void *gn_b, const void *r_k, float eps, void *d_y, void *d_r, void *d_k,
+                  void *d_v, void *d_g, float *dpart, float *hscal, int nblocks, hipStream_t st) {
+    if (rows <= 0 || nblocks <= 0 || any_null({dout, y, r, k, v, g, gn_w, gn_b, r_k, d_y, d_v, d_g, dpart}) ||
+        (compact ? !hscal : !d_r || !d_k))
+        return RWKV7_EINVAL;
+    if (!row_width_ok(D)) return RWKV7_ESHAPE;
+    return launch_rows(compact ? tmix_post_bwd_kernel<T, true> : tmix_post_bwd_kernel<T, false>, nblocks, D, st, rows, D,
+                       (const T *)dout, (const T *)y, (const T *)r, (const T *)k, (const T *)v, (const T *)g, (const T *)gn_w,
+                       (const T *)gn_b, (const T *)r_k, eps, (T *)d_y, (T *)d_r, (T *)d_k, (T *)d_v, (T *)d_g, dpart, hscal);
+}
+// branch NULL: plain LayerNorm of x, x_out unused; beta NULL: no bias
+template <typename T>
+int add_ln_fwd(long rows, int D, const void *x, const void *branch, const void *gamma, const void *beta, float eps, void *x_out,
+               void *h, float *mean, float *rstd, int nblocks, hipStream_t st) {
+    if (rows <= 0 || nblocks <= 0 || any_null({x, gamma, h, mean, rstd})) return RWKV7_EINVAL;
+    if (branch && !x_out) return RWKV7_EINVAL;
+    if (!row_width_ok(D)) return RWKV7_ESHAPE;
+    return launch_rows(add_ln_fwd_kernel<T>, nblocks, D, st, rows, D, (const T *)x, (const T *)branch, (const T *)gamma,
+                       (const T *)beta, eps, (T *)x_out, (T *)h, mean, rstd);
 }
 template <typename T>
-int tmix_post_bwd(long rows, int D, const void *dout, const void *y, const void *r, const void *k, const void *v,
-                  const void *g, const void *gn_w, const void *gn_b, const void *r_k, float eps, void *d_y, void *d_r,
-                  void *d_k, void *d_v, void *d_g, float *dpart, float *hscal, int nblocks, hipStream_t st) {
-    (void)hipGetLastError();
-    if (hscal)   // compact: d_v receives dt, d_r / d_k are not written
-        hipLaunchKernelGGL((tmix_post_bwd_kernel<T, true>), dim3(nblocks), dim3(D / 8), 0, st, rows, D, (const T *)dout,
-                           (const T *)y, (const T *)r, (const T *)k, (const T *)v, (const T *)g, (const T *)gn_w,
-                           (const T *)gn_b, (const T *)r_k, eps, (T *)d_y, (T *)d_r, (T *)d_k, (T *)d_v, (T *)d_g,
-                           dpart, hscal);
-    else
-        hipLaunchKernelGGL((tmix_post_bwd_kernel<T, false>), dim3(nblocks), dim3(D / 8), 0, st, rows, D, (const T *)dout,
-                           (const T *)y, (const T *)r, (const T *)k, (const T *)v, (const T *)g, (const T *)gn_w,
-                           (const T *)gn_b, (const T *)r_k, eps, (T *)d_y, (T *)d_r, (T *)d_k, (T *)d_v, (T *)d_g,
-                           dpart, hscal);
-    return finish();
+int add_ln_bwd(long rows, int D, const void *dh, const void *d_resid, const void *x1, const float *mean, const float *rstd,
+               const void *gamma, void *dx, float *dpart, int nblocks, hipStream_t st) {
+    if (rows <= 0 || nblocks <= 0 || any_null({dh, x1, mean, rstd, gamma, dx, dpart})) return RWKV7_EINVAL;
+    if (!row_width_ok(D)) return RWKV7_ESHAPE;
+    return launch_rows(add_ln_bwd_kernel<T>, nblocks, D, st, rows, D, (const T *)dh, (const T *)d_resid, (const T *)x1, mean, rstd,
+                       (const T *)gamma, (T *)dx, dpart);
 }
-template <typename T>
-int add_ln_fwd(long rows, int D, const void *x, const void *branch, const void *gamma, const void *beta, float eps,
-               void *x_out, void *h, float *mean, float *rstd, int nblocks, hipStream_t st) {
+// relusq forward and its two backwards over n elements, 8 per thread, grid-stride; every pointer is required
+template <typename... P>
+int relusq(void (*kernel)(long, P...), long n, hipStream_t st, P... ptrs) {
+    if (n <= 0 || any_null({(const void *)ptrs...})) return RWKV7_EINVAL;
+    if (n % 8 != 0) return RWKV7_ESHAPE;
     (void)hipGetLastError();
-    hipLaunchKernelGGL((add_ln_fwd_kernel<T>), dim3(nblocks), dim3(D / 8), 0, st, rows, D, (const T *)x,
-                       (const T *)branch, (const T *)gamma, (const T *)beta, eps, (T *)x_out, (T *)h, mean, rstd);
-    return finish();
-}
-template <typename T>
-int add_ln_bwd(long rows, int D, const void *dh, const void *d_resid, const void *x1, const float *mean,
-               const float *rstd, const void *gamma, void *dx, float *dpart, int nblocks, hipStream_t st) {
-    (void)hipGetLastError();
-    hipLaunchKernelGGL((add_ln_bwd_kernel<T>), dim3(nblocks), dim3(D / 8), 0, st, rows, D, (const T *)dh,
-                       (const T *)d_resid, (const T *)x1, mean, rstd, (const T *)gamma, (T *)dx, dpart);
-    return finish();
+    const long n8 = n / 8;
+    const int grid = (int)((n8 + 255) / 256 < 8192 ? (n8 + 255) / 256 : 8192);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, n8, ptrs...);
+    return (int)hipGetLastError();
 }
 template <typename T>
 int relusq_fwd(long n, const void *x, void *y, hipStream_t st) {
-    (void)hipGetLastError();
-    const long n8 = n / 8;
-    const int grid = (int)((n8 + 255) / 256 < 8192 ? (n8 + 255) / 256 : 8192);
-    hipLaunchKernelGGL((relusq_fwd_kernel<T>), dim3(grid), dim3(256), 0, st, n8, (const T *)x, (T *)y);
-    return finish();
+    return relusq(relusq_fwd_kernel<T>, n, st, (const T *)x, (T *)y);
 }
 template <typename T>
 int relusq_bwd(long n, const void *x, const void *dy, void *dx, hipStream_t st) {
-    (void)hipGetLastError();
-    const long n8 = n / 8;
-    const int grid = (int)((n8 + 255) / 256 < 8192 ? (n8 + 255) / 256 : 8192);
-    hipLaunchKernelGGL((relusq_bwd_kernel<T>), dim3(grid), dim3(256), 0, st, n8, (const T *)x, (const T *)dy, (T *)dx);
-    return finish();
+    return relusq(relusq_bwd_kernel<T>, n, st, (const T *)x, (const T *)dy, (T *)dx);
 }
 template <typename T>
-int relusq_bwd_s(long n, const void *x, const void *dy, void *dx, hipStream_t st) {
-    (void)hipGetLastError();
-    const long n8 = n / 8;
-    const int grid = (int)((n8 + 255) / 256 < 8192 ? (n8 + 255) / 256 : 8192);
-    hipLaunchKernelGGL((relusq_bwd_s_kernel<T>), dim3(grid), dim3(256), 0, st, n8, (const T *)x, (const T *)dy, (T *)dx);
-    return finish();
+int relusq_bwd_s(long n, const void *s, const void *dy, void *dx, hipStream_t st) {
+    return relusq(relusq_bwd_s_kernel<T>, n, st, (const T *)s, (const T *)dy, (T *)dx);
 }
 
-#define INSTANTIATE(T)                                                                                              \
-    template int mix_fwd<T>(int, int, int, int, const void *, const void *, const void *, const void *, void *, int, \
-                            hipStream_t);                                                                           \
-    template int mix_bwd<T>(int, int, int, int, const void *const *, const void *, const void *, const void *,       \
-                            const void *, void *, float *, int, int, hipStream_t);                                                     \
-    template int tmix_prepare_fwd<T>(long, int, const void *, const void *, const void *, const void *, const void *, \
-                                     const void *, const void *, const void *, const void *, void *, void *, void *, \
-                                     void *, void *, int, hipStream_t);                                             \
-    template int add_ln_fwd<T>(long, int, const void *, const void *, const void *, const void *, float, void *, void *, \
-                               float *, float *, int, hipStream_t);                                                 \
-    template int add_ln_bwd<T>(long, int, const void *, const void *, const void *, const float *, const float *,    \
-                               const void *, void *, float *, int, hipStream_t);                                     \
-    template int add_ln_mix_fwd<T>(int, int, int, int, void *, const void *, const void *, const void *, const void *, float, const void *, \
-                                   const void *, void *, void *, float *, float *, int, int, hipStream_t);           \
-    template int mix_add_ln_bwd<T>(int, int, int, int, const void *const *, const void *, const void *, const float *, const float *, \
-                                   const void *, const void *, const void *, const void *, void *, float *, int, int, hipStream_t); \
-    template int tmix_prepare_bwd_sum<T>(long, int, const void *, const void *, const void *, const void *,          \
-                                         const void *, const void *, const void *, const void *, const void *,       \
-                                         const void *const *, int, void *, void *, void *, void *, void *, void *, void *, \
-                                         float *, int, hipStream_t);                                                 \
-    template int tmix_prepare_bwd<T>(long, int, const void *, const void *, const void *, const void *, const void *, \
-                                     const void *, const void *, const void *, const void *, const void *,          \
-                                     const void *, const void *, const void *, const void *, void *, void *, void *, \
-                                     void *, void *, void *, float *, int, hipStream_t);                            \
-    template int tmix_post_fwd<T>(long, int, const void *, const void *, const void *, const void *, const void *,  \
-                                  const void *, const void *, const void *, float, void *, int, hipStream_t);       \
-    template int tmix_post_bwd<T>(long, int, const void *, const void *, const void *, const void *, const void *,  \
-                                  const void *, const void *, const void *, const void *, float, void *, void *,    \
-                                  void *, void *, void *, float *, float *, int, hipStream_t);                               \
-    template int relusq_fwd<T>(long, const void *, void *, hipStream_t);                                            \
-    template int relusq_bwd<T>(long, const void *, const void *, void *, hipStream_t);                              \
-    template int relusq_bwd_s<T>(long, const void *, const void *, void *, hipStream_t);
-INSTANTIATE(bf16_t)
-INSTANTIATE(float)
-
 }  // namespace rwkv7
+
+// ---- the extern "C" entries of the stages above, for bf16 and fp32: the signature of include/rwkv7_hip.h (included above, so an
+//      entry that departs from its prototype does not compile) and one forwarding call each.  No check lives here.
+#define EW_ENTRIES(SFX, TY) \
+    int rwkv7_mix_fwd_##SFX(int B, int T, int D, int nmix, const void *x, const void *x_prev, const void *mask, const void *params, \
+                            void *out, int nblocks, rwkv7_stream_t stream) { \
+        return rwkv7::mix_fwd<TY>(B, T, D, nmix, x, x_prev, mask, params, out, nblocks, (hipStream_t)stream); \
+    } \
+    int rwkv7_mix_bwd_##SFX(int B, int T, int D, int nmix, const void *const *g, const void *x, const void *x_prev, const void *mask, \
+                            const void *params, void *dx, float *dpart, int nblocks, int run_len, rwkv7_stream_t stream) { \
+        return rwkv7::mix_bwd<TY>(B, T, D, nmix, g, x, x_prev, mask, params, dx, dpart, nblocks, run_len, (hipStream_t)stream); \
+    } \
+    int rwkv7_tmix_prepare_fwd_##SFX(long rows, int D, const void *w_pre, const void *k, const void *v, const void *a_pre, \
+                                     const void *v_pre, const void *v_first, const void *mask, const void *k_k, const void *k_a, \
+                                     void *w, void *k2, void *v2, void *ain, void *bin, int nblocks, rwkv7_stream_t stream) { \
+        return rwkv7::tmix_prepare_fwd<TY>(rows, D, w_pre, k, v, a_pre, v_pre, v_first, mask, k_k, k_a, w, k2, v2, ain, bin, nblocks, \
+                                           (hipStream_t)stream); \
+    } \
+    int rwkv7_add_ln_fwd_##SFX(long rows, int D, const void *x, const void *branch, const void *gamma, const void *beta, float eps, \
+                               void *x_out, void *h, float *mean, float *rstd, int nblocks, rwkv7_stream_t stream) { \
+        return rwkv7::add_ln_fwd<TY>(rows, D, x, branch, gamma, beta, eps, x_out, h, mean, rstd, nblocks, (hipStream_t)stream); \
+    } \
+    int rwkv7_add_ln_bwd_##SFX(long rows, int D, const void *dh, const void *d_resid, const void *x1, const float *mean, \
+                               const float *rstd, const void *gamma, void *dx, float *dpart, int nblocks, rwkv7_stream_t stream) { \
+        return rwkv7::add_ln_bwd<TY>(rows, D, dh, d_resid, x1, mean, rstd, gamma, dx, dpart, nblocks, (hipStream_t)stream); \
+    } \
+    int rwkv7_add_ln_mix_fwd_##SFX(int B, int T, int D, int nmix, const void *x, const void *branch, const void *gamma, \
+                                   const void *beta, float eps, const void *mask, const void *params, void *x_out, void *out, \
+                                   float *mean, float *rstd, int nblocks, int run_len, rwkv7_stream_t stream) { \
+        return rwkv7::add_ln_mix_fwd<TY>(B, T, D, nmix, false, nullptr, x, branch, gamma, beta, eps, mask, params, x_out, out, mean, \
+                                         rstd, nblocks, run_len, (hipStream_t)stream); \
+    } \
+    int rwkv7_add_ln_mix_fwd_h_##SFX(int B, int T, int D, int nmix, const void *x, const void *branch, const void *gamma, \
+                                     const void *beta, float eps, const void *mask, const void *params, void *x_out, void *out, \
+                                     void *h, float *mean, float *rstd, int nblocks, int run_len, rwkv7_stream_t stream) { \
+        return rwkv7::add_ln_mix_fwd<TY>(B, T, D, nmix, true, h, x, branch, gamma, beta, eps, mask, params, x_out, out, mean, rstd, \
+                                         nblocks, run_len, (hipStream_t)stream); \
+    } \
+    int rwkv7_mix_add_ln_bwd_##SFX(int B, int T, int D, int nmix, const void *const *g, const void *d_resid, const void *x1, \
+                                   const float *mean, const float *rstd, const void *gamma, const void *beta, const void *mask, \
+                                   const void *params, void *dx, float *dpart, int nblocks, int run_len, rwkv7_stream_t stream) { \
+        return rwkv7::mix_add_ln_bwd<TY>(B, T, D, nmix, g, d_resid, x1, mean, rstd, gamma, beta, mask, params, dx, dpart, nblocks, \
+                                         run_len, (hipStream_t)stream); \
+    } \
+    int rwkv7_tmix_prepare_bwd_sum_##SFX(long rows, int D, const void *w_pre, const void *k, const void *v, const void *a_pre, \
+                                         const void *v_pre, const void *v_first, const void *mask, const void *k_k, const void *k_a, \
+                                         const void *const *gsum, void *d_wpre, void *d_k, void *d_v, void *d_apre, void *d_vpre, \
+                                         void *d_vfirst, void *d_r, float *dpart, int nblocks, rwkv7_stream_t stream) { \
+        return rwkv7::tmix_prepare_bwd_sum<TY>(rows, D, w_pre, k, v, a_pre, v_pre, v_first, mask, k_k, k_a, gsum, 15, d_wpre, d_k, d_v, \
+                                               d_apre, d_vpre, d_vfirst, d_r, dpart, nblocks, (hipStream_t)stream); \
+    } \
+    int rwkv7_tmix_prepare_bwd_sum_compact_##SFX(long rows, int D, const void *w_pre, const void *k, const void *v, const void *a_pre, \
+                                                 const void *v_pre, const void *v_first, const void *mask, const void *k_k, \
+                                                 const void *k_a, const void *const *gsum, void *d_wpre, void *d_k, void *d_v, \
+                                                 void *d_apre, void *d_vpre, void *d_vfirst, void *d_r, float *dpart, int nblocks, \
+                                                 rwkv7_stream_t stream) { \
+        return rwkv7::tmix_prepare_bwd_sum<TY>(rows, D, w_pre, k, v, a_pre, v_pre, v_first, mask, k_k, k_a, gsum, 19, d_wpre, d_k, d_v, \
+                                               d_apre, d_vpre, d_vfirst, d_r, dpart, nblocks, (hipStream_t)stream); \
+    } \
+    int rwkv7_tmix_prepare_bwd_##SFX(long rows, int D, const void *w_pre, const void *k, const void *v, const void *a_pre, \
+                                     const void *v_pre, const void *v_first, const void *mask, const void *k_k, const void *k_a, \
+                                     const void *d_w, const void *d_k2, const void *d_v2, const void *d_ain, const void *d_bin, \
+                                     void *d_wpre, void *d_k, void *d_v, void *d_apre, void *d_vpre, void *d_vfirst, float *dpart, \
+                                     int nblocks, rwkv7_stream_t stream) { \
+        return rwkv7::tmix_prepare_bwd<TY>(rows, D, w_pre, k, v, a_pre, v_pre, v_first, mask, k_k, k_a, d_w, d_k2, d_v2, d_ain, d_bin, \
+                                           d_wpre, d_k, d_v, d_apre, d_vpre, d_vfirst, dpart, nblocks, (hipStream_t)stream); \
+    } \
+    int rwkv7_tmix_post_fwd_##SFX(long rows, int D, const void *y, const void *r, const void *k, const void *v, const void *g, \
+                                  const void *gn_w, const void *gn_b, const void *r_k, float eps, void *out, int nblocks, \
+                                  rwkv7_stream_t stream) { \
+        return rwkv7::tmix_post_fwd<TY>(rows, D, y, r, k, v, g, gn_w, gn_b, r_k, eps, out, nblocks, (hipStream_t)stream); \
+    } \
+    int rwkv7_tmix_post_bwd_##SFX(long rows, int D, const void *dout, const void *y, const void *r, const void *k, const void *v, \
+                                  const void *g, const void *gn_w, const void *gn_b, const void *r_k, float eps, void *d_y, void *d_r, \
+                                  void *d_k, void *d_v, void *d_g, float *dpart, int nblocks, rwkv7_stream_t stream) { \
+        return rwkv7::tmix_post_bwd<TY>(rows, D, false, dout, y, r, k, v, g, gn_w, gn_b, r_k, eps, d_y, d_r, d_k, d_v, d_g, dpart, \
+                                        nullptr, nblocks, (hipStream_t)stream); \
+    } \
+    int rwkv7_tmix_post_bwd_compact_##SFX(long rows, int D, const void *dout, const void *y, const void *r, const void *k, \
+                                          const void *v, const void *g, const void *gn_w, const void *gn_b, const void *r_k, float eps, \
+                                          void *d_y, void *dt, void *d_g, float *hscal, float *dpart, int nblocks, \
+                                          rwkv7_stream_t stream) { \
+        return rwkv7::tmix_post_bwd<TY>(rows, D, true, dout, y, r, k, v, g, gn_w, gn_b, r_k, eps, d_y, nullptr, nullptr, dt, d_g, dpart, \
+                                        hscal, nblocks, (hipStream_t)stream); \
+    } \
+    int rwkv7_relusq_fwd_##SFX(long n, const void *x, void *y, rwkv7_stream_t stream) { \
+        return rwkv7::relusq_fwd<TY>(n, x, y, (hipStream_t)stream); \
+    } \
+    int rwkv7_relusq_bwd_##SFX(long n, const void *x, const void *dy, void *dx, rwkv7_stream_t stream) { \
+        return rwkv7::relusq_bwd<TY>(n, x, dy, dx, (hipStream_t)stream); \
+    } \
+    int rwkv7_relusq_bwd_s_##SFX(long n, const void *s, const void *dy, void *dx, rwkv7_stream_t stream) { \
+        return rwkv7::relusq_bwd_s<TY>(n, s, dy, dx, (hipStream_t)stream); \
+    }
+
+extern "C" {
+EW_ENTRIES(bf16, rwkv7::bf16_t)
+EW_ENTRIES(f32, float)
+}
+#undef EW_ENTRIES
+

@@ -34,6 +34,7 @@
 // groups staggered by one step, one reading fragments while the other runs MFMAs: 320 us (gemm_nt8s_staggered_groups.hip: a load step
 // moves 64 KB through the LDS, as long as the MFMAs beside it, plus latency and a barrier); the DMA in its scalar-base form
 // (inline asm, no 64-bit VALU add per instruction): +-0.
+#include "launchers.h"
 #include "chunk_common.h"
 #include "launch_attr.h"
 #ifndef GEMM4_EXP

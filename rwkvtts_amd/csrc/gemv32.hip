@@ -15,6 +15,7 @@
 // suggests: every lane of a fragment load reads a different 2 KB-strided row (32 lines per instruction) and each call
 // still pays ~5 us of launch/drain even inside a hipGraph.  The decode step went 4.4 -> 4.0 ms; the real lever is fewer,
 // fused kernels per layer (655 launches per step).
+#include "launchers.h"
 #include "chunk_common.h"
 
 namespace rwkv7 {

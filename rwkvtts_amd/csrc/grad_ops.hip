@@ -6,6 +6,7 @@
 //   * AdamW with the clip factor taken from device memory.
 // Bytes per element: 2 for the norm, 6 for the first accumulate of a window (10 for the later ones, which also read the
 // fp32 sum), 8 for the fold, against AdamW's 28.
+#include "launchers.h"
 #include "adamw_body.h"
 
 namespace rwkv7 {

@@ -5,6 +5,7 @@
 // the partials meet.  So head_eval_kernel's loss_rows / correct_rows are bit-identical to the training kernels' by construction.
 // Labels are NOT checked on the device (the kernels index x[label] for rows whose label is not ignore_index); columns V .. ld - 1 are
 // neither read nor written.
+#include "launchers.h"
 #include "ln_row.h"
 
 namespace rwkv7 {

@@ -8,26 +8,10 @@
 // through RWKV7_HIP_SO.  Each variant is its own entry point: the library has no process-wide switches (threading row).
 #include <hip/hip_runtime.h>
 
-#include <initializer_list>
-
 #include "../../../include/rwkv7_hip_lab.h"
+#include "../launchers.h"   // the lab section
 
-namespace rwkv7 {
-int chunk_bwd_out9_bf16(int, int, int, const void *, const void *, const void *, const void *, const void *, const void *, const void *,
-                        const void *, const float *, const float *, const void *, void *, void *, void *, void *, void *, void *, hipStream_t);
-int chunk_fwd4_bf16(int, int, int, const void *, const void *, const void *, const void *, const void *, const void *, const float *, void *,
-                    float *, void *, const int *, int, hipStream_t);
-int gemm_nt_bf16_variant(int, int, int, const void *, const void *, void *, int, int, hipStream_t);
-int gemm_nt_relusq_bwd_bf16(int, int, int, const void *, const void *, const void *, void *, hipStream_t);
-}  // namespace rwkv7
-
-namespace {
-bool any_null(std::initializer_list<const void *> ps) {
-    for (const void *p : ps)
-        if (p == nullptr) return true;
-    return false;
-}
-}  // namespace
+using rwkv7::any_null;
 
 extern "C" {
 int rwkv7_lab_wkv_chunk_bwd_out9_z_bf16(int B, int T, int H, const void *w, const void *q, const void *k, const void *v, const void *a,

@@ -15,6 +15,7 @@
 // the same box (0.856 before).  K tile 32 with four buffers (three tiles in flight, counted vmcnt, raw barrier): slower (0.83) --
 // it is not the DMA latency that limits the loop.  PMC: same HBM traffic and L2 misses as the library's kernel, 1.6x its L2
 // requests.  Outcome of the experiment: fused.py (FUSED_KEY_RELUSQ) -- ties the library pair inside the training step, not adopted.
+#include "../launchers.h"
 #include "../chunk_common.h"
 #include "../launch_attr.h"
 

@@ -20,6 +20,7 @@
 // the wave that had nothing in phase A)
 // then the ten accumulator tiles are staged (fp32, over the dead operand planes) and the epilogue runs as before.  T^-1, A_qb and
 // G1 are not needed at all: 28 (rows) + 8 (u) + 8 (z) + 8.5 (E) + 8.5 (H_C) KB in, 24 KB out per chunk; LDS 133 KB.
+#include "../launchers.h"
 #include "../chunk_bwd_common.h"
 #include "../launch_attr.h"
 

@@ -1,7 +1,10 @@
 // rwkvtts_amd/csrc/ln_row.h -- what the row-stream kernels that LayerNorm a row share (elementwise.hip, prefill_rows.hip): 8-channel
 // vector I/O, the workgroup sums with a pinned summation order, and the residual add + LayerNorm of one row (add_ln_row), so that
-// every kernel built on it gives the same bits for the same row.
+// every kernel built on it gives the same bits for the same row; and, on the host, the one launch shape they all have.
 #pragma once
+#include <type_traits>
+
+#include "../../include/rwkv7_hip.h"
 #include "wkv7_common.h"
 
 namespace rwkv7 {
@@ -171,6 +174,27 @@ __device__ __forceinline__ void add_ln_row(const RowPre<T> &f, long o, bool has_
     if (write && h_out) V8<T>::st(h_out + o, hm);
 #pragma unroll
     for (int j = 0; j < 8; j++) hm[j] *= m;
+}
+
+// ---- host side: how every row-stream kernel is launched ---------------------------------------------------------------------------
+// a row of D channels on D/8 threads, whole heads (64 channels) only
+inline bool row_width_ok(int D) { return D > 0 && D % 64 == 0 && D <= kEwMaxThreads * 8; }
+
+// nblocks workgroups of D/8 threads; returns the launch's error
+template <typename... P, typename... A>
+int launch_rows(void (*kernel)(P...), int nblocks, int D, hipStream_t st, A... args) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(D / 8), 0, st, args...);
+    return (int)hipGetLastError();
+}
+
+// launch(std::integral_constant<int, N>) for the N of NS... that equals nmix: NS is the list of lerp counts a stage instantiates its
+// kernel for, and an nmix outside it is RWKV7_ESHAPE
+template <int... NS, typename F>
+int for_nmix(int nmix, F launch) {
+    int rc = RWKV7_ESHAPE;
+    (void)((nmix == NS && ((rc = launch(std::integral_constant<int, NS>{})), true)) || ...);
+    return rc;
 }
 
 }  // namespace rwkv7

@@ -21,21 +21,14 @@
 // overlap only across the two waves of a SIMD; ~10 us of staging skeleton (16 stages: 45 KB of register -> LDS stores and a barrier
 // each); the loads add ~8 us that hide only in part.  HBM: 67 MB in, 19 MB out.  The backward is unchanged (fused.py:
 // rwkv7_mix_lora_combine_bwd / wcat_* on the through-the-lerp form, which is the exact gradient of this forward).
-#include "chunk_common.h"
-#include "launch_attr.h"
 #include <type_traits>
 
-namespace rwkv7 {
+#include "../../include/rwkv7_hip.h"   // RWKV7_ESHAPE
+#include "chunk_common.h"
+#include "launch_attr.h"
+#include "launchers.h"
 
-struct LoraDownDesc {
-    int nb;               // branches
-    int r[4], off[4];     // rank and first output column of each branch inside R
-    int act[4];           // 0 none, 1 tanh, 2 sigmoid
-    const void *w1[4];    // pack: Linear(D, r_i).weight [r_i][D]
-    const void *mu[4];    // lerp coefficient [D]
-    void *out[4];         // [M][r_i]
-    int tile0[5];         // column group g owns the 32-column tiles tile0[g] .. tile0[g + 1] - 1
-};
+namespace rwkv7 {
 
 namespace {
 constexpr int kRows = 128;          // rows per workgroup
@@ -347,7 +340,7 @@ int lora_down_pack(const LoraDownDesc &d, int R, int D, void *packed, hipStream_
 
 // M % 128 == 0, M % T == 0, D % 128 == 0, ranks multiples of 32, 2..10 column tiles that cut into two halves of at most two branches
 int lora_down_fwd(LoraDownDesc &d, int R, long M, int T, int D, const void *x, const void *mask, const void *packed, hipStream_t st) {
-    if (lora_down_cut(d, R) < 0) return -4;
+    if (lora_down_cut(d, R) < 0) return RWKV7_ESHAPE;
     const bool generic = mask != nullptr || T % kRows != 0;
     return generic ? launch_lora_down<true>(d, M, T, D, x, mask, packed, st) : launch_lora_down<false>(d, M, T, D, x, mask, packed, st);
 }

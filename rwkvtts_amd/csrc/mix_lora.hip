@@ -6,19 +6,10 @@
 //   combine_fwd / _bwd      h[t] = m_t G_a[t] + m_{t-1} G_b[t - 1] (nothing before the first step of a sequence), rounded to bf16 as the
 //                           projection's output would be, then the branch's activation (none / tanh / sigmoid), written per branch [M, r_i]
 // All bf16, fp32 arithmetic; every tensor here is at most [M, 2 R] with R <= 288 columns: what was six [M, D] streams is on the small side.
+#include "launchers.h"
 #include "wkv7_common.h"
 
 namespace rwkv7 {
-
-struct MixLoraDesc {
-    int nb;               // branches (3 in layer 0: w, a, g; else 4: w, a, v, g)
-    int r[4], off[4];     // rank and first column of each branch inside R
-    int act[4];           // 0 none, 1 tanh, 2 sigmoid
-    const void *w1[4];    // Linear(D, r_i).weight  [r_i][D]
-    const void *mu[4];    // lerp coefficient [D]
-    void *out[4];         // fwd: activation outputs [M][r_i];  wcat_bwd: dW1_i [r_i][D]
-    void *out2[4];        // wcat_bwd: dmu_i [D];  combine_bwd: the incoming gradients d a_i [M][r_i]
-};
 
 namespace {
 __device__ __forceinline__ int branch_of(const MixLoraDesc &d, int col) {

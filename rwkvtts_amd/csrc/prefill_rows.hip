@@ -14,6 +14,7 @@
 // x_prev_rd and x_prev may be the same field: a row that reads and writes the same r reads first, inside the thread that owns the
 // channels.  Two DIFFERENT rows of one launch that read and write the same r (the first and the last row of a longer piece) race
 // unless x_prev_rd is a snapshot.  r is not range-checked: device data, the caller's guarantee (include/rwkv7_hip.h).
+#include "launchers.h"
 #include "ln_row.h"
 
 namespace rwkv7 {
@@ -102,18 +103,12 @@ __global__ __launch_bounds__(kEwMaxThreads) void add_ln_mix_rows_kernel(int T_, 
 int add_ln_mix_rows_fwd_bf16(int T_, int D, int nmix, const void *x, const void *branch, const void *gamma, const void *beta, float eps,
                              const void *mask, const void *params, const int *prev_src, const int *last_dst, const void *x_prev_rd,
                              void *x_prev, void *x_out, void *out, int nblocks, int run_len, hipStream_t st) {
-    (void)hipGetLastError();
     using T = bf16_t;
-    const dim3 grid(nblocks), block(D / 8);
-    if (nmix == 6)
-        hipLaunchKernelGGL((add_ln_mix_rows_kernel<6>), grid, block, 0, st, T_, D, run_len, (const T *)x, (const T *)branch, (const T *)gamma,
-                           (const T *)beta, eps, (const T *)mask, (const T *)params, prev_src, last_dst, (const T *)x_prev_rd, (T *)x_prev,
-                           (T *)x_out, (T *)out);
-    else
-        hipLaunchKernelGGL((add_ln_mix_rows_kernel<1>), grid, block, 0, st, T_, D, run_len, (const T *)x, (const T *)branch, (const T *)gamma,
-                           (const T *)beta, eps, (const T *)mask, (const T *)params, prev_src, last_dst, (const T *)x_prev_rd, (T *)x_prev,
-                           (T *)x_out, (T *)out);
-    return (int)hipGetLastError();
+    return for_nmix<1, 6>(nmix, [&](auto n) {
+        return launch_rows(add_ln_mix_rows_kernel<decltype(n)::value>, nblocks, D, st, T_, D, run_len, (const T *)x, (const T *)branch,
+                           (const T *)gamma, (const T *)beta, eps, (const T *)mask, (const T *)params, prev_src, last_dst,
+                           (const T *)x_prev_rd, (T *)x_prev, (T *)x_out, (T *)out);
+    });
 }
 
 }  // namespace rwkv7

@@ -20,6 +20,7 @@
 
 #include <type_traits>
 
+#include "launchers.h"
 #include "sampling_common.h"
 
 namespace rwkv7 {

@@ -21,6 +21,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launchers.h"
+
 // the library is built with -ffast-math: the order stated above is a contract, so no reassociation of the fp64 adds in this file
 #pragma clang fp reassociate(off)
 

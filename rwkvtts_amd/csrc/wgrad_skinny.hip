@@ -12,6 +12,7 @@
 // transpose read (frag_tr), so nothing is transposed in memory.  Row strides of the planes are = 16 (mod 64) dwords: the four
 // token rows a transpose read touches then fall into disjoint bank windows.  Partials [S][N][K] fp32 are summed (and rounded to
 // bf16, straight into the gradient buffer) by rwkv7_sum_slabs_bf16.
+#include "launchers.h"
 #include "chunk_common.h"
 
 namespace rwkv7 {

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launchers.h"
 #include "sampling_common.h"
 
 namespace rwkv7 {

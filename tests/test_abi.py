@@ -171,3 +171,124 @@ def test_struct_mirrors_match_the_compiler(tmp_path):
     for s, cls in mirrors.items():
         py_side = [(".", ctypes.sizeof(cls), 0)] + [(n, getattr(cls, n).offset, getattr(cls, n).size) for n, *_ in cls._fields_]
         assert py_side == c_side[s], s
+
+
+# ---- the fused row stages: what every entry refuses before a launch ------------------------------------------------------------
+# One line per entry, parameters in the header's order as name:kind.  Kinds: P required pointer, O pointer that may be NULL on its
+# own, Q pointer that may be NULL only together with others (the cases are spelled out per entry), N count that must be positive,
+# D row width (a multiple of 64, at most 4096), M nmix, G host array of nmix gradient pointers, S15 / S19 host array gsum, E element
+# count of relusq (positive multiple of 8), T32 row count that must be a positive multiple of 32, F float.
+_PREP_IN = "rows:N D:D w_pre:P k:P v:P a_pre:P v_pre:Q v_first:Q mask:O k_k:P k_a:P"
+_PREP_OUT = "d_wpre:P d_k:P d_v:P d_apre:P d_vpre:Q d_vfirst:Q"
+_POST_IN = "rows:N D:D dout:P y:P r:P k:P v:P g:P gn_w:P gn_b:P r_k:P eps:F"
+_LN_MIX = "B:N T:N D:D nmix:M x:P branch:Q gamma:P beta:O eps:F mask:O params:P x_out:Q out:P"
+_FUSED_ENTRIES = {
+    "mix_fwd": "B:N T:N D:D nmix:M x:P x_prev:O mask:O params:P out:P nblocks:N",
+    "mix_bwd": "B:N T:N D:D nmix:M g:G x:P x_prev:O mask:O params:P dx:P dpart:P nblocks:N run_len:N",
+    "tmix_prepare_fwd": _PREP_IN + " w:P k2:P v2:P ain:P bin:P nblocks:N",
+    "tmix_prepare_bwd": _PREP_IN + " d_w:P d_k2:P d_v2:P d_ain:P d_bin:P " + _PREP_OUT + " dpart:P nblocks:N",
+    "tmix_prepare_bwd_sum": _PREP_IN + " gsum:S15 " + _PREP_OUT + " d_r:P dpart:P nblocks:N",
+    "tmix_prepare_bwd_sum_compact": _PREP_IN + " gsum:S19 " + _PREP_OUT + " d_r:P dpart:P nblocks:N",
+    "add_ln_fwd": "rows:N D:D x:P branch:Q gamma:P beta:O eps:F x_out:Q h:P mean:P rstd:P nblocks:N",
+    "add_ln_bwd": "rows:N D:D dh:P d_resid:O x1:P mean:P rstd:P gamma:P dx:P dpart:P nblocks:N",
+    "add_ln_mix_fwd": _LN_MIX + " mean:P rstd:P nblocks:N run_len:N",
+    "add_ln_mix_fwd_h": _LN_MIX + " h:P mean:P rstd:P nblocks:N run_len:N",
+    "mix_add_ln_bwd": "B:N T:N D:D nmix:M g:G d_resid:O x1:P mean:P rstd:P gamma:P beta:O mask:O params:P dx:P dpart:P "
+                      "nblocks:N run_len:N",
+    "tmix_post_fwd": "rows:N D:D y:P r:P k:P v:P g:P gn_w:P gn_b:P r_k:P eps:F out:P nblocks:N",
+    "tmix_post_bwd": _POST_IN + " d_y:P d_r:P d_k:P d_v:P d_g:P dpart:P nblocks:N",
+    "tmix_post_bwd_compact": _POST_IN + " d_y:P dt:P d_g:P hscal:P dpart:P nblocks:N",
+    "relusq_fwd": "n:E x:P y:P",
+    "relusq_bwd": "n:E x:P dy:P dx:P",
+    "relusq_bwd_s": "n:E s:P dy:P dx:P",
+    "add_ln_mix_rows_fwd": "T:T32 D:D nmix:M x:P branch:Q gamma:P beta:O eps:F mask:O params:P prev_src:P last_dst:P x_prev_rd:O "
+                           "x_prev:P x_out:Q out:P nblocks:N run_len:N",
+}
+# nmix values an entry has no kernel for, beside 2 (no entry has one), 0 and 7
+_NO_NMIX = {"mix_add_ln_bwd": (3,), "add_ln_mix_rows_fwd": (3,)}
+# gsum slots that must be set; every other slot may be NULL (include/rwkv7_hip.h: the second partials, d_vfirst_in, and for the
+# compact entry the post tensors 4, 6, 13)
+_GSUM_REQUIRED = {"S15": (0, 2, 4, 5, 6, 7, 9, 11, 13), "S19": (0, 2, 5, 7, 9, 11, 15, 16, 17, 18)}
+_EINVAL, _ESHAPE = -1, -4
+_BAD_D = 72   # the one broken rule of the cases that show a NULL is accepted: were the NULL refused too, the entry would answer -1
+
+
+def _fused_cases(name, params):
+    """[(label, {parameter: value}, expected code)]: each case breaks exactly one rule of a call that is otherwise valid."""
+    kinds = dict(params)
+    cases = []
+    for p, kind in params:
+        if kind == "P":
+            cases.append((f"{p} NULL", {p: None}, _EINVAL))
+        elif kind == "O":
+            cases.append((f"{p} NULL is allowed", {p: None, "D": _BAD_D}, _ESHAPE))
+        elif kind in ("N", "E", "T32"):
+            cases += [(f"{p} = {v}", {p: v}, _EINVAL) for v in (0, -1)]
+            if kind == "E":
+                cases.append((f"{p} % 8 != 0", {p: 12}, _ESHAPE))
+            if kind == "T32":
+                cases.append((f"{p} % 32 != 0", {p: 48}, _ESHAPE))
+        elif kind == "D":
+            cases += [(f"{p} = {v}", {p: v}, _ESHAPE) for v in (0, 72, 4160)]
+        elif kind == "M":
+            cases += [(f"{p} = {v}", {p: v}, _ESHAPE) for v in (2, 0, 7) + _NO_NMIX.get(name, ())]
+        elif kind == "G":
+            cases.append((f"{p} NULL", {p: None}, _EINVAL))
+            for i in range(6):
+                arr = (ctypes.c_void_p * 6)(*([16] * 6))
+                arr[i] = None
+                cases.append((f"{p}[{i}] NULL, nmix = 6", {p: arr, "nmix": 6}, _EINVAL))
+        elif kind in _GSUM_REQUIRED:
+            n = int(kind[1:])
+            cases.append((f"{p} NULL", {p: None}, _EINVAL))
+            for i in range(n):
+                arr = (ctypes.c_void_p * n)(*([16] * n))
+                arr[i] = None
+                if i in _GSUM_REQUIRED[kind]:
+                    cases.append((f"{p}[{i}] NULL", {p: arr}, _EINVAL))
+                else:
+                    cases.append((f"{p}[{i}] NULL is allowed", {p: arr, "D": _BAD_D}, _ESHAPE))
+    if "branch" in kinds:
+        cases += [("branch without x_out", {"x_out": None}, _EINVAL),
+                  ("x_out without branch is allowed", {"branch": None, "D": _BAD_D}, _ESHAPE),
+                  ("neither branch nor x_out is allowed", {"branch": None, "x_out": None, "D": _BAD_D}, _ESHAPE)]
+    if "v_pre" in kinds:
+        absent = {"v_pre": None, "v_first": None}
+        cases += [("v_pre without v_first", {"v_first": None}, _EINVAL), ("v_first without v_pre", {"v_pre": None}, _EINVAL)]
+        if "d_vpre" in kinds:
+            absent.update(d_vpre=None, d_vfirst=None)
+            cases += [("v_pre without d_vpre", {"d_vpre": None}, _EINVAL), ("v_pre without d_vfirst", {"d_vfirst": None}, _EINVAL),
+                      ("d_vpre and d_vfirst without v_pre are allowed", {"v_pre": None, "v_first": None, "D": _BAD_D}, _ESHAPE)]
+        cases.append(("layer 0 (no value residual) is allowed", dict(absent, D=_BAD_D), _ESHAPE))
+    return cases
+
+
+def _fused_valid(kind):
+    one = ctypes.c_void_p(16)  # never dereferenced: every case is refused before a launch
+    if kind in ("P", "O", "Q"):
+        return one
+    if kind == "G":
+        return (ctypes.c_void_p * 6)(*([16] * 6))
+    if kind in _GSUM_REQUIRED:
+        return (ctypes.c_void_p * int(kind[1:]))(*([16] * int(kind[1:])))
+    return {"N": 4, "D": 64, "M": 1, "E": 64, "T32": 32, "F": 1e-5}[kind]
+
+
+@pytest.mark.parametrize("name,sfx", [(n, s) for n in sorted(_FUSED_ENTRIES) for s in ("bf16", "f32")
+                                      if (n, s) != ("add_ln_mix_rows_fwd", "f32")])   # the packed-rows entry exists in bf16 only
+def test_fused_stage_entries_refuse_before_launch(hip_lib, name, sfx):
+    """Every fused row-stage entry, one broken rule per call, answers the code include/rwkv7_hip.h gives for that rule: RWKV7_EINVAL
+    (-1) for a missing pointer or a count below 1, RWKV7_ESHAPE (-4) for a size no kernel exists for.  Nothing is launched."""
+    fn = getattr(hip_lib, f"rwkv7_{name}_{sfx}")
+    params = [tuple(p.split(":")) for p in _FUSED_ENTRIES[name].split()]
+    assert len(fn.argtypes) == len(params) + 1, "the table's parameter list is not the header's"
+    cases = _fused_cases(name, params)
+    assert len({label for label, _, _ in cases}) == len(cases)
+    wrong = []
+    for label, change, want in cases:
+        assert set(change) <= {p for p, _ in params}
+        args = [change[p] if p in change else _fused_valid(kind) for p, kind in params]
+        got = fn(*args, None)
+        if got != want:
+            wrong.append(f"{label}: {got}, expected {want}")
+    assert not wrong, f"rwkv7_{name}_{sfx}: " + "; ".join(wrong)
