@@ -458,6 +458,19 @@ int rwkv7_ce_fwd_bwd_ls_bf16(long rows, int V, void *logits, const long *labels,
  *      neither read nor written). */
 int rwkv7_ce_fwd_bwd_ld_bf16(long rows, int V, long ld, void *logits, const long *labels, long ignore_index, float scale, float *loss_rows,
                              float label_smoothing, rwkv7_stream_t stream);
+/*      The backward of a per-SEQUENCE sum of log-probabilities (losses.fused_linear_seq_logprob): the plain cross-entropy gradient
+ *      (label smoothing 0) of a chunk of logits [rows, ld] whose scale is looked up per row.  Row r of the chunk is row row0 + r of the
+ *      batch; its sequence is the largest s < n_seq with seq_start[s] <= row0 + r, provided row0 + r < seq_start[n_seq] (seq_start:
+ *      int64 [n_seq + 1] on the DEVICE, non-decreasing; equal neighbours are empty sequences).  The row is REPLACED by
+ *      (softmax - onehot) * seq_scale[s] (seq_scale: fp32 [n_seq] on the DEVICE; the product is formed in fp32 and rounded to bf16
+ *      once): bit for bit what rwkv7_ce_fwd_bwd_ld_bf16 writes with scale = seq_scale[s] and label_smoothing = 0.  Rows with
+ *      label == ignore_index, rows in front of seq_start[0] and rows at or behind seq_start[n_seq] are replaced by zeros (finite
+ *      logits).  loss_rows may be NULL; otherwise it receives what rwkv7_ce_fwd_bwd_ld_bf16 writes, for every row of the chunk
+ *      whatever its sequence.  Columns V .. ld - 1 are neither read nor written.  seq_start is NOT range-checked beyond that.  No
+ *      atomics, nothing shared between rows.  RWKV7_EINVAL, before any launch: a NULL logits / labels / seq_start / seq_scale,
+ *      rows <= 0, V <= 0, ld < V, row0 < 0, n_seq <= 0. */
+int rwkv7_ce_seq_bwd_bf16(long rows, int V, long ld, void *logits, const long *labels, long ignore_index, long row0, long n_seq,
+                          const long *seq_start, const float *seq_scale, float *loss_rows, rwkv7_stream_t stream);
 /* ---- Cosy head loss: label-smoothing KL loss (cosyvoice/transformer/label_smoothing_loss.py:68-96), its gradient and the accuracy
  *      flag (cosyvoice/utils/common.py:76-95) of a chunk of bf16 logits [rows, ld] in one pass.  Columns V .. ld - 1 are neither read
  *      nor written.  dlogits (bf16 [rows, ld]) MAY be the same pointer as logits (in place); otherwise the logits are left intact.

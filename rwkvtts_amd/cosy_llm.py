@@ -18,8 +18,10 @@ from torch.nn.utils.rnn import pad_sequence
 
 from .backbone import Cache, ModelOutput, RWKV7Config, RWKV7Model
 from .hf_api import HFModelMixin
-from .losses import (EVAL_KL, SCORE_KEYS, eval_mode, fused_linear_eval, fused_linear_kl_accuracy, fused_linear_score, label_smoothing_kl,
-                     label_smoothing_kl_fused, padded_seq_start, th_accuracy)
+from .losses import (EVAL_KL, SCORE_KEYS, eval_mode, fused_linear_eval, fused_linear_kl_accuracy, fused_linear_score,
+                     fused_linear_seq_logprob, label_smoothing_kl, label_smoothing_kl_fused, padded_seq_start, scored_forward,
+                     seq_token_counts,
+                     th_accuracy)
 
 IGNORE_ID = -1  # cosyvoice/utils/common.py:24
 
@@ -123,6 +125,17 @@ def _cosy_scores(hidden, labels, lm_head, smoothing):
     return dict(zip(SCORE_KEYS, out))
 
 
+def _cosy_logprobs(hidden, labels, lm_head):
+    """sequence_logprobs of the Cosy layout from the backbone's hidden states [B, L, D] (with autograd) and the targets [B, L]:
+    _cosy_scores' rows and utterances, the plain log-softmax at the target (no smoothing).  The value is formed by the row reduction
+    of this layout's own score (EVAL_KL, which at smoothing 0 is -log p): bit for bit -score's loss_sum where lsm_weight = 0."""
+    B, L = labels.shape
+    labels = labels.to(hidden.device)
+    seq_start = padded_seq_start(B, L, hidden.device)
+    logp = fused_linear_seq_logprob(hidden, labels, lm_head.weight, lm_head.bias, IGNORE_ID, seq_start=seq_start, kind=EVAL_KL)
+    return dict(logp=logp, tokens=seq_token_counts(labels, IGNORE_ID, seq_start))
+
+
 class RWKV7CosyLM(HFModelMixin, nn.Module):
     config_class = RWKV7CosyConfig
 
@@ -216,14 +229,19 @@ class RWKV7CosyLM(HFModelMixin, nn.Module):
             return _cosy_metrics(hidden, labels, self.lm_head, self.config.lsm_weight, self.config.length_normalized_loss)
 
     def _scored_rows(self, input_ids, attention_mask, inputs_embeds, labels, max_tokens_k, kwargs):
-        """What eval_metrics and score evaluate (call inside eval_mode): the backbone's hidden states [B, L, D] and the targets [B, L]."""
+        """What eval_metrics, score (inside eval_mode) and sequence_logprobs (the current mode: forward's dropout while training)
+        evaluate: the backbone's hidden states [B, L, D] and the targets [B, L]."""
         if "batch" in kwargs:
             inputs_embeds, attention_mask, labels = self.build_inputs(kwargs["batch"])
+            if self.dropout is not None:
+                inputs_embeds = self.dropout(inputs_embeds)   # the identity in eval mode
             if max_tokens_k is not None:
                 max_bsz = max_tokens_k * 1024 // inputs_embeds.shape[1]
                 if max_bsz < inputs_embeds.shape[0]:
                     inputs_embeds, labels, attention_mask = inputs_embeds[:max_bsz], labels[:max_bsz], attention_mask[:max_bsz]
-        return self.model(input_ids=input_ids, attention_mask=attention_mask, inputs_embeds=inputs_embeds)[0], labels
+        # scored_forward: under no_grad the plain call; with autograd (sequence_logprobs) the same no_grad pass, recomputed in backward
+        return scored_forward(lambda ids, emb: self.model(input_ids=ids, attention_mask=attention_mask, inputs_embeds=emb)[0],
+                              input_ids, inputs_embeds), labels
 
     def score(self, input_ids=None, attention_mask=None, inputs_embeds=None, labels=None, max_tokens_k: Optional[int] = None, **kwargs):
         """Per-utterance scores of one batch (eval_metrics' batch kwargs, rows and targets; the backbone once, eval mode, no autograd,
@@ -233,6 +251,17 @@ class RWKV7CosyLM(HFModelMixin, nn.Module):
         with eval_mode(self):
             hidden, labels = self._scored_rows(input_ids, attention_mask, inputs_embeds, labels, max_tokens_k, kwargs)
             return _cosy_scores(hidden, labels, self.lm_head, self.config.lsm_weight)
+
+    def sequence_logprobs(self, input_ids=None, attention_mask=None, inputs_embeds=None, labels=None, max_tokens_k: Optional[int] = None,
+                          **kwargs):
+        """Per-utterance sum of log-probabilities UNDER AUTOGRAD (preference training: DataParallelTrainer.preference_step, DESIGN.md
+        section 6.5): score's batch kwargs, rows, targets and utterances, in the module's current mode and differentiable: the backbone
+        runs as score runs it and once more with autograd when backward arrives (losses.scored_forward; call .backward()).
+        Returns a dict of [B] device tensors: logp fp64 (the sum over the utterance's targets of log p(target), no label smoothing,
+        differentiable; losses.fused_linear_seq_logprob) and tokens int64.  In eval mode tokens is score's and, where lsm_weight = 0,
+        logp is bit for bit -score(...)["loss_sum"]."""
+        hidden, labels = self._scored_rows(input_ids, attention_mask, inputs_embeds, labels, max_tokens_k, kwargs)
+        return _cosy_logprobs(hidden, labels, self.lm_head)
 
     def forward_one_step(self, xs, masks, cache=None):
         """cosy_llm.py:274-286 / llm.py:146-158."""
@@ -440,3 +469,14 @@ class RWKV7LM(nn.Module):
             lm_input, attention_mask, lm_target = self.build_inputs(batch)
             hidden = self.llm.model(inputs_embeds=lm_input, attention_mask=attention_mask)[0]
             return _cosy_scores(hidden, lm_target, self.llm.lm_head, self.lsm_weight)
+
+    def sequence_logprobs(self, batch: dict):
+        """Per-utterance sum of log-probabilities under autograd (forward's argument; score's rows and targets, the current mode with
+        forward's dropout): see RWKV7CosyLM.sequence_logprobs."""
+        if not (hasattr(self.llm, "model") and hasattr(self.llm, "lm_head")):
+            raise TypeError("RWKV7LM.sequence_logprobs needs an llm with .model and .lm_head (the hidden states go to the fused head)")
+        lm_input, attention_mask, lm_target = self.build_inputs(batch)
+        if self.dropout is not None:
+            lm_input = self.dropout(lm_input)
+        hidden = scored_forward(lambda emb: self.llm.model(inputs_embeds=emb, attention_mask=attention_mask)[0], lm_input)
+        return _cosy_logprobs(hidden, lm_target, self.llm.lm_head)

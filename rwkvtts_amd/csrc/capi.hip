@@ -496,6 +496,13 @@ int rwkv7_ce_fwd_bwd_ld_bf16(long rows, int V, long ld, void *logits, const long
     if (!(label_smoothing >= 0.f && label_smoothing < 1.f)) return RWKV7_EINVAL;
     return rwkv7::ce_fwd_bwd(rows, V, ld, logits, labels, ignore_index, scale, loss_rows, label_smoothing, (hipStream_t)stream);
 }
+int rwkv7_ce_seq_bwd_bf16(long rows, int V, long ld, void *logits, const long *labels, long ignore_index, long row0, long n_seq,
+                          const long *seq_start, const float *seq_scale, float *loss_rows, rwkv7_stream_t stream) {
+    if (rows <= 0 || V <= 0 || ld < V || row0 < 0 || n_seq <= 0 ||
+        any_null({(const void *)logits, (const void *)labels, (const void *)seq_start, (const void *)seq_scale}))
+        return RWKV7_EINVAL;
+    return rwkv7::ce_seq_bwd(rows, V, ld, logits, labels, ignore_index, row0, n_seq, seq_start, seq_scale, loss_rows, (hipStream_t)stream);
+}
 // the entropy constant of the label-smoothing KL's target distribution (1 - s on the label, s / (V - 1) elsewhere), sum_j t_j ln t_j
 // with 0 ln 0 = 0 (what F.kl_div gives for a zero target)
 static float kl_entropy_const(float smoothing, int V) {

@@ -1,5 +1,6 @@
 // rwkvtts_amd/csrc/head_loss.hip -- the three kernels that walk a row of bf16 head logits [rows, ld]: the two training heads (loss and
-// d loss / d logits in one pass) and the forward-only metrics of held-out evaluation.  They share ONE row body (the anonymous namespace
+// d loss / d logits in one pass; the cross-entropy one also with a scale per SEQUENCE, rwkv7_ce_seq_bwd_bf16) and the forward-only
+// metrics of held-out evaluation.  They share ONE row body (the anonymous namespace
 // below): how a row is split, how a thread folds elements into (m, ssum, xsum[, best]), how two such partials merge, the two closing
 // loss formulas and the gradient of an element.  A kernel adds only its structure: which thread owns which element and in which order
 // the partials meet.  So head_eval_kernel's loss_rows / correct_rows are bit-identical to the training kernels' by construction.
@@ -159,8 +160,39 @@ __device__ __forceinline__ uint4 grad_piece(const uint4 r, int base, float lse, 
 // label smoothing ls: d loss / d x_j = softmax_j - ls / V - (1 - ls) [j == label].
 // ld: elements between rows (>= V; round 6: the Spark head's logits live in a buffer padded to a multiple of 256 columns, so rows are 16-byte
 // aligned and the head GEMMs see aligned leading dimensions)
+// Where a row's scale comes from is the kernel's one parameter (Scale, the two structs below): one value for the whole chunk
+// (rwkv7_ce_fwd_bwd*_bf16: loss_rows is never NULL there), or the value of the row's SEQUENCE (rwkv7_ce_seq_bwd_bf16, the backward of
+// losses.fused_linear_seq_logprob: the upstream gradient of a per-sequence sum of log-probabilities differs from sequence to sequence,
+// so it cannot be applied to the finished gradient afterwards as one scalar; loss_rows may be NULL).  Everything else is one text.
+struct UniformScale {
+    float scale;
+    __device__ __forceinline__ float operator()(long) const { return scale; }
+};
+
+// Row r of the chunk is row row0 + r of the batch; its sequence is the largest s < n_seq with seq_start[s] <= row0 + r, provided
+// row0 + r < seq_start[n_seq] (seq_start: n_seq + 1 non-decreasing offsets; equal neighbours are empty sequences, which own no row).
+// A row in front of seq_start[0] or at / behind seq_start[n_seq] gets scale 0, like an ignored row.  The search is the same for the
+// 64 lanes of a row's wave: the row index goes through readfirstlane, so the offsets arrive by scalar loads and no lane diverges.
+struct SeqScale {
+    long row0, n_seq;
+    const long *seq_start;
+    const float *seq_scale;
+    __device__ __forceinline__ float operator()(long row) const {
+        const long g = row0 + row;
+        const long gu = ((long)__builtin_amdgcn_readfirstlane((int)(g >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)g);
+        if (gu >= seq_start[n_seq]) return 0.f;
+        long lo = 0, hi = n_seq;   // lo ends as the number of s < n_seq with seq_start[s] <= gu
+        while (lo < hi) {
+            const long mid = (lo + hi) >> 1;
+            if (seq_start[mid] <= gu) lo = mid + 1; else hi = mid;
+        }
+        return lo > 0 ? seq_scale[lo - 1] : 0.f;
+    }
+};
+
+template <typename Scale>
 __global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(long rows, int V, long ld, bf16_t *__restrict__ logits, const long *__restrict__ labels,
-                                                         long ignore_index, float scale, float *__restrict__ loss_rows, float ls) {
+                                                         long ignore_index, Scale scale_of, float *__restrict__ loss_rows, float ls) {
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -176,8 +208,8 @@ __global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(long rows, int V, long 
     for (int i = lane; i < sp.nv; i += 64) acc_piece(acc, xv[i], sp.head + 8 * i);
     acc_butterfly(acc);
     const float lse = acc_lse(acc);
-    if (lane == 0) loss_rows[row] = valid ? ce_row_loss(lse, acc.xsum, bf2f(x[lab < 0 ? 0 : lab]), V, ls) : 0.f;
-    const float sc = valid ? scale : 0.f, hit = 1.f - ls, off_all = ls / (float)V;
+    if (lane == 0 && loss_rows) loss_rows[row] = valid ? ce_row_loss(lse, acc.xsum, bf2f(x[lab < 0 ? 0 : lab]), V, ls) : 0.f;
+    const float sc = valid ? scale_of(row) : 0.f, hit = 1.f - ls, off_all = ls / (float)V;
     const int labi = (int)lab;   // an ignored row's gradient is 0 whatever this matches
     auto minus_target = [&](float p, int j) { return p - off_all - (j == labi ? hit : 0.f); };
     if (lane < sp.head) x[lane] = grad_one(bf2f(x[lane]), lane, lse, sc, minus_target);
@@ -189,8 +221,16 @@ __global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(long rows, int V, long 
 int ce_fwd_bwd(long rows, int V, long ld, void *logits, const long *labels, long ignore_index, float scale, float *loss_rows,
                float label_smoothing, hipStream_t st) {
     (void)hipGetLastError();
-    hipLaunchKernelGGL(ce_fwd_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, rows, V, ld, (bf16_t *)logits, labels,
-                       ignore_index, scale, loss_rows, label_smoothing);
+    hipLaunchKernelGGL(ce_fwd_bwd_kernel<UniformScale>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, rows, V, ld, (bf16_t *)logits,
+                       labels, ignore_index, UniformScale{scale}, loss_rows, label_smoothing);
+    return (int)hipGetLastError();
+}
+
+int ce_seq_bwd(long rows, int V, long ld, void *logits, const long *labels, long ignore_index, long row0, long n_seq,
+               const long *seq_start, const float *seq_scale, float *loss_rows, hipStream_t st) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(ce_fwd_bwd_kernel<SeqScale>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, rows, V, ld, (bf16_t *)logits,
+                       labels, ignore_index, SeqScale{row0, n_seq, seq_start, seq_scale}, loss_rows, 0.f);
     return (int)hipGetLastError();
 }
 

@@ -121,9 +121,11 @@ int cache_rows_commit_bf16(int layers, int n, const void *const *src_tbl, void *
                            int D, int H, hipStream_t stream);
 
 // ---- loss heads and per-sequence scores (head_loss.hip, seq_scores.hip).  C: the entropy constant of the smoothed target
-//      distribution; argmax_rows may be NULL
+//      distribution; argmax_rows, and ce_seq_bwd's loss_rows, may be NULL
 int ce_fwd_bwd(long rows, int V, long ld, void *logits, const long *labels, long ignore_index, float scale, float *loss_rows,
                float label_smoothing, hipStream_t stream);
+int ce_seq_bwd(long rows, int V, long ld, void *logits, const long *labels, long ignore_index, long row0, long n_seq,
+               const long *seq_start, const float *seq_scale, float *loss_rows, hipStream_t stream);
 int kl_acc_fwd_bwd(long rows, int V, long ld, const void *logits, void *dlogits, const long *labels, long ignore_index, float smoothing,
                    float C, float scale, float *loss_rows, int *correct_rows, hipStream_t stream);
 int head_eval(long rows, int V, long ld, const void *logits, const long *labels, long ignore_index, int kind, float smoothing, float C,

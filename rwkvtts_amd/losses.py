@@ -13,6 +13,8 @@ fused_linear_eval          : forward-only loss sum / valid count / correct count
 fused_linear_score         : the same rows reduced per SEQUENCE instead of per batch (loss sum, tokens, correct, worst token): the
     per-row outputs of rwkv7_head_eval_bf16 kept for the whole batch, then one rwkv7_seq_scores_f32 launch (the heads' score,
     DataParallelTrainer.score).
+fused_linear_seq_logprob   : that loss sum, negated, UNDER AUTOGRAD with an upstream gradient per sequence (the heads' sequence_logprobs,
+    DataParallelTrainer.preference_step): backward runs the head GEMM again chunk by chunk and rwkv7_ce_seq_bwd_bf16 on each chunk.
 """
 import contextlib
 import math
@@ -349,6 +351,20 @@ def eval_mode(module):
         module.train(was_training)
 
 
+def scored_forward(fn, *tensors):
+    """fn(*tensors) as the scores see it, differentiable all the same: the pass runs under no_grad now -- the kernels, and so the bits,
+    of eval_metrics / score, whose backbone chooses other (fused training) nodes when autograd is on -- and once more with autograd
+    when backward arrives (torch.utils.checkpoint in its re-entrant form: the host and device random streams of the first pass are
+    replayed for the second and put back afterwards).  The price is one more forward pass of fn.  Gradients reach fn's parameters and
+    the tensors given here through .backward() only (torch.autograd.grad on the result is not supported by that form).  Without
+    autograd it is fn(*tensors)."""
+    if not torch.is_grad_enabled():
+        return fn(*tensors)
+    from torch.utils.checkpoint import checkpoint
+    tape = torch.zeros((), requires_grad=True)   # puts the node on the tape even if no tensor of the batch requires a gradient
+    return checkpoint(lambda _tape, *t: fn(*t), tape, *tensors, use_reentrant=True)
+
+
 def _eval_rows_torch(logits, labels, ignore_index, kind, smoothing):
     """The two row formulas of rwkv7_head_eval_bf16 in torch, fp32 from the logits as given: (loss_rows fp32, correct_rows bool)."""
     x = logits.float()
@@ -370,6 +386,20 @@ def _eval_rows_torch(logits, labels, ignore_index, kind, smoothing):
     return per.masked_fill(~valid, 0.0), correct
 
 
+def _chunk_plan(N, V, esize, hip, chunk, align=1, overlap_last=False):
+    """(rows per chunk, first row of every chunk) of _eval_chunks' walk over N rows (see there)."""
+    if chunk is None:
+        # torch route: fp32 logits and one fp32 temporary of that size
+        chunk = EVAL_CHUNK_ROWS or auto_chunk(N, V, esize if hip else 8)
+    if hip:
+        chunk = -(-max(1, chunk) // align) * align
+    chunk = max(1, min(chunk, N))
+    starts = list(range(0, N, chunk))
+    if hip and overlap_last:
+        starts[-1] = N - chunk   # N rows when one chunk holds them all
+    return chunk, starts
+
+
 def _eval_chunks(hidden, labels, weight, bias, ignore_index, kind, smoothing, chunk, *, align=1, overlap_last=False, out=None):
     """The forward-only chunk walk under fused_linear_eval and _score_rows: yields (hip, loss_rows fp32 [rows], correct_rows [rows]) of
     F.linear(hidden, weight, bias) for one chunk of rows after the other; hip: which route the call takes.
@@ -385,13 +415,7 @@ def _eval_chunks(hidden, labels, weight, bias, ignore_index, kind, smoothing, ch
     h2, lab = hidden.reshape(-1, D), labels.reshape(-1)
     N, dev = h2.shape[0], h2.device
     hip = _hip_gate(h2, lab, weight, bias)
-    if chunk is None:
-        # torch route: fp32 logits and one fp32 temporary of that size
-        chunk = EVAL_CHUNK_ROWS or auto_chunk(N, V, h2.element_size() if hip else 8)
-    if hip:
-        chunk = -(-max(1, chunk) // align) * align
-    chunk = max(1, min(chunk, N))
-    starts = list(range(0, N, chunk))
+    chunk, starts = _chunk_plan(N, V, h2.element_size(), hip, chunk, align, overlap_last)
     whole = out is not None
     if hip:
         _check_labels(lab, V, ignore_index)
@@ -401,8 +425,6 @@ def _eval_chunks(hidden, labels, weight, bias, ignore_index, kind, smoothing, ch
             out = (torch.empty(chunk, dtype=torch.float32, device=dev), torch.empty(chunk, dtype=torch.int32, device=dev))
         lab = lab.contiguous()
         wt = weight.t()
-        if overlap_last:
-            starts[-1] = N - chunk   # N rows when one chunk holds them all
     for s in starts:
         h, lb = h2[s:s + chunk], lab[s:s + chunk]
         rows = h.shape[0]
@@ -511,11 +533,17 @@ def fused_linear_score(hidden, labels, weight, bias, ignore_index, kind, smoothi
     call -- observed from 16 rows per call on, not promised by the library."""
     if seq_start is None or seq_start.dim() != 1 or seq_start.numel() < 2:
         raise ValueError("fused_linear_score: seq_start must be a 1-D tensor of n_seq + 1 >= 2 row offsets")
+    return _seq_scores(hidden, labels, weight, bias, ignore_index, kind, smoothing, seq_start, chunk)[0]
+
+
+def _seq_scores(hidden, labels, weight, bias, ignore_index, kind, smoothing, seq_start, chunk):
+    """fused_linear_score's body: (its five outputs, labels int64 [N] contiguous, seq_start as used -- int64 on the device, clamped
+    to [0, N] -- and hip: which route the call took)."""
     loss_rows, correct_rows, lab, hip = _score_rows(hidden, labels, weight, bias, ignore_index, kind, smoothing, chunk)
     N, dev = lab.numel(), lab.device
     st = seq_start.to(device=dev, dtype=torch.int64).clamp(0, N).contiguous()   # the kernel checks no range: keep every read inside
     if not hip:
-        return _seq_scores_torch(st, loss_rows, correct_rows, lab, ignore_index)
+        return _seq_scores_torch(st, loss_rows, correct_rows, lab, ignore_index), lab, st, hip
     n_seq = st.numel() - 1
     loss_sum = torch.empty(n_seq, dtype=torch.float64, device=dev)
     tokens, correct, worst_row = (torch.empty(n_seq, dtype=torch.int64, device=dev) for _ in range(3))
@@ -523,9 +551,115 @@ def fused_linear_score(hidden, labels, weight, bias, ignore_index, kind, smoothi
     _lib.call("rwkv7_seq_scores_f32", loss_rows, n_seq, st, loss_rows, correct_rows, lab, ignore_index, loss_sum, tokens, correct,
               worst_loss, worst_row)
     SCORE_HITS[0] += 1
-    return loss_sum, tokens, correct, worst_loss, worst_row
+    return (loss_sum, tokens, correct, worst_loss, worst_row), lab, st, hip
 
 
 def padded_seq_start(B, T, device):
     """seq_start of a padded [B, T] batch flattened row-major: sequence b is the rows b T .. (b + 1) T - 1."""
     return torch.arange(B + 1, dtype=torch.int64, device=device) * T
+
+
+# ---- per-sequence log-probabilities under autograd (DESIGN.md section 6.5) ---------------------------------------------------------
+SEQLP_HITS = [0]   # launches of rwkv7_ce_seq_bwd_bf16 (one per chunk of a backward pass): how a test sees which route a call took
+
+
+def _row_scales(seq_start, seq_scale, row0, rows):
+    """rwkv7_ce_seq_bwd_bf16's lookup in torch, on the device: fp32 [rows], seq_scale of the sequence of rows row0 .. row0 + rows - 1
+    (the largest s with seq_start[s] <= row), 0 for a row in front of seq_start[0] or at / behind seq_start[-1]."""
+    r = torch.arange(row0, row0 + rows, dtype=torch.int64, device=seq_start.device)
+    s = torch.searchsorted(seq_start, r, right=True) - 1   # the largest index (of n_seq + 1 offsets) with seq_start[s] <= row
+    inside = (s >= 0) & (r < seq_start[-1])
+    return torch.where(inside, seq_scale[s.clamp(0, seq_scale.numel() - 1)], torch.zeros_like(seq_scale[:1]))
+
+
+class _FusedLinearSeqLogprob(torch.autograd.Function):
+    """Forward: fused_linear_score's loss_sum, negated (no logits kept: hidden, labels and seq_start are what backward needs beside
+    the head's own parameters).  Backward: the head GEMM once more, chunk by chunk along the forward's walk, each chunk's logits
+    turned in place into (softmax - onehot) * (-g[sequence of the row]) and fed to the three gradient GEMMs."""
+
+    @staticmethod
+    def forward(ctx, hidden, weight, bias, labels, seq_start, ignore_index, kind, chunk):
+        (loss_sum, *_), lab, st, hip = _seq_scores(hidden, labels, weight, bias, ignore_index, kind, 0.0, seq_start, chunk)
+        ctx.save_for_backward(hidden, weight, bias, lab, st)
+        ctx.hip, ctx.ignore_index, ctx.chunk = hip, ignore_index, chunk
+        return -loss_sum
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        hidden, weight, bias, lab, st = ctx.saved_tensors
+        need, hip, ignore_index = ctx.needs_input_grad, ctx.hip, ctx.ignore_index
+        (N, D), V, dev = hidden.shape, weight.shape[0], hidden.device
+        n_seq = st.numel() - 1
+        seq_scale = (-g).float().contiguous()   # d(-loss_sum[s]) / d(row loss) = -1: the kernel's gradient is the loss's
+        dh = torch.empty_like(hidden) if need[0] else None
+        dw = torch.zeros_like(weight, dtype=torch.float32) if need[1] else None
+        db = torch.zeros_like(bias, dtype=torch.float32) if (bias is not None and need[2]) else None
+        chunk, starts = _chunk_plan(N, V, hidden.element_size(), hip, ctx.chunk, SCORE_CHUNK_ALIGN, True)
+        if hip:
+            ld = -(-V // 8) * 8
+            buf = torch.empty(chunk, ld, dtype=hidden.dtype, device=dev)
+            wt = weight.t()
+        done = 0   # rows [0, done) have their gradients: an overlapping last chunk contributes its remaining rows only
+        for s in starts:
+            h = hidden[s:s + chunk]
+            rows, skip = h.shape[0], done - s
+            if hip:
+                logits = buf[:rows, :V]
+                if bias is None:
+                    torch.mm(h, wt, out=logits)
+                else:
+                    torch.addmm(bias, h, wt, out=logits)
+                _lib.call("rwkv7_ce_seq_bwd_bf16", buf, rows - skip, V, ld, buf[skip:], lab[done:], ignore_index, done, n_seq, st,
+                          seq_scale, None)
+                SEQLP_HITS[0] += 1
+                pd = logits[skip:]
+                col = pd.sum(0, dtype=torch.float32) if db is not None else None
+            else:
+                x = F.linear(h, weight, bias).float()
+                lb = lab[s:s + rows]
+                p = torch.softmax(x, dim=1)
+                p.scatter_add_(1, lb.clamp(min=0).unsqueeze(1), torch.full_like(p[:, :1], -1.0))
+                p = p * (_row_scales(st, seq_scale, s, rows) * (lb != ignore_index)).unsqueeze(1)
+                pd = p.to(hidden.dtype)
+                col = p.sum(0) if db is not None else None
+            h = h[skip:]
+            if need[0]:
+                dh[done:s + rows] = pd @ weight
+            if need[1]:
+                dw += (pd.t() @ h).float()
+            if db is not None:
+                db += col
+            done = s + rows
+        return (dh, dw.to(weight.dtype) if dw is not None else None, db.to(bias.dtype) if db is not None else None,
+                None, None, None, None, None)
+
+
+def seq_token_counts(labels, ignore_index, seq_start):
+    """int64 [n_seq] on the labels' device: the number of labels != ignore_index among each sequence's rows (fused_linear_score's
+    `tokens`, from a running count of the flattened labels: no host read)."""
+    lab = labels.reshape(-1)
+    st = seq_start.to(device=lab.device, dtype=torch.int64).clamp(0, lab.numel())
+    run = torch.cat((torch.zeros(1, dtype=torch.int64, device=lab.device), (lab != ignore_index).cumsum(0)))
+    return (run[st[1:]] - run[st[:-1]]).clamp(min=0)   # a decreasing pair is an empty sequence
+
+
+def fused_linear_seq_logprob(hidden, labels, weight, bias, ignore_index, *, seq_start, chunk=None, kind=EVAL_CE):
+    """Per-sequence sum of log-probabilities of a head under autograd: hidden [..., D], labels [...] (N rows once flattened), seq_start
+    as in fused_linear_score -> fp64 [n_seq], sum over the sequence's rows with label != ignore_index of log softmax(F.linear(hidden,
+    weight, bias))[label]; differentiable with respect to hidden, weight and bias, with any upstream gradient per sequence (fp64 or
+    fp32 [n_seq]).
+    Forward: fused_linear_score's loss_sum with smoothing 0, negated -- the same rows, route, chunk walk and launches, so on either
+    route the value is bit for bit -fused_linear_score(..., kind, 0.0)[0].  kind: whose row reduction forms the value, EVAL_CE (the
+    cross-entropy kernels') or EVAL_KL (the Cosy KL kernel's, which at smoothing 0 is the same -log p in another summation order:
+    the Cosy heads pass it so that their value is their own score's).  Nothing of size [N, V] is kept for backward.
+    Backward, bf16 CUDA hidden / weight / bias with int64 labels: per chunk of the forward's walk the head GEMM into one reused
+    [chunk, ld] bf16 buffer, rwkv7_ce_seq_bwd_bf16 on it in place (the scale -g[s] of the row's sequence applied in fp32 before the
+    one bf16 rounding; seq_start and the scales stay on the device: no host synchronisation), then dh = pd W, dW += (pd^T h).float(),
+    db += column sums.  An overlapping last chunk contributes only the rows its predecessor did not cover.  Gradients are NOT
+    bit-identical across chunk sizes (dW's fp32 sum over chunks).  Anything else: the same definitions from fp32 logits per chunk
+    in torch."""
+    if seq_start is None or seq_start.dim() != 1 or seq_start.numel() < 2:
+        raise ValueError("fused_linear_seq_logprob: seq_start must be a 1-D tensor of n_seq + 1 >= 2 row offsets")
+    D = hidden.shape[-1]
+    return _FusedLinearSeqLogprob.apply(hidden.reshape(-1, D), weight, bias, labels.reshape(-1), seq_start, ignore_index, kind, chunk)

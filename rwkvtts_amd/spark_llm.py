@@ -21,7 +21,8 @@ import torch.nn.functional as F
 from .backbone import Cache, Linear, ModelOutput, RWKV7Config, RWKV7Model
 from .hf_api import HFModelMixin
 from .losses import (EVAL_CE, SCORE_KEYS, eval_mode, fused_linear_cross_entropy, fused_linear_eval, fused_linear_score,
-                     padded_seq_start)
+                     fused_linear_seq_logprob, padded_seq_start, scored_forward,
+                     seq_token_counts)
 
 
 class RWKV7SpeechConfig(RWKV7Config):
@@ -122,11 +123,16 @@ class RWKV7ForSpeech(HFModelMixin, nn.Module):
         return dict(loss=(loss_sum / tokens).float().reshape(()), loss_sum=loss_sum, tokens=tokens, correct=correct, denom=tokens)
 
     def _scored_rows(self, input_ids, attention_mask, inputs_embeds, labels, kwargs):
-        """What eval_metrics and score evaluate (call inside eval_mode): the backbone's hidden states, forward's shifted labels, the
-        ignore index and cu_seqlens (None for a padded batch)."""
+        """What eval_metrics, score (inside eval_mode) and sequence_logprobs (the current mode: forward's dropout on inputs_embeds
+        while training) evaluate: the backbone's hidden states, forward's shifted labels, the ignore index and cu_seqlens (None for a
+        padded batch)."""
         for k in ("past_key_values", "use_cache", "output_attentions", "output_hidden_states", "return_dict", "logits_to_keep"):
             kwargs.pop(k, None)
-        hidden = self.model(input_ids=input_ids, attention_mask=attention_mask, inputs_embeds=inputs_embeds, **kwargs)[0]
+        if self.training and inputs_embeds is not None:
+            inputs_embeds = self.dropout(inputs_embeds)
+        # scored_forward: under no_grad the plain call; with autograd (sequence_logprobs) the same no_grad pass, recomputed in backward
+        hidden = scored_forward(lambda ids, emb: self.model(input_ids=ids, attention_mask=attention_mask, inputs_embeds=emb, **kwargs)[0],
+                                input_ids, inputs_embeds)
         ignore_index = getattr(self.criterion, "ignore_index", -100)
         labels = labels.to(hidden.device)
         labels = torch.cat((labels[..., 1:], torch.full_like(labels[:, :1], ignore_index)), 1)
@@ -147,15 +153,32 @@ class RWKV7ForSpeech(HFModelMixin, nn.Module):
         form one more (possibly empty) utterance at the end.  Summed over the utterances, tokens and correct equal eval_metrics'."""
         with eval_mode(self):
             hidden, labels, ignore_index, cu = self._scored_rows(input_ids, attention_mask, inputs_embeds, labels, kwargs)
-            B, T = labels.shape
-            if cu is None:
-                seq_start = padded_seq_start(B, T, hidden.device)
-            else:
-                seq_start = cu.to(device=hidden.device, dtype=torch.int64)
-                if getattr(self.config, "strict_reference_loss", False):
-                    seq_start = torch.cat((seq_start, torch.full_like(seq_start[:1], B * T)))
+            seq_start = self._utterance_rows(labels, cu, hidden.device)
             out = fused_linear_score(hidden, labels, self.lm_head.weight, self.lm_head.bias, ignore_index, EVAL_CE, seq_start=seq_start)
         return dict(zip(SCORE_KEYS, out))
+
+    def _utterance_rows(self, labels, cu, device):
+        """seq_start of score and sequence_logprobs: the utterances' first rows in the flattened [B * T] rows (see score)."""
+        B, T = labels.shape
+        if cu is None:
+            return padded_seq_start(B, T, device)
+        seq_start = cu.to(device=device, dtype=torch.int64)
+        if getattr(self.config, "strict_reference_loss", False):
+            seq_start = torch.cat((seq_start, torch.full_like(seq_start[:1], B * T)))
+        return seq_start
+
+    def sequence_logprobs(self, input_ids=None, attention_mask=None, inputs_embeds=None, labels=None, **kwargs):
+        """Per-utterance sum of log-probabilities UNDER AUTOGRAD (preference training: DataParallelTrainer.preference_step, DESIGN.md
+        section 6.5): score's batch kwargs, rows, shifted labels and utterances, but in the module's current mode (training mode:
+        forward's dropout on inputs_embeds is live) and differentiable: the backbone runs as score runs it and once more with
+        autograd when backward arrives (losses.scored_forward; call .backward(), not torch.autograd.grad).  Returns a dict of [utterances] device tensors:
+        logp fp64 (the sum over the utterance's valid positions of log p(label), differentiable: losses.fused_linear_seq_logprob, the
+        [B, T, V] logits never exist) and tokens int64 (the number of those positions).  In eval mode logp is bit for bit
+        -score(...)["loss_sum"] and tokens is score's."""
+        hidden, labels, ignore_index, cu = self._scored_rows(input_ids, attention_mask, inputs_embeds, labels, kwargs)
+        seq_start = self._utterance_rows(labels, cu, hidden.device)
+        logp = fused_linear_seq_logprob(hidden, labels, self.lm_head.weight, self.lm_head.bias, ignore_index, seq_start=seq_start)
+        return dict(logp=logp, tokens=seq_token_counts(labels, ignore_index, seq_start))
 
     def prepare_inputs_for_generation(self, input_ids=None, past_key_values=None, attention_mask=None,
                                       inputs_embeds=None, use_cache=True, logits_to_keep=None, **kwargs):

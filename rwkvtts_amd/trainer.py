@@ -777,15 +777,20 @@ class DataParallelTrainer:
         gradients (rwkv7_grad_fold_bf16, mean over k, one rounding to bf16) right before it goes on the wire, so the exchange still
         overlaps this backward pass; the NaN flag that is all-reduced is the max over the k micro-batches.  Without a preceding
         accumulate() nothing of that runs."""
+        return self._step_on(lambda: (self.model(**batch).loss, None))
+
+    def _step_on(self, loss_fn):
+        """The body of step() for any scalar loss: loss_fn() runs the forward pass (after the gradient hooks are armed) and returns
+        (loss, bad), bad: None, or a device bool that raises the NaN flag besides a non-finite loss.  Returns the detached loss."""
         k = self._acc_count + 1
         if k > 1:
             self.reducer.pre_exchange = lambda s_, e_: self._fold(s_, e_, 1.0 / k)
         self.flat.arm()
-        out = self.model(**batch)
-        loss = out.loss
+        loss, bad = loss_fn()
         flag_work = None
         if self.nan_guard:
-            self.nan_flag.copy_((~torch.isfinite(loss.detach())).reshape(1))
+            nonfinite = ~torch.isfinite(loss.detach())
+            self.nan_flag.copy_((nonfinite if bad is None else nonfinite | bad).reshape(1))
             if k > 1:
                 torch.maximum(self.nan_flag, self._acc_flag, out=self.nan_flag)
             if self.world > 1:
@@ -836,6 +841,43 @@ class DataParallelTrainer:
             m._mix_key = None
         self.step_idx += 1
         return loss.detach()
+
+    def preference_step(self, *, beta, ref_logps=None, sft_weight=0.0, **batch):
+        """One optimisation step of direct preference optimisation on this rank's 2P utterances: utterance 2i
+        is the chosen and 2i + 1 the rejected candidate of pair i.  ref_logps: [2P] (tensor or numpy), the frozen reference's sum of
+        log-probabilities per utterance, i.e. -score([batch])["loss_sum"] taken before tuning; None: zeros.  With pi the policy's
+        model.sequence_logprobs(**batch)["logp"] (the module's current mode; the backbone forward runs twice, see there):
+            margin_i = beta ((pi_c - pi_r) - (ref_c - ref_r)),
+            loss = mean_i softplus(-margin_i) + sft_weight (-sum_i pi_c,i / sum_i tokens_c,i),
+        in fp64 on the device.  The loss then takes exactly step()'s path (_step_on): armed hooks, the on-device NaN flag (raised by a
+        non-finite loss or a non-finite ref_logps entry: a zero-gradient step on every rank), the bucketed exchange, clipping, the
+        AdamW launches, reattach, step_idx.  No host read.  Not allowed inside an accumulation window.  Returns device tensors: loss,
+        margin (mean), accuracy (share of pairs with margin > 0), logp_chosen [P], logp_rejected [P] (all detached)."""
+        if self._acc_count != 0:
+            raise RuntimeError(f"preference_step inside an accumulation window ({self._acc_count} micro-batches pending): "
+                               "call step() first")
+        out = {}
+
+        def loss_fn():
+            seq = self.model.sequence_logprobs(**batch)
+            logp, tokens = seq["logp"], seq["tokens"]
+            ref = torch.zeros_like(logp) if ref_logps is None else \
+                torch.as_tensor(ref_logps).to(device=logp.device, dtype=logp.dtype).reshape(-1)
+            if logp.numel() % 2 != 0 or logp.numel() == 0 or ref.numel() != logp.numel():
+                self.flat.reattach()   # nothing ran backward: the hooks are disarmed again
+                raise ValueError(f"preference_step needs chosen/rejected pairs and one ref_logps entry each: {logp.numel()} "
+                                 f"utterances, {ref.numel()} reference values")
+            pc, pr = logp[0::2], logp[1::2]
+            margin = float(beta) * ((pc - pr) - (ref[0::2] - ref[1::2]))
+            loss = torch.nn.functional.softplus(-margin).mean()
+            if sft_weight:
+                loss = loss - float(sft_weight) * (pc.sum() / tokens[0::2].sum().clamp(min=1))
+            m = margin.detach()
+            out.update(margin=m.mean(), accuracy=(m > 0).double().mean(), logp_chosen=pc.detach(), logp_rejected=pr.detach())
+            return loss, ~torch.isfinite(ref).all()
+
+        out["loss"] = self._step_on(loss_fn)
+        return {k: out[k] for k in ("loss", "margin", "accuracy", "logp_chosen", "logp_rejected")}
 
     def evaluate(self, batches):
         """Held-out evaluation.  batches: an iterable of batch dicts, this rank's shard (at least one batch on
