@@ -1,10 +1,9 @@
-"""Fixed inputs and calls for pinning the closed-batch token draws of csrc/sampling.hip (rwkv7_sample_rows_f32,
-rwkv7_sample_rows_tail_f32, rwkv7_ras_step_f32) bit for bit (test infrastructure).  The per-slot kernels are required to equal these
-entries (tests/test_continuous*_gpu.py), so once the draw bodies are shared only a record of these ids can see a change in a shared
-body.  The inputs are built on the CPU from seeded generators (the same on every machine); only results are meant to be stored.
-
-tools/pin_draw_ids.py records `run_groups()` into tests/golden/draw_ids.npz and compares a later run against it.  No record has
-been written yet."""
+"""Fixed inputs and calls for the token draws of csrc/sampling.hip (rwkv7_sample_rows_f32, rwkv7_sample_rows_tail_f32,
+rwkv7_ras_step_f32) and their per-slot forms (test infrastructure).  The inputs are built on the CPU from seeded generators (the same
+on every machine).  Their ids are pinned by the host replay of the draw (tests/draw_replay.py), which predicts every id from Philox
+and a float64 chain, not by a recorded file: tests/test_draw_replay.py shows on the CPU that the replay is the law and that every
+case below leaves at most 3 % of its draws ambiguous, tests/test_draw_replay_gpu.py runs the cases (run_groups() included) on the
+device and compares id for id."""
 import numpy as np
 import torch
 
@@ -66,11 +65,11 @@ def row_cases(n):
     return [(f"rows{n}/{name}", lg, kw, tail) for name, lg, kw, tail in cases]
 
 
-def segment_cases():
+def segment_cases(rows=ROWS):
     """four unequal segments with allowed ranges (lo > 0 on segment 0): the Philox counter holds the workgroup index"""
     sizes, allow = [97, 1281, 33, 700], [(10, 90), (0, 1281), (0, 33), (100, 400)]
     g = torch.Generator().manual_seed(77)
-    lg = torch.randn(ROWS, sum(sizes) + 5, generator=g) * 2.0
+    lg = torch.randn(rows, sum(sizes) + 5, generator=g) * 2.0
     modes = (("greedy", dict()), ("multinomial", dict(do_sample=True, temperature=0.6)),
              ("k7_p0.9", dict(do_sample=True, top_k=7, top_p=0.9, temperature=1.37)), ("k64_p0.5", dict(do_sample=True, top_k=64, top_p=0.5)))
     return [(f"nseg4/{name}", lg, dict(seg_len=sizes, allow=allow, suppress=[12, 5], seed=SEED_HI, **kw), None) for name, kw in modes]
@@ -111,7 +110,7 @@ def ras_cases(V):
     cases = []
     for win in (10, 128):
         g = torch.Generator().manual_seed(3000 + V + win)
-        base = torch.randn(V, generator=g) * 1.5
+        base = torch.randn(V, generator=g) * 5.0    # (a spread at which under 3 % of the whole-row draws fall within the fp32 margin)
         ring = torch.randint(0, V - 1, (win,), generator=g)
         ptr = 3 if win == 10 else 70
         lg = base.clone()
@@ -161,3 +160,103 @@ def run_groups(dev):
     for run in groups().values():
         res.update(run(dev))
     return res
+
+
+# ---- cases whose every id the host replay predicts (tests/test_draw_replay.py, tests/test_draw_replay_gpu.py) -------------------
+# both sides of each elements-per-thread class boundary (1280 | 1281, 8448 | 8449), a small range and the largest one
+CLOSED_SIZES = (97, 1280, 1281, 8448, 8449, 15360)
+CLOSED_ROWS = 1024
+BIG_STEP = 2 ** 32 + 3
+RAS_SEEDS = (SEED_LO, SEED_HI, 77)
+RAS_LONG = 64
+
+
+def closed_launches(seed):
+    """(seed, step) of the launches of one closed-batch case; DIFFER: pairs of launches that differ only in the high word of the
+    step (BIG_STEP | 3) or of the seed (bit 63) and must not draw the same ids"""
+    return [(seed, 0), (seed, 5), (seed, BIG_STEP), (seed, 3), (seed ^ (1 << 63), 5)]
+
+
+DIFFER = ((2, 3), (1, 4))
+_closed = {}
+
+
+def closed_logits(n):
+    """CLOSED_ROWS different rows for an allowed range of n ids (shared by every mode, never written).  The spread (3.0) keeps
+    the whole-row CDF steps of the multinomial mode far enough apart that under 3 % of its draws fall within the fp32 margin."""
+    if n not in _closed:
+        _closed[n] = torch.randn(CLOSED_ROWS, n + 3, generator=torch.Generator().manual_seed(5000 + n)) * 3.0
+    return _closed[n]
+
+
+def closed_cases(n):
+    """[(name, logits, replay / RowSampler keywords, launches)]"""
+    return [(f"closed{n}/{name}", closed_logits(n), dict(seg_len=[n], **kw), closed_launches(seed)) for name, kw, seed in _modes()]
+
+
+def selection_cases():
+    """rows that leave the one-pass selection or have no candidate at all, with the id of every draw asserted
+    [(name, logits, keywords, launches)]"""
+    g = torch.Generator().manual_seed(91)
+    L = [(SEED_LO, 0), (SEED_HI, 7)]
+    out = []
+    R, n = 256, 8449                                  # clustered: one far outlier, the rest within 1e-2 (the radix select)
+    lg = torch.randn(R, n, generator=g) * 1e-2 + 10.0
+    lg[torch.arange(R), torch.randint(0, n, (R,), generator=g)] = -1000.0
+    out.append(("clustered", lg, dict(seg_len=[n], do_sample=True, top_k=20, top_p=0.9, temperature=0.01), L))
+    R, n = 64, 1000                                   # constant rows; three leaders and 200 ids tied at the k-th value (k = 5)
+    lg = torch.full((R, n), 3.0)
+    for r in range(32, R):
+        lg[r] = torch.randn(n, generator=g)
+        tied = torch.randperm(n, generator=g)[:203]
+        lg[r, tied[3:]] = 6.0
+        lg[r, tied[:3]] = torch.tensor([9.0, 8.0, 7.0])
+    out.append(("constant_and_200_tied", lg, dict(seg_len=[n], do_sample=True, top_k=5), L))
+    R, n = 256, 1281                                  # three more ids equal to the 7th largest value of a random row
+    lg = torch.randn(R, n, generator=g) * 2.0
+    kth = lg.topk(7, 1).values[:, -1]
+    for r in range(R):
+        lg[r, torch.randperm(n, generator=g)[:3]] = kth[r]
+    out.append(("ties_at_kth", lg, dict(seg_len=[n], do_sample=True, top_k=7, top_p=0.9, temperature=0.6), L))
+    half = torch.randn(R, n, generator=g) * 3.0      # half of every row is -inf
+    half[:, ::2] = float("-inf")
+    out.append(("half_inf_k7", half, dict(seg_len=[n], do_sample=True, top_k=7, top_p=0.9), L))
+    out.append(("half_inf_multinomial", half, dict(seg_len=[n], do_sample=True), L))
+    R, n = 64, 97                                     # five finite ids per row, top_k = 64; rows 0..7 hold nothing but -inf
+    few = torch.full((R, n), float("-inf"))
+    for r in range(8, R):
+        few[r, torch.randperm(n, generator=g)[:5]] = torch.randn(5, generator=g) * 2.0
+    for name, kw in (("greedy", dict()), ("k64", dict(do_sample=True, top_k=64, top_p=0.9)), ("multinomial", dict(do_sample=True))):
+        out.append(("few_finite_" + name, few, dict(seg_len=[n], allow=[(10, 90)], **kw), L))
+    lg = torch.randn(R, n, generator=g)               # suppression and the min-EOS bar cover the whole allowed range
+    for name, kw in (("greedy", dict()), ("k7", dict(do_sample=True, top_k=7)), ("multinomial", dict(do_sample=True))):
+        out.append(("all_dropped_" + name, lg, dict(seg_len=[n], allow=[(10, 13)], suppress=[10, 11], min_eos=(12, 100), **kw), L))
+    return out
+
+
+def slot_case():
+    """rwkv7_sample_slots_f32 with heterogeneous slots: (logits [rows, V + 3], row -> slot (one entry names no slot), per-slot
+    parameter dicts, suppressed ids, EOS id).  Slot 5 is dead; sampled slots with top_k = 0 and greedy slots occur."""
+    import random
+    S, V = 24, 1281
+    E = V - 2
+    rng = random.Random(17)
+    g = torch.Generator().manual_seed(321)
+    P = []
+    for s in range(S):
+        do_sample = s % 4 != 0
+        top_k = rng.choice([0, 1, 7, 64]) if do_sample else 0
+        step = rng.choice([0, 3, BIG_STEP])
+        P.append(dict(do_sample=do_sample, top_k=top_k, top_p=rng.choice([1.0, 0.9, 0.5]) if top_k else 1.0,
+                      temperature=rng.choice([0.6, 1.0, 1.37]), seed=rng.getrandbits(64) | ((s % 2) << 63), step=step,
+                      min_until=step + (s % 3 == 0), limit=step + 5, live=s != 5))
+    perm = torch.randperm(S, generator=g).tolist()
+    rows = perm[:10] + [S + 3] + perm[10:]
+    lg = torch.randn(len(rows), V + 3, generator=g) * 3.0
+    lg[::3, E] = 30.0                                   # EOS leads a third of the rows; barred in the slots with min_until > step
+    return lg, rows, P, [7, 640], E
+
+
+def slot_inv_temp(p):
+    """the fp32 factor a slot stores for temperature p["temperature"]"""
+    return (torch.tensor(1.0) / torch.tensor(p["temperature"], dtype=torch.float32)).item() if p["do_sample"] else 1.0

@@ -9,6 +9,7 @@ import torch
 
 from rwkvtts_amd.sampling import RowSampler, ras_step
 from sampling_laws import exact_probs as _exact_probs
+from sampling_laws import ras_exact as _ras_exact
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -164,27 +165,6 @@ def test_unsupported_requests_are_refused():
     assert RowSampler.supported(torch.device(DEV), [66661], allow=[(65536, 66561)], do_sample=True, top_k=50) is None
     with pytest.raises(ValueError):
         RowSampler(torch.device(DEV), [100], do_sample=True, top_k=0, top_p=0.9)
-
-
-def _ras_exact(logp64, recent, ignore_eos, eos, top_p, top_k, win, tau_r):
-    """probability of every output id of ras_sampling + EOS rejection (the semantics of cosy_llm.ras_sampling_device)"""
-    probs = logp64.softmax(0)
-    sv, si = probs.sort(descending=True, stable=True)
-    cum_before = sv.cumsum(0) - sv
-    keep = ((cum_before < top_p) & (torch.arange(sv.numel()) < top_k)).long().cumprod(0).double()
-    pk = sv * keep
-    if ignore_eos:
-        pk = pk.masked_fill(si == eos, 0.0)
-        if pk.sum() == 0:
-            pk = sv.masked_fill(si == eos, 0.0)
-    pc = torch.zeros_like(probs).scatter(0, si, pk / pk.sum())          # P(candidate = id)
-    full = probs.clone()
-    if ignore_eos:
-        full[eos] = 0
-    full = full / full.sum()
-    rep = torch.tensor([(recent == i).sum().item() for i in range(probs.numel())])
-    redo = (rep >= win * tau_r).double()
-    return pc * (1 - redo) + (pc * redo).sum() * full
 
 
 @pytest.mark.parametrize("case", ["plain", "ignore_eos", "eos_alone", "repeat"])
