@@ -442,6 +442,22 @@ int rwkv7_add_ln_mix_rows_fwd_bf16(int T, int D, int nmix, const void *x, const 
  *      layers > 65535, D or H < 1; RWKV7_ESHAPE: D % 8 != 0 or D > 4096; RWKV7_EHEAD: D != 64 * H.  Nothing is launched then. */
 int rwkv7_cache_rows_commit_bf16(int layers, int n, const void *const *src_tbl, void *const *dst_tbl, const int *src_row,
                                  const int *dst_row, int D, int H, rwkv7_stream_t stream);
+/*   rwkv7_cache_rows_seed_bf16: the same launch (one kernel body, csrc/cache_rows.hip) for an admission that starts some requests
+ *      from STORED states and the others from zero (rwkvtts_amd/state_store.py; ContinuousDecoder(..., state_store=...)): what 3 L
+ *      index_fill_ plus 3 L index_copy_ calls do, and the choice between the two is device data.  Tables, shapes and error codes as
+ *      for rwkv7_cache_rows_commit_bf16.  Entry i, with s = src_row[i] and d = dst_row[i]:
+ *        d < 0                        skipped
+ *        s >= 0                       row s of the source -> row d of the destination, all three fields of all layers, bits preserved
+ *        s == RWKV7_SEED_ZERO (-1)    zeros -> row d of the destination, all three fields of all layers; the source is not read
+ *        s < -1                       skipped
+ *      Rows are NOT range-checked (device data): the caller guarantees source rows inside the source cache, destination rows inside
+ *      the destination cache, and DISTINCT destination rows among the active entries (copy and zero entries alike).  With one
+ *      cache as source and destination no active destination may equal an active source.  Rows not named keep every bit.
+ *      n = 0 returns RWKV7_OK without a launch.  RWKV7_EINVAL: NULL table, NULL index array with n > 0, n < 0, layers < 1, n or
+ *      layers > 65535, D or H < 1; RWKV7_ESHAPE: D % 8 != 0 or D > 4096; RWKV7_EHEAD: D != 64 * H.  Nothing is launched then. */
+#define RWKV7_SEED_ZERO (-1)
+int rwkv7_cache_rows_seed_bf16(int layers, int n, const void *const *src_tbl, void *const *dst_tbl, const int *src_row,
+                               const int *dst_row, int D, int H, rwkv7_stream_t stream);
 /*      (The round-3/4 per-chunk gradient kernel, csrc/lab/wkv7_chunk_bwd9.hip, is an A/B twin with its own entry point in the lab build:
  *      include/rwkv7_hip_lab.h.  There are no process-wide switches in this library.) */
 /* ---- head loss: softmax cross-entropy of a chunk of bf16 logits [rows,V], forward and backward in one pass

@@ -47,6 +47,8 @@ class Request:
     seed: int = 0
     group_size: int = 1             # candidates of one prompt that are admitted together (GroupScheduler); 1: a request of its own
     leader: Optional[int] = None    # handle of the group's first candidate, whose prefill this one shares; None: it prefills itself
+    state: Optional[str] = None     # name of the stored state the prompt continues from (state_store.StateStore); None: from zero
+    state_row: Optional[int] = None  # that state's row in the store, resolved (and pinned) at submit
 
 
 def candidate_seed(seed: int, i: int) -> int:
@@ -275,15 +277,24 @@ class ContinuousDecoder:
     its cache row copied to the siblings' rows (_fan_out); logprobs=True makes the captured step and the admission draw call
     rwkv7_sample_slots_lp_f32, which also writes every drawn id's log-probability (tok_lp [slots, cap] fp32) and the running fp64
     sum (cum_lp [slots]); take_logprobs(handle) hands them out once the handle has been returned, rank_candidates orders them.
-    logprobs=True changes no id; with logprobs=False and no submit_n every code path and launch is the one of before."""
+    logprobs=True changes no id; with logprobs=False and no submit_n every code path and launch is the one of before.
+
+    Stored states: with state_store=StateStore(model, ...) a request may name a stored state, submit(state="voice", input_ids=suffix):
+    its prompt is the SUFFIX and continues from the stored row, which one rwkv7_cache_rows_seed_bf16 launch copies into the slot's
+    row (eager: together with the zero rows of the fresh requests of the same admission, instead of the index_fill_ loop; graph /
+    overlap: ahead of a PackedPrefill whose zero marks are per sequence; overlap: on the side stream into the staging rows).  The
+    name is pinned in the store from submit() until its admission has read the row.  A seeded request's ids do not depend on its
+    slot or on when it is admitted, as for any request (graph / overlap: for the same pack composition).  Without a store every
+    code path and launch is the one of before."""
 
     logprobs = False   # the default of the constructor's switch; nothing below looks at tok_lp / cum_lp without it
     lp = None          # SlotLogprob with logprobs=True: the draws go through rwkv7_sample_slots_lp_f32
+    store = None       # the attached StateStore; without one nothing below seeds a row
 
     def __init__(self, model, slots: int = 32, max_new_tokens_cap: int = 3000, eos_token_id: Optional[int] = None,
                  pad_token_id: Optional[int] = None, suppress_tokens: Optional[Sequence[int]] = None, check_every: int = 16,
                  admission: str = "eager", prefill_max_seqs: int = 8, prefill_buckets: Sequence[int] = (256, 512, 1024, 2048, 4096),
-                 overlap_replays: int = 8, logprobs: bool = False):
+                 overlap_replays: int = 8, logprobs: bool = False, state_store=None):
         if admission not in ("eager", "graph", "overlap"):
             raise ValueError(f"admission = {admission!r}: 'eager', 'graph' or 'overlap'")
         if overlap_replays < 0:
@@ -298,6 +309,12 @@ class ContinuousDecoder:
         self.device, self.slots, self.cap, self.check_every = dev, slots, int(max_new_tokens_cap), int(check_every)
         self.eos = None if eos_token_id is None else int(eos_token_id)
         self.pad = pad_token_id
+        self.store = state_store
+        if state_store is not None:
+            why = state_store.compatible(m.config, m.dtype, dev)
+            if why:
+                raise ValueError("state_store: " + why)
+            state_store.table   # built here, on this stream, not by the first admission (which may run on the side stream)
         self.cache = Cache.zeros(m.config, slots, dev, m.dtype)
         why = step_class(slots).supported(m.model, m.lm_head, self.cache)
         if why is None and m.dtype != torch.bfloat16:
@@ -381,19 +398,23 @@ class ContinuousDecoder:
     # ---- public interface ----------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def submit(self, input_ids=None, inputs_embeds=None, max_new_tokens: int = 256, min_new_tokens: int = 0, do_sample: bool = False,
-               temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: Optional[int] = None) -> int:
-        """Queue one request (a prompt of T ids [T] / [1, T] or embeddings [T, D] / [1, T, D]); returns its handle.  Non-blocking."""
+               temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: Optional[int] = None, state: Optional[str] = None) -> int:
+        """Queue one request (a prompt of T ids [T] / [1, T] or embeddings [T, D] / [1, T, D]); returns its handle.  Non-blocking.
+        state: the name of a state in the attached store; the prompt (>= 1 token) is then the suffix that continues from it.
+        ValueError without a store, KeyError for a name the store does not hold."""
         seed = int(fresh_seed() if seed is None else seed) & ((1 << 64) - 1)
-        return self.sched.submit(seed=seed, **self._request_fields(input_ids, inputs_embeds, max_new_tokens, min_new_tokens, do_sample,
-                                                                   temperature, top_k, top_p))
+        fields = self._request_fields(input_ids, inputs_embeds, max_new_tokens, min_new_tokens, do_sample, temperature, top_k, top_p)
+        return self.sched.submit(seed=seed, **fields, **self._state_fields(state))
 
     @torch.no_grad()
     def submit_n(self, n: int, input_ids=None, inputs_embeds=None, max_new_tokens: int = 256, min_new_tokens: int = 0,
-                 do_sample: bool = False, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: Optional[int] = None) -> List[int]:
+                 do_sample: bool = False, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: Optional[int] = None,
+                 state: Optional[str] = None) -> List[int]:
         """Queue n candidates of ONE prompt (submit()'s arguments): their handles in candidate order.  Candidate i draws with the key
         candidate_seed(seed, i) and is, id for id, the request submit(..., seed=candidate_seed(seed, i)) would be.  The group is admitted
         whole, when n slots are free: the prompt is prefilled once and its cache row copied to the other candidates' rows.
-        n > slots: ValueError.  n > 1 with admission="overlap": ValueError (the staging index arrays hold one entry per prompt)."""
+        n > slots: ValueError.  n > 1 with admission="overlap": ValueError (the staging index arrays hold one entry per prompt).
+        state: as for submit(); the group's first candidate is seeded from the stored row and its row fans out as ever."""
         n = int(n)
         if n < 1 or n > self.slots:
             raise ValueError(f"n = {n} candidates outside 1..{self.slots} (slots): a group is admitted whole")
@@ -402,6 +423,7 @@ class ContinuousDecoder:
                              "to prompts; use admission='eager' or 'graph'")
         fields = self._request_fields(input_ids, inputs_embeds, max_new_tokens, min_new_tokens, do_sample, temperature, top_k, top_p)
         seed = int(fresh_seed() if seed is None else seed) & ((1 << 64) - 1)
+        fields.update(self._state_fields(state))   # pinned once per group: the first candidate's admission unpins
         if n == 1:
             return [self.sched.submit(seed=seed, **fields)]
         return self.sched.submit_group(n, [candidate_seed(seed, i) for i in range(n)], **fields)
@@ -416,6 +438,38 @@ class ContinuousDecoder:
             return self._lp_done.pop(handle)
         except KeyError:
             raise KeyError(f"handle {handle}: not finished yet (step() / run() has not returned it), unknown, or already taken") from None
+
+    def _state_fields(self, state) -> dict:
+        """submit(state=...): the name's row, pinned until the request's admission has read it.  Call it last: nothing after it may raise."""
+        if state is None:
+            return {}
+        if self.store is None:
+            raise ValueError(f"state = {state!r} needs ContinuousDecoder(..., state_store=...)")
+        return dict(state=state, state_row=self.store.pin(state))   # KeyError for an unknown name
+
+    def _unpin(self, took):
+        for _, r in took:
+            if r.state is not None and r.leader is None:
+                self.store.unpin(r.state)
+
+    def _seed(self, heads, dst_tbl, dst_rows, n_dst: int, zero_fresh: bool):
+        """One rwkv7_cache_rows_seed_bf16 launch on the current stream for the admitted `heads`: the stored row of every seeded
+        request -> its row dst_rows[i] of the cache behind dst_tbl (of n_dst rows); a fresh request's row gets zeros (zero_fresh) or
+        is left to the prefill kernels' zero marks (its entry is skipped)."""
+        from .prefill import SEED_ZERO, cache_rows_seed, check_seed_rows
+        cfg = self.model.config
+        src = [SEED_ZERO if r.state_row is None else r.state_row for _, r in heads]
+        dst = [d if (zero_fresh or r.state_row is not None) else -1 for d, (_, r) in zip(dst_rows, heads)]
+        src, dst = check_seed_rows(src, dst, self.store.capacity, n_dst)
+        rows = torch.tensor([src, dst], dtype=torch.int32).pin_memory().to(self.device, non_blocking=True)
+        cache_rows_seed(self.store.table, dst_tbl, rows[0], rows[1], len(heads), len(self.cache), cfg.hidden_size, cfg.num_heads)
+
+    def _cache_tbl(self):
+        """The live cache's own field table (built once)."""
+        if self._fan_tbl is None:
+            from .prefill import cache_field_table
+            self._fan_tbl = cache_field_table(self.cache)
+        return self._fan_tbl
 
     def _request_fields(self, input_ids, inputs_embeds, max_new_tokens, min_new_tokens, do_sample, temperature, top_k, top_p) -> dict:
         """submit()'s argument checks and the prompt's embeddings: Request's fields but the handle and the seed."""
@@ -501,10 +555,14 @@ class ContinuousDecoder:
         for n in lens:
             cu.append(cu[-1] + n)
         rows64 = torch.tensor(slots, dtype=torch.int64).to(dev, non_blocking=True)
-        for st in self.cache.states:   # a fresh state for every admitted request
-            st.att_x_prev.index_fill_(0, rows64, 0)
-            st.att_kv.index_fill_(0, rows64, 0)
-            st.ffn_x_prev.index_fill_(0, rows64, 0)
+        if self.store is not None:     # a stored state or a fresh one for every admitted request, in one launch
+            self._seed(heads, self._cache_tbl(), slots, self.slots, zero_fresh=True)
+            self._unpin(took)
+        else:
+            for st in self.cache.states:   # a fresh state for every admitted request
+                st.att_x_prev.index_fill_(0, rows64, 0)
+                st.att_kv.index_fill_(0, rows64, 0)
+                st.ffn_x_prev.index_fill_(0, rows64, 0)
         packed = torch.cat([r.embeds for _, r in heads], 0).unsqueeze(0)
         cu_t = torch.tensor(cu, dtype=torch.int32)
         h = m.model(inputs_embeds=packed, cu_seqlens=cu_t, past_key_values=self.cache, cache_rows=torch.tensor(slots)).last_hidden_state
@@ -518,7 +576,13 @@ class ContinuousDecoder:
     def _admit_graph(self, took, heads, slots):
         """Admission through PackedPrefill: the rows are reset by the kernels (zero marks), the layout goes over as one pinned index
         block per replay, and nothing is read back."""
-        h_last = self.prefill.run([r.embeds for _, r in heads], slots, fresh=True)
+        fresh = True
+        if any(r.state_row is not None for _, r in heads):   # stored rows in; the fresh requests keep the kernels' zero marks
+            self._seed(heads, self._cache_tbl(), slots, self.slots, zero_fresh=False)
+            fresh = [r.state_row is None for _, r in heads]
+        if self.store is not None:
+            self._unpin(took)
+        h_last = self.prefill.run([r.embeds for _, r in heads], slots, fresh=fresh)
         logits = self.model.lm_head(h_last).float()
         if len(heads) < len(took):
             logits, slots = self._fan_out(took, heads, logits)
@@ -530,7 +594,7 @@ class ContinuousDecoder:
         admitted together in ONE rwkv7_cache_rows_commit_bf16 launch over the cache's own field table (a repeated source row fans out; no
         row is both read and written: sources are first candidates, destinations are not).  Returns (one logits row per admitted
         request -- its prompt's, gathered --, every admitted slot in `took` order)."""
-        from .prefill import cache_field_table, cache_rows_commit, check_commit_rows
+        from .prefill import cache_rows_commit, check_commit_rows
         dev, cfg = self.device, self.model.config
         slot_of = {r.handle: s for s, r in heads}
         row_of = {r.handle: i for i, (_, r) in enumerate(heads)}
@@ -538,10 +602,9 @@ class ContinuousDecoder:
         src, dst = check_commit_rows([a for a, _ in sibs], [b for _, b in sibs], self.slots, self.slots)
         if set(src) & set(dst):
             raise RuntimeError(f"fan-out rows {src} -> {dst}: a row is both read and written")
-        if self._fan_tbl is None:
-            self._fan_tbl = cache_field_table(self.cache)
+        tbl = self._cache_tbl()
         rows = torch.tensor([src, dst], dtype=torch.int32).to(dev, non_blocking=True)
-        cache_rows_commit(self._fan_tbl, self._fan_tbl, rows[0], rows[1], len(sibs), len(self.cache), cfg.hidden_size, cfg.num_heads)
+        cache_rows_commit(tbl, tbl, rows[0], rows[1], len(sibs), len(self.cache), cfg.hidden_size, cfg.num_heads)
         pick = torch.tensor([row_of[r.handle if r.leader is None else r.leader] for _, r in took], dtype=torch.int64).to(dev, non_blocking=True)
         return logits.index_select(0, pick), [s for s, _ in took]
 
@@ -614,13 +677,18 @@ class ContinuousDecoder:
 
     def _launch_device(self, took):
         """The group's prefill into stage rows 0 .. n - 1 on the side stream.  The side stream first waits for the decode stream: for
-        the prompts' embeddings, and for the previous commit's read of the stage rows and of logits_stage."""
+        the prompts' embeddings, for the previous commit's read of the stage rows and of logits_stage, and for whatever wrote the
+        stored states the group continues from (a StateStore.capture issued on the decode stream just before)."""
         main, side = torch.cuda.current_stream(self.device), self._side
         side.wait_stream(main)
         with torch.cuda.stream(side):
             for _, r in took:
                 r.embeds.record_stream(side)
-            h_last = self.prefill.run([r.embeds for _, r in took], list(range(len(took))), fresh=True)
+            fresh = True
+            if any(r.state_row is not None for _, r in took):   # stored rows -> staging rows; the names stay pinned until the commit
+                self._seed(took, self._src_tbl, list(range(len(took))), self.stage_rows, zero_fresh=False)
+                fresh = [r.state_row is None for _, r in took]
+            h_last = self.prefill.run([r.embeds for _, r in took], list(range(len(took))), fresh=fresh)
             self.logits_stage[:len(took)].copy_(self.model.lm_head(h_last).float())
             self._ready.record(side)
 
@@ -640,6 +708,8 @@ class ContinuousDecoder:
         self._pin_used[k] = True
         self._groups += 1
         main.wait_event(self._ready)
+        if self.store is not None:
+            self._unpin(took)   # the decode stream is now ordered after the side stream's read of the stored rows
         cfg = self.model.config
         cache_rows_commit(self._src_tbl, self._dst_tbl, self._src_row, self._dst_row, n, len(self.cache), cfg.hidden_size, cfg.num_heads)
         row_slot = self._dst_row[:n]

@@ -1,29 +1,38 @@
-// rwkvtts_amd/csrc/cache_rows.hip -- commit staged cache rows (rwkvtts_amd/continuous.py, admission="overlap"): for every entry i
-// with dst_row[i] >= 0, row src_row[i] of a source cache is copied to row dst_row[i] of a destination cache, all three fields
-// (att_x_prev bf16 [S,D], att_kv fp32 [S,H,64,64], ffn_x_prev bf16 [S,D]) of all layers, in ONE launch: what 3 L index_copy_ calls do.
+// rwkvtts_amd/csrc/cache_rows.hip -- whole cache rows in ONE launch, all three fields (att_x_prev bf16 [S,D], att_kv fp32 [S,H,64,64],
+// ffn_x_prev bf16 [S,D]) of all layers: what 3 L index_copy_ (and index_fill_) calls do.  Two entries over one kernel body:
+//   commit (rwkvtts_amd/continuous.py, admission="overlap" and submit_n): for every entry i with src_row[i] >= 0 and dst_row[i] >= 0,
+//          row src_row[i] of a source cache is copied to row dst_row[i] of a destination cache;
+//   seed   (rwkvtts_amd/state_store.py, admission from a stored state): the same, and an entry with src_row[i] == RWKV7_SEED_ZERO (-1)
+//          writes zeros to row dst_row[i] instead (a fresh request next to seeded ones); src_row[i] < -1 skips the entry.
 //
 // A row of the three fields of one layer is one virtual array of 16-byte vectors: D/8 | 1024 H | D/8 (D = 64 H, so 1040 H in all).
 // Grid (piece of that array, entry, layer); a thread moves kCommitVecs vectors, all loads issued before the first store.  The field
 // pointers come from two device tables, the rows from two device index arrays, so nothing about a particular admission reaches the
-// launch.  Pure copy: plain 16-byte vector loads and stores, no LDS, no atomics, bits preserved whatever they encode.
+// launch -- the choice between copy and zero included.  Plain 16-byte vector loads and stores, no LDS, no atomics, bits preserved
+// whatever they encode.
 //
 // Neither row index is range-checked against the caches' row counts (device data; the caller's guarantee, include/rwkv7_hip.h); a
-// negative index of either kind skips the entry.  Destination rows must be distinct among the active entries.
+// negative destination skips the entry, and so does a negative source other than the seed entry's zero mark.  Destination rows must
+// be distinct among the active entries.
 #include <hip/hip_runtime.h>
 
+#include "../../include/rwkv7_hip.h"
 #include "launchers.h"
 
 namespace rwkv7 {
 
 constexpr int kCommitThreads = 256, kCommitVecs = 4;
 
-__global__ __launch_bounds__(kCommitThreads) void cache_rows_commit_kernel(const uint4 *const *__restrict__ src_tbl,
-                                                                           uint4 *const *__restrict__ dst_tbl,
-                                                                           const int *__restrict__ src_row,
-                                                                           const int *__restrict__ dst_row, int xv, int kvv) {
+// kZero: a source row of RWKV7_SEED_ZERO means "write zeros" (the seed entry); without it every negative source row skips (commit)
+template <bool kZero>
+__global__ __launch_bounds__(kCommitThreads) void cache_rows_kernel(const uint4 *const *__restrict__ src_tbl,
+                                                                    uint4 *const *__restrict__ dst_tbl,
+                                                                    const int *__restrict__ src_row,
+                                                                    const int *__restrict__ dst_row, int xv, int kvv) {
     const int e = blockIdx.y, l = blockIdx.z;
     const long sr = src_row[e], dr = dst_row[e];
-    if (sr < 0 || dr < 0) return;   // uniform over the workgroup
+    const bool zero = kZero && sr == RWKV7_SEED_ZERO;
+    if ((sr < 0 && !zero) || dr < 0) return;   // uniform over the workgroup
     const uint4 *const s0 = src_tbl[3 * l], *const s1 = src_tbl[3 * l + 1], *const s2 = src_tbl[3 * l + 2];
     uint4 *const d0 = dst_tbl[3 * l], *const d1 = dst_tbl[3 * l + 1], *const d2 = dst_tbl[3 * l + 2];
     const int nv = 2 * xv + kvv;
@@ -46,7 +55,7 @@ __global__ __launch_bounds__(kCommitThreads) void cache_rows_commit_kernel(const
                 from = s2 + sr * xv + (i - xv - kvv);
                 to[j] = d2 + dr * xv + (i - xv - kvv);
             }
-            v[j] = *from;
+            v[j] = zero ? make_uint4(0, 0, 0, 0) : *from;   // a zero entry reads nothing: `from` is never dereferenced
         }
     }
 #pragma unroll
@@ -54,15 +63,26 @@ __global__ __launch_bounds__(kCommitThreads) void cache_rows_commit_kernel(const
         if (to[j]) *to[j] = v[j];
 }
 
-int cache_rows_commit_bf16(int layers, int n, const void *const *src_tbl, void *const *dst_tbl, const int *src_row, const int *dst_row,
-                           int D, int H, hipStream_t st) {
+template <bool kZero>
+static int cache_rows_launch(int layers, int n, const void *const *src_tbl, void *const *dst_tbl, const int *src_row, const int *dst_row,
+                             int D, int H, hipStream_t st) {
     (void)hipGetLastError();
     const int xv = D / 8, kvv = H * 1024, nv = 2 * xv + kvv;
     const int per = kCommitThreads * kCommitVecs;
     const dim3 grid((nv + per - 1) / per, n, layers), block(kCommitThreads);
-    hipLaunchKernelGGL(cache_rows_commit_kernel, grid, block, 0, st, (const uint4 *const *)src_tbl, (uint4 *const *)dst_tbl, src_row,
+    hipLaunchKernelGGL(cache_rows_kernel<kZero>, grid, block, 0, st, (const uint4 *const *)src_tbl, (uint4 *const *)dst_tbl, src_row,
                        dst_row, xv, kvv);
     return (int)hipGetLastError();
+}
+
+int cache_rows_commit_bf16(int layers, int n, const void *const *src_tbl, void *const *dst_tbl, const int *src_row, const int *dst_row,
+                           int D, int H, hipStream_t st) {
+    return cache_rows_launch<false>(layers, n, src_tbl, dst_tbl, src_row, dst_row, D, H, st);
+}
+
+int cache_rows_seed_bf16(int layers, int n, const void *const *src_tbl, void *const *dst_tbl, const int *src_row, const int *dst_row,
+                         int D, int H, hipStream_t st) {
+    return cache_rows_launch<true>(layers, n, src_tbl, dst_tbl, src_row, dst_row, D, H, st);
 }
 
 }  // namespace rwkv7

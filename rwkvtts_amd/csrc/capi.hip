@@ -220,15 +220,29 @@ int rwkv7_add_ln_mix_rows_fwd_bf16(int T, int D, int nmix, const void *x, const 
     return rwkv7::add_ln_mix_rows_fwd_bf16(T, D, nmix, x, branch, gamma, beta, eps, mask, params, prev_src, last_dst,
                                            x_prev_rd ? x_prev_rd : x_prev, x_prev, x_out, out, nblocks, run_len, (hipStream_t)stream);
 }
-// staged cache rows -> slot rows in one launch (rwkvtts_amd/continuous.py, admission="overlap"): tables and row indices are device data
-int rwkv7_cache_rows_commit_bf16(int layers, int n, const void *const *src_tbl, void *const *dst_tbl, const int *src_row,
-                                 const int *dst_row, int D, int H, rwkv7_stream_t stream) {
+// staged cache rows -> slot rows in one launch (rwkvtts_amd/continuous.py, admission="overlap"): tables and row indices are device data.
+// The checks of the two row entries; 1: checked, but nothing to do (n = 0)
+static int cache_rows_check(int layers, int n, const void *const *src_tbl, void *const *dst_tbl, const int *src_row, const int *dst_row,
+                            int D, int H) {
     if (layers < 1 || layers > 65535 || n < 0 || n > 65535 || D <= 0 || H <= 0 || !src_tbl || !dst_tbl) return RWKV7_EINVAL;
     if (D % 8 != 0 || D > 4096) return RWKV7_ESHAPE;
     if (D != 64 * H) return RWKV7_EHEAD;
-    if (n == 0) return RWKV7_OK;   // nothing to commit: no launch
+    if (n == 0) return 1;
     if (!src_row || !dst_row) return RWKV7_EINVAL;
+    return RWKV7_OK;
+}
+int rwkv7_cache_rows_commit_bf16(int layers, int n, const void *const *src_tbl, void *const *dst_tbl, const int *src_row,
+                                 const int *dst_row, int D, int H, rwkv7_stream_t stream) {
+    const int rc = cache_rows_check(layers, n, src_tbl, dst_tbl, src_row, dst_row, D, H);
+    if (rc) return rc < 0 ? rc : RWKV7_OK;   // an argument error, or nothing to commit: no launch
     return rwkv7::cache_rows_commit_bf16(layers, n, src_tbl, dst_tbl, src_row, dst_row, D, H, (hipStream_t)stream);
+}
+// stored or zero rows -> slot (or staging) rows in one launch (rwkvtts_amd/state_store.py): copy or zero is device data too
+int rwkv7_cache_rows_seed_bf16(int layers, int n, const void *const *src_tbl, void *const *dst_tbl, const int *src_row,
+                               const int *dst_row, int D, int H, rwkv7_stream_t stream) {
+    const int rc = cache_rows_check(layers, n, src_tbl, dst_tbl, src_row, dst_row, D, H);
+    if (rc) return rc < 0 ? rc : RWKV7_OK;
+    return rwkv7::cache_rows_seed_bf16(layers, n, src_tbl, dst_tbl, src_row, dst_row, D, H, (hipStream_t)stream);
 }
 // plain rows (one state per row, [B,H,64,64]): the packed entries with seq_chunk_off = NULL, nseq = 0
 int rwkv7_wkv_chunk_fwd_state_bf16(int B, int T, int H, const void *w, const void *q, const void *k, const void *v,

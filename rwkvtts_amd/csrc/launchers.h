@@ -119,6 +119,8 @@ int add_ln_mix_rows_fwd_bf16(int T, int D, int nmix, const void *x, const void *
                              void *x_prev, void *x_out, void *out, int nblocks, int run_len, hipStream_t stream);
 int cache_rows_commit_bf16(int layers, int n, const void *const *src_tbl, void *const *dst_tbl, const int *src_row, const int *dst_row,
                            int D, int H, hipStream_t stream);
+int cache_rows_seed_bf16(int layers, int n, const void *const *src_tbl, void *const *dst_tbl, const int *src_row, const int *dst_row,
+                         int D, int H, hipStream_t stream);   // src_row == RWKV7_SEED_ZERO: zeros instead of a copy
 
 // ---- loss heads and per-sequence scores (head_loss.hip, seq_scores.hip).  C: the entropy constant of the smoothed target
 //      distribution; argmax_rows, and ce_seq_bwd's loss_rows, may be NULL

@@ -55,7 +55,7 @@ class Replay:
         return torch.cat([self.seq_off, self.state_row, self.last_row, self.prev_src, self.last_dst, self.keep.to(torch.int32)])
 
 
-def plan(lens: Sequence[int], rows: Sequence[int], fresh: bool, n_rows: int, max_seqs: int = 8,
+def plan(lens: Sequence[int], rows: Sequence[int], fresh, n_rows: int, max_seqs: int = 8,
          buckets: Sequence[int] = (256, 512, 1024, 2048, 4096)) -> List[Replay]:
     """The replays that prefill prompts of `lens` tokens into cache rows `rows` (of a cache with n_rows rows).  Pure host function.
 
@@ -65,10 +65,14 @@ def plan(lens: Sequence[int], rows: Sequence[int], fresh: bool, n_rows: int, max
     packed first-fit in order; a pack that does not fit the largest bucket or max_seqs becomes several replays.  A prompt longer than
     a bucket holds (largest bucket - 1 tokens) is cut on multiples of 32 tokens into pieces that go to consecutive replays: the later
     pieces continue from the row (prev_src = the row, no zero mark).  fresh=False: the first pieces continue from what the rows hold
-    too (a prompt that arrives in parts)."""
+    too (a prompt that arrives in parts).  fresh may also be a sequence of bools, one per prompt: sequence i gets the zero mark on its
+    first piece only if fresh[i] (a pack that mixes fresh prompts with suffixes of a stored state)."""
     lens, rows = [int(n) for n in lens], [int(r) for r in rows]
     buckets = sorted(int(b) for b in buckets)
     N = len(lens)
+    fresh = [bool(fresh)] * N if isinstance(fresh, (bool, int)) else [bool(f) for f in fresh]
+    if len(fresh) != N:
+        raise ValueError(f"fresh names {len(fresh)} sequences, there are {N}")
     if not buckets or any(b < 2 * C or b % C for b in buckets) or max_seqs < 1:
         raise ValueError(f"buckets must be multiples of {C} >= {2 * C} and max_seqs >= 1, got {buckets}, {max_seqs}")
     if len(rows) != N:
@@ -112,7 +116,7 @@ def plan(lens: Sequence[int], rows: Sequence[int], fresh: bool, n_rows: int, max
         rp = Replay(t_al, seq_off, state_row, prev_src, last_dst, keep, last_row)
         first, last = lay.first.tolist(), lay.last.tolist()
         for j, (i, lo, hi) in enumerate(g):
-            zero = fresh and lo == 0
+            zero = fresh[i] and lo == 0
             state_row[j] = rows[i] | (ROW_ZERO if zero else 0)
             prev_src[first[j]] = -2 if zero else rows[i]
             last_dst[last[j]] = rows[i]
@@ -190,6 +194,31 @@ def cache_rows_commit(src_tbl, dst_tbl, src_row, dst_row, n: int, layers: int, D
     _lib.call("rwkv7_cache_rows_commit_bf16", dst_tbl, int(layers), int(n), src_tbl, dst_tbl, src_row, dst_row, int(D), int(H))
 
 
+SEED_ZERO = -1   # RWKV7_SEED_ZERO (include/rwkv7_hip.h)
+
+
+def check_seed_rows(src_row: Sequence[int], dst_row: Sequence[int], src_rows: int, dst_rows: int):
+    """check_commit_rows for rwkv7_cache_rows_seed_bf16: an entry is active with a destination >= 0 and a source >= SEED_ZERO (a
+    source below it skips the entry, as a negative destination does); an active source is SEED_ZERO or a row in [0, src_rows)."""
+    src_row, dst_row = [int(r) for r in src_row], [int(r) for r in dst_row]
+    if len(src_row) != len(dst_row):
+        raise ValueError(f"{len(src_row)} source rows for {len(dst_row)} destination rows")
+    act = [(s, d) for s, d in zip(src_row, dst_row) if d >= 0 and s >= SEED_ZERO]
+    if any(s >= src_rows for s, _ in act) or any(d >= dst_rows for _, d in act) or len({d for _, d in act}) != len(act):
+        raise ValueError(f"rows {src_row} -> {dst_row}: sources must be {SEED_ZERO} (zero) or lie in [0, {src_rows}), destinations "
+                         f"distinct in [0, {dst_rows})")
+    return src_row, dst_row
+
+
+def cache_rows_seed(src_tbl, dst_tbl, src_row, dst_row, n: int, layers: int, D: int, H: int):
+    """rwkv7_cache_rows_seed_bf16 on the current stream: cache_rows_commit's arguments; an entry whose source row is SEED_ZERO writes
+    zeros to its destination row, one whose source row is below that is skipped.  The caller has checked the values (check_seed_rows)."""
+    for t in (src_row, dst_row):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.is_cuda and t.numel() >= n
+    assert src_tbl.dtype == torch.int64 and dst_tbl.dtype == torch.int64 and src_tbl.numel() == dst_tbl.numel() == 3 * layers
+    _lib.call("rwkv7_cache_rows_seed_bf16", dst_tbl, int(layers), int(n), src_tbl, dst_tbl, src_row, dst_row, int(D), int(H))
+
+
 class _Bucket:
     def __init__(self, t_al, max_seqs, D, dev):
         self.t_al = t_al
@@ -248,9 +277,9 @@ class PackedPrefill:
         return self
 
     @torch.no_grad()
-    def run(self, prompts: Sequence[torch.Tensor], rows: Sequence[int], fresh: bool = True) -> torch.Tensor:
-        """prompts: [n_i, D] bf16 embeddings on the device; rows: their cache rows (host ints).  Returns h_last [len(prompts), D]: the
-        final-norm output at every prompt's last token.  Per replay: the bucket's static input row is zeroed up to the high-water
+    def run(self, prompts: Sequence[torch.Tensor], rows: Sequence[int], fresh=True) -> torch.Tensor:
+        """prompts: [n_i, D] bf16 embeddings on the device; rows: their cache rows (host ints); fresh: a bool, or one bool per prompt
+        (False: the prompt continues from what its row holds).  Returns h_last [len(prompts), D]: the final-norm output at every prompt's last token.  Per replay: the bucket's static input row is zeroed up to the high-water
         mark its previous use left (a per-bucket high-water mark, not a full clear), the pieces are copied into their aligned ranges,
         the index block goes over in one pinned host-to-device copy, and the graph is replayed.  No device read-back anywhere."""
         rows = [int(r) for r in rows]
