@@ -458,6 +458,49 @@ int rwkv7_cache_rows_commit_bf16(int layers, int n, const void *const *src_tbl, 
 #define RWKV7_SEED_ZERO (-1)
 int rwkv7_cache_rows_seed_bf16(int layers, int n, const void *const *src_tbl, void *const *dst_tbl, const int *src_row,
                                const int *dst_row, int D, int H, rwkv7_stream_t stream);
+/* ---- state tuning (rwkvtts_amd/state_tune.py, csrc/state_tune.hip): every weight frozen, the initial states of named voices are
+ *      the trained tensors.  The MASTER state of voice v is fp32, per layer att_x_prev [V,D], att_kv [V,H,64,64], ffn_x_prev [V,D];
+ *      its AdamW moments m and v are fp32 of the same shapes.  Every table below is a DEVICE table of 3 * layers pointers in the
+ *      order of rwkv7_cache_rows_seed_bf16 (per layer att_x_prev, att_kv, ffn_x_prev; every field contiguous, 16-byte aligned).
+ *   rwkv7_state_rows_expand_f32: the forward hand-over, one launch for all layers and fields.  dst_tbl names an n-row bf16 cache
+ *      (att_x_prev / ffn_x_prev bf16 [n,D], att_kv fp32 [n,H,64,64]); voice is DEVICE int32 [n].  Entry i, with v = voice[i]:
+ *        v >= 0     master row v -> row i of the cache: att_kv bits copied, the two shift rows rounded ONCE to bf16
+ *                   (round-to-nearest-even; a NaN stays a quiet NaN)
+ *        v == -1    zeros -> row i, all three fields of all layers; no source is read
+ *        v < -1     skipped: row i keeps every bit
+ *      voice[i] is NOT range-checked against the master's rows (device data; the caller's guarantee).
+ *      n = 0 returns RWKV7_OK without a launch.  Error codes as for rwkv7_cache_rows_seed_bf16: RWKV7_EINVAL: NULL table, NULL voice
+ *      with n > 0, n < 0, layers < 1, n or layers > 65535, D or H < 1; RWKV7_ESHAPE: D % 8 != 0 or D > 4096; RWKV7_EHEAD:
+ *      D != 64 * H.  Nothing is launched then. */
+int rwkv7_state_rows_expand_f32(int layers, int n, const void *const *master_tbl, void *const *dst_tbl, const int *voice, int D, int H,
+                                rwkv7_stream_t stream);
+/*   rwkv7_state_rows_adamw_f32: the optimizer step of the voices of one batch, one launch for all layers, fields and active voices.
+ *        grad_tbl     the leaf gradients of the n-row cache the forward started from: fp32 [n,H,64,64] for att_kv, bf16 [n,D] for
+ *                     the shift rows.  A NULL entry: that field is not tuned -- its master, moments and store row are left alone
+ *                     (the m_tbl / v_tbl entries of such a field are not read and may be NULL too)
+ *        master_tbl, m_tbl, v_tbl   the fp32 master states and moments, updated in place
+ *        store_tbl    the serving cache (a StateStore's: bf16 shift rows, fp32 att_kv) that receives the new states
+ *        seg_start    DEVICE int32 [A + 1], a CSR over seg_rows: active voice a owns seg_rows[seg_start[a] .. seg_start[a + 1])
+ *        seg_rows     DEVICE int32 [seg_start[A]]: rows of the gradient cache, grouped by voice
+ *        seg_info     DEVICE int32 [A][3] = {the voice's row in the master, its row in the store or -1 (no row is written), its
+ *                     step count t >= 1 (1 for its first update)}
+ *        skip_flag    DEVICE float or NULL; != 0 runs the step on a ZERO gradient, as rwkv7_adamw_groups_bf16 does (the gradients
+ *                     are still read; a NaN in them reaches nothing)
+ *      Per element of a tuned field of an active voice: g = grad_scale * (the gradients of the voice's rows added in fp32, one after
+ *      the other in the listed order, starting from 0), then the update rule of rwkv7_adamw_bf16 (torch.optim.AdamW, decoupled
+ *      weight decay) with the bias corrections 1 - beta^t of THAT voice's t, formed on the device in double from the float betas;
+ *      then the new state is written to the voice's store row: the fp32 value for att_kv, one round-to-nearest-even to bf16 for the
+ *      shift rows.  No atomics: an element is owned by one thread, which walks the voice's rows itself, so a voice's result does not
+ *      depend on the grid, on the other voices of the launch or on their order, and two identical calls give the same bits.  Voices
+ *      not named keep every bit of master, moments and store row.  A voice may be listed ONCE, store rows must be distinct, and the
+ *      gradient cache must not overlap the store.  No row is range-checked (device data; the caller validates on the host).
+ *      n = 0 or A = 0 returns RWKV7_OK without a launch.  RWKV7_EINVAL: a NULL table, a NULL seg_* array with n > 0 and A > 0, n or
+ *      A < 0 or > 65535, layers < 1 or > 21845 (3 * layers is a grid dimension), D or H < 1; RWKV7_ESHAPE: D % 8 != 0 or D > 4096;
+ *      RWKV7_EHEAD: D != 64 * H.  Nothing is launched then. */
+int rwkv7_state_rows_adamw_f32(int layers, int n, int A, const void *const *grad_tbl, void *const *master_tbl, void *const *m_tbl,
+                               void *const *v_tbl, void *const *store_tbl, const int *seg_start, const int *seg_rows, const int *seg_info,
+                               const float *skip_flag, float lr, float beta1, float beta2, float eps, float weight_decay,
+                               float grad_scale, int D, int H, rwkv7_stream_t stream);
 /*      (The round-3/4 per-chunk gradient kernel, csrc/lab/wkv7_chunk_bwd9.hip, is an A/B twin with its own entry point in the lab build:
  *      include/rwkv7_hip_lab.h.  There are no process-wide switches in this library.) */
 /* ---- head loss: softmax cross-entropy of a chunk of bf16 logits [rows,V], forward and backward in one pass

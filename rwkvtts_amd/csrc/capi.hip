@@ -244,6 +244,26 @@ int rwkv7_cache_rows_seed_bf16(int layers, int n, const void *const *src_tbl, vo
     if (rc) return rc < 0 ? rc : RWKV7_OK;
     return rwkv7::cache_rows_seed_bf16(layers, n, src_tbl, dst_tbl, src_row, dst_row, D, H, (hipStream_t)stream);
 }
+// state tuning (rwkvtts_amd/state_tune.py): master rows -> training cache rows, and the AdamW step of the voices of a batch.  The
+// shape checks are cache_rows_check's (a table stands in for the index arrays it also wants).
+int rwkv7_state_rows_expand_f32(int layers, int n, const void *const *master_tbl, void *const *dst_tbl, const int *voice, int D, int H,
+                                rwkv7_stream_t stream) {
+    const int rc = cache_rows_check(layers, n, master_tbl, dst_tbl, voice, voice, D, H);
+    if (rc) return rc < 0 ? rc : RWKV7_OK;
+    return rwkv7::state_rows_expand_f32(layers, n, master_tbl, dst_tbl, voice, D, H, (hipStream_t)stream);
+}
+int rwkv7_state_rows_adamw_f32(int layers, int n, int A, const void *const *grad_tbl, void *const *master_tbl, void *const *m_tbl,
+                               void *const *v_tbl, void *const *store_tbl, const int *seg_start, const int *seg_rows, const int *seg_info,
+                               const float *skip_flag, float lr, float beta1, float beta2, float eps, float weight_decay,
+                               float grad_scale, int D, int H, rwkv7_stream_t stream) {
+    if (A < 0 || A > 65535 || n < 0 || n > 65535 || layers > 21845 || !m_tbl || !v_tbl || !store_tbl)   // 3 * layers is a grid dimension
+        return RWKV7_EINVAL;
+    const int rc = cache_rows_check(layers, A ? n : 0, grad_tbl, master_tbl, seg_start, seg_rows, D, H);   // no voice: as no row
+    if (rc) return rc < 0 ? rc : RWKV7_OK;
+    if (!seg_info) return RWKV7_EINVAL;
+    return rwkv7::state_rows_adamw_f32(layers, A, grad_tbl, master_tbl, m_tbl, v_tbl, store_tbl, seg_start, seg_rows, seg_info, skip_flag,
+                                       lr, beta1, beta2, eps, weight_decay, grad_scale, D, H, (hipStream_t)stream);
+}
 // plain rows (one state per row, [B,H,64,64]): the packed entries with seq_chunk_off = NULL, nseq = 0
 int rwkv7_wkv_chunk_fwd_state_bf16(int B, int T, int H, const void *w, const void *q, const void *k, const void *v,
                                    const void *a, const void *b, const float *tinv, void *y, float *sa, void *hs,

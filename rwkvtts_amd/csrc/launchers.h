@@ -122,6 +122,14 @@ int cache_rows_commit_bf16(int layers, int n, const void *const *src_tbl, void *
 int cache_rows_seed_bf16(int layers, int n, const void *const *src_tbl, void *const *dst_tbl, const int *src_row, const int *dst_row,
                          int D, int H, hipStream_t stream);   // src_row == RWKV7_SEED_ZERO: zeros instead of a copy
 
+// ---- state tuning (state_tune.hip): fp32 master states of named voices -> rows of a bf16 cache, and their AdamW step from the
+//      cache's leaf gradients straight into the serving cache's rows.  skip_flag may be NULL; A >= 1, n >= 1
+int state_rows_expand_f32(int layers, int n, const void *const *master_tbl, void *const *dst_tbl, const int *voice, int D, int H,
+                          hipStream_t stream);
+int state_rows_adamw_f32(int layers, int A, const void *const *grad_tbl, void *const *master_tbl, void *const *m_tbl, void *const *v_tbl,
+                         void *const *store_tbl, const int *seg_start, const int *seg_rows, const int *seg_info, const float *skip_flag,
+                         float lr, float beta1, float beta2, float eps, float wd, float grad_scale, int D, int H, hipStream_t stream);
+
 // ---- loss heads and per-sequence scores (head_loss.hip, seq_scores.hip).  C: the entropy constant of the smoothed target
 //      distribution; argmax_rows, and ce_seq_bwd's loss_rows, may be NULL
 int ce_fwd_bwd(long rows, int V, long ld, void *logits, const long *labels, long ignore_index, float scale, float *loss_rows,
