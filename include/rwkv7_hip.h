@@ -986,6 +986,32 @@ typedef struct rwkv7_ras_slot_state {
 } rwkv7_ras_slot_state;
 int rwkv7_ras_slots_f32(int rows, int V, const float *logits, long ld, const int *row_slot, const rwkv7_ras_slot_state *st,
                         rwkv7_stream_t stream);
+/* rwkv7_ras_slots_lp_f32: rwkv7_ras_slots_f32 that also reports the log-probability of every id it draws
+ * (ContinuousCosyDecoder(logprobs=True): ranking n candidates of one utterance without a second, teacher-forced pass).  For a live
+ * slot every field of `st` -- id, ring, ptr, n_out, seq, step, live, x -- is written bit for bit as rwkv7_ras_slots_f32 writes it.
+ * The value is
+ *   lp = x[id] - m - log sum_j exp(x[j] - m)        (m = the row's maximum)
+ * with x the RAW fp32 logits of the row -- temperature 1, before top-k, top-p and the repetition test; the reference's
+ * logits.log_softmax(-1) entry -- and j over the ids the draw could have produced: all V ids, minus EOS while
+ * step[s] < n_ignore[s] (the reference redraws until it gets another id).  The EOS-free sum is formed from its own terms, not by
+ * subtracting EOS's from the full sum.  When the repetition test replaces the nucleus candidate by the draw from the full
+ * distribution, lp is that id's value under the same formula.  With n = n_out[s] before the call:
+ *   id != eos (emitted):  tok_lp[s][n] = lp (if 0 <= n < seq_ld; row stride seq_ld, column = the id's index in seq),
+ *                         cum_lp[s] += (double)lp (plain read, add, store: one workgroup owns a slot); end_lp[s] is untouched
+ *   id == eos:            end_lp[s] = lp; tok_lp, cum_lp (and n_out) are untouched
+ * A row without a finite logit (or, next to a barred EOS, without any other id of non-zero weight) gives -INFINITY, not NaN.  A
+ * slot that is not live, and a row whose slot is outside [0, slots), leave all three arrays untouched.  The reductions run
+ * thread -> wave -> workgroup in a fixed order: the same logits row and slot state give the same bits whatever row, slot or grid
+ * they are drawn in.  Errors: those of rwkv7_ras_slots_f32, and RWKV7_EINVAL for a null lp, lp->tok_lp, lp->cum_lp or lp->end_lp;
+ * nothing is launched then.  (A struct plus a typedef, like rwkv7_slot_logprob; the Python mirror is continuous_cosy.RasSlotLogprob.) */
+struct rwkv7_ras_slot_logprob {
+    float *tok_lp;              /* [slots][seq_ld]: log-probability of every EMITTED id, column = its index in seq */
+    double *cum_lp;             /* [slots]: running fp64 sum of the slot's tok_lp, in emission order */
+    float *end_lp;              /* [slots]: log-probability of the EOS draw that ended the utterance (written only then) */
+};
+typedef struct rwkv7_ras_slot_logprob rwkv7_ras_slot_logprob;
+int rwkv7_ras_slots_lp_f32(int rows, int V, const float *logits, long ld, const int *row_slot, const rwkv7_ras_slot_state *st,
+                           const rwkv7_ras_slot_logprob *lp, rwkv7_stream_t stream);
 
 /* the low-rank pair of the decode step in one launch: y[M,N] = act(x[M,K] @ w1[R,K]^T) @ w2[N,R]^T (+ bias); M <= 32,
  * K % 64 == 0, R in {32,64,128}, act 0 none / 1 tanh / 2 sigmoid (rwkv_s2s_single_ffn.py:497-500: w, a, v, g branches) */

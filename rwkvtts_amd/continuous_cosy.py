@@ -14,6 +14,10 @@ A request's draws use (its seed, its loop index, its own ring) only, so its ids 
 (graph admission: for the same pack composition, see ContinuousDecoder).  cosy_request is the host part of inference(): the prompt
 layout and the length bounds.  The reference zeroes the token-shift rows of the cache at the end of an utterance (cosy_llm.py:247-251);
 that is not repeated here, because admission resets a slot's rows before they are used again.
+
+Best-of-n (submit_n, logprobs=True, take_logprobs): n candidates of one utterance share one prefill -- the first candidate's cache
+row is copied to its siblings' rows in one rwkv7_cache_rows_commit_bf16 launch -- and rwkv7_ras_slots_lp_f32 writes every drawn id's
+log-probability at draw time, so rank_candidates orders the candidates without a teacher-forced pass.
 """
 from __future__ import annotations
 
@@ -26,7 +30,7 @@ import torch
 from . import _lib
 from .backbone import Cache
 from .decode import check_slots, step_class, step_for
-from .continuous import SlotScheduler
+from .continuous import GroupScheduler, candidate_seed
 from .sampling import MAX_DOMAIN, fresh_seed
 
 MAX_WIN = 128          # entries of a slot's ring (rwkv7_ras_slots_f32)
@@ -44,13 +48,23 @@ class RasSlotState(ctypes.Structure):
                 ("top_k_max", ctypes.c_int), ("eos", ctypes.c_long)]
 
 
-def ras_slots(logits: torch.Tensor, st: RasSlotState, row_slot: Optional[torch.Tensor] = None):
+class RasSlotLogprob(ctypes.Structure):
+    """rwkv7_ras_slot_logprob (include/rwkv7_hip.h)."""
+    _fields_ = [("tok_lp", ctypes.c_void_p), ("cum_lp", ctypes.c_void_p), ("end_lp", ctypes.c_void_p)]
+
+
+def ras_slots(logits: torch.Tensor, st: RasSlotState, row_slot: Optional[torch.Tensor] = None, lp: Optional[RasSlotLogprob] = None):
     """rwkv7_ras_slots_f32 on the current stream: logits fp32 [rows, V] (unit column stride); row_slot int32 [rows] or None (row r
-    is slot r)."""
+    is slot r).  With lp (tok_lp fp32 [slots, seq_ld], cum_lp fp64 [slots], end_lp fp32 [slots]): rwkv7_ras_slots_lp_f32, the same
+    draw plus the drawn ids' log-probabilities."""
     assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
     if row_slot is not None:
         assert row_slot.dtype == torch.int32 and row_slot.is_contiguous() and row_slot.numel() == logits.shape[0]
-    _lib.call("rwkv7_ras_slots_f32", logits, logits.shape[0], logits.shape[1], logits, logits.stride(0), row_slot, ctypes.byref(st))
+    args = (logits.shape[0], logits.shape[1], logits, logits.stride(0), row_slot, ctypes.byref(st))
+    if lp is None:
+        _lib.call("rwkv7_ras_slots_f32", logits, *args)
+    else:
+        _lib.call("rwkv7_ras_slots_lp_f32", logits, *args, ctypes.byref(lp))
 
 
 @dataclass
@@ -135,13 +149,32 @@ class ContinuousCosyDecoder:
     defaults that submit() may override per request.  admission / prefill_max_seqs / prefill_buckets: as in ContinuousDecoder.
 
     The reference zeroes the token-shift rows at the end of an utterance; that is not repeated, because admission resets the slot's
-    rows before they are reused."""
+    rows before they are reused.
+
+    Best-of-n: submit_n(n, ...) queues n candidates of one utterance, admitted together (GroupScheduler), the prompt prefilled once
+    and its cache row copied to the siblings' rows (_fan_out).  logprobs=True makes the captured step and the admission draw call
+    rwkv7_ras_slots_lp_f32, which also writes every emitted id's log-probability under the raw logits (tok_lp [slots, cap] fp32),
+    their running fp64 sum (cum_lp [slots]) and the log-probability of the EOS draw that ended the utterance (end_lp [slots]);
+    take_logprobs(handle) hands them out once the handle has been reported finished, and continuous.rank_candidates orders a group:
+
+        hs = eng.submit_n(4, text=..., prompt_speech_token=..., seed=7); out = eng.run()
+        lp = [eng.take_logprobs(h) for h in hs]                                   # (tok_lp[:n], cum_lp, end_lp) per candidate
+        best = hs[rank_candidates([c for _, c, _ in lp], [out[h].numel() for h in hs])[0]]
+
+    cum_lp covers the emitted ids only; a caller who wants the EOS draw to count adds it: [c + e.double() for _, c, e in lp] (with
+    out[h].numel() + 1 as the length for a candidate that ended on EOS; end_lp is 0 for one that ran to its max_len).  A candidate
+    without an emitted id (EOS first) has length 0, which rank_candidates refuses: leave it out.  logprobs=True changes no id; with
+    logprobs=False and no submit_n every code path and launch is the one of before."""
+
+    logprobs = False   # the default of the constructor's switch; nothing below looks at tok_lp / cum_lp / end_lp without it
+    lp = None          # RasSlotLogprob with logprobs=True: the draws go through rwkv7_ras_slots_lp_f32
 
     def __init__(self, model, slots: int = 32, max_len_cap: int = 3000, check_every: int = 16, admission: str = "eager",
                  win_size: int = 10, top_p: float = 0.8, tau_r: float = 0.1, prefill_max_seqs: int = 8,
-                 prefill_buckets: Sequence[int] = (256, 512, 1024, 2048, 4096)):
+                 prefill_buckets: Sequence[int] = (256, 512, 1024, 2048, 4096), logprobs: bool = False):
         if admission not in ("eager", "graph"):
             raise ValueError(f"admission = {admission!r}: 'eager' or 'graph'")
+        self.logprobs = bool(logprobs)
         check_slots(slots)   # 1..32, or 64 / 96 / 128: ValueError before anything touches the device
         if max_len_cap < 1 or check_every < 1:
             raise ValueError("max_len_cap and check_every must be >= 1")
@@ -194,8 +227,15 @@ class ContinuousCosyDecoder:
         st.emb, st.x, st.D, st.slots = emb_w.data_ptr(), self.x.data_ptr(), D, S
         st.win_size, st.top_k_max, st.eos = self.win_size, MAX_RAS_TOP_K, self.eos
         self.st = st
+        if self.logprobs:   # what rwkv7_ras_slots_lp_f32 writes next to seq / n_out
+            self.tok_lp = torch.zeros(S, self.cap, dtype=torch.float32, device=dev)
+            self.cum_lp = torch.zeros(S, dtype=torch.float64, device=dev)
+            self.end_lp = torch.zeros(S, dtype=torch.float32, device=dev)
+            self.lp = RasSlotLogprob(self.tok_lp.data_ptr(), self.cum_lp.data_ptr(), self.end_lp.data_ptr())
+        self._lp_done: Dict[int, Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = {}   # handle -> its values until take_logprobs()
+        self._fan_tbl = None   # submit_n: the cache's own field table, source and destination of the fan-out copy
 
-        self.sched = SlotScheduler(slots)
+        self.sched = GroupScheduler(slots)   # for groups of one its admit() is SlotScheduler's
         self._extra: Dict[int, float] = {}   # handle -> tau_r: what the scheduler's request does not carry
         self.dstep = step_for(m.model, m.lm_head, self.cache)
         # capture the step with every slot idle (live = 0): the draw writes nothing, and what the warm-up does to the state of idle
@@ -215,7 +255,7 @@ class ContinuousCosyDecoder:
             self.prefill = PackedPrefill(m.model, self.cache, max_seqs=prefill_max_seqs, buckets=prefill_buckets)
 
     def _step(self):
-        ras_slots(self.dstep(self.x), self.st)
+        ras_slots(self.dstep(self.x), self.st, None, self.lp)
 
     # ---- public interface ----------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -226,6 +266,52 @@ class ContinuousCosyDecoder:
         """Queue one utterance; returns its handle.  Non-blocking.  Either text (+ prompt_text, prompt_speech_token and the length
         ratios: cosy_request builds the prompt), or the low-level form inputs_embeds [T, D] / [1, T, D] with min_len, max_len and
         original_text_len.  sampling: the top_k of the nucleus."""
+        fields, tau_r = self._request_fields(text, prompt_text, prompt_speech_token, sampling, max_token_text_ratio, min_token_text_ratio,
+                                             inputs_embeds, min_len, max_len, original_text_len, top_p, tau_r)
+        seed = int(fresh_seed() if seed is None else seed) & ((1 << 64) - 1)
+        h = self.sched.submit(seed=seed, **fields)
+        self._extra[h] = tau_r
+        return h
+
+    @torch.no_grad()
+    def submit_n(self, n: int, text=None, prompt_text=None, prompt_speech_token=None, sampling: int = 25, max_token_text_ratio: float = 20,
+                 min_token_text_ratio: float = 0.5, seed: Optional[int] = None, inputs_embeds=None, min_len: Optional[int] = None,
+                 max_len: Optional[int] = None, original_text_len: Optional[int] = None, top_p: Optional[float] = None,
+                 tau_r: Optional[float] = None) -> List[int]:
+        """Queue n candidates of ONE utterance (submit()'s arguments; one cosy_request, one embeds tensor): their handles in
+        candidate order.  Candidate i draws with the key candidate_seed(seed, i) and is, id for id, the request
+        submit(..., seed=candidate_seed(seed, i)) would be.  The group is admitted whole, when n slots are free: the prompt is
+        prefilled once and its cache row copied to the other candidates' rows.  n < 1 or n > slots: ValueError, nothing is queued."""
+        n = int(n)
+        if n < 1 or n > self.slots:
+            raise ValueError(f"n = {n} candidates outside 1..{self.slots} (slots): a group is admitted whole")
+        fields, tau_r = self._request_fields(text, prompt_text, prompt_speech_token, sampling, max_token_text_ratio, min_token_text_ratio,
+                                             inputs_embeds, min_len, max_len, original_text_len, top_p, tau_r)
+        seed = int(fresh_seed() if seed is None else seed) & ((1 << 64) - 1)
+        if n == 1:
+            hs = [self.sched.submit(seed=seed, **fields)]
+        else:
+            hs = self.sched.submit_group(n, [candidate_seed(seed, i) for i in range(n)], **fields)
+        for h in hs:   # the scheduler's request does not carry tau_r: one entry per candidate
+            self._extra[h] = tau_r
+        return hs
+
+    def take_logprobs(self, handle: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(tok_lp [n] fp32, cum_lp fp64 scalar, end_lp fp32 scalar) of a request that step() / run() / stream() has reported
+        finished, all on the device: the log-probability of each of its n emitted ids under the raw logits (temperature 1, before
+        top-k / top-p and the repetition test, over the ids the draw could produce), their sum, added in emission order in fp64, and
+        the log-probability of the EOS draw that ended it (0 when it ran to its max_len instead).  Needs logprobs=True; a handle's
+        result can be taken once."""
+        if not self.logprobs:
+            raise ValueError("take_logprobs needs ContinuousCosyDecoder(..., logprobs=True)")
+        try:
+            return self._lp_done.pop(handle)
+        except KeyError:
+            raise KeyError(f"handle {handle}: not finished yet (step() / run() / stream() has not reported it), unknown, or already taken") from None
+
+    def _request_fields(self, text, prompt_text, prompt_speech_token, sampling, max_token_text_ratio, min_token_text_ratio, inputs_embeds,
+                        min_len, max_len, original_text_len, top_p, tau_r) -> Tuple[dict, float]:
+        """submit()'s argument checks and the prompt: (the scheduler request's fields but the handle and the seed, tau_r)."""
         if (text is None) == (inputs_embeds is None):
             raise ValueError("pass exactly one of text or inputs_embeds")
         if not 1 <= int(sampling) <= MAX_RAS_TOP_K:
@@ -241,11 +327,9 @@ class ContinuousCosyDecoder:
             raise ValueError(f"prompt of shape {tuple(req.embeds.shape)}")
         if not 1 <= req.limit <= self.cap:
             raise ValueError(f"max_len = {req.limit} outside 1..{self.cap} (max_len_cap)")
-        seed = int(fresh_seed() if seed is None else seed) & ((1 << 64) - 1)
-        h = self.sched.submit(embeds=req.embeds, max_new_tokens=req.limit, min_new_tokens=req.n_ignore, do_sample=True,
-                              top_k=int(sampling), top_p=self.top_p if top_p is None else float(top_p), seed=seed)
-        self._extra[h] = self.tau_r if tau_r is None else float(tau_r)
-        return h
+        fields = dict(embeds=req.embeds, max_new_tokens=req.limit, min_new_tokens=req.n_ignore, do_sample=True, top_k=int(sampling),
+                      top_p=self.top_p if top_p is None else float(top_p))
+        return fields, self.tau_r if tau_r is None else float(tau_r)
 
     @torch.no_grad()
     def step(self) -> List[Tuple[int, torch.Tensor]]:
@@ -253,7 +337,7 @@ class ContinuousCosyDecoder:
         rb = self._cycle()
         if rb is None:
             return []
-        return [(self.sched.retire(s).handle, self.seq[s, :int(rb[2, s])].clone()) for s in self._ended(rb)]
+        return [(self._retire(s, int(rb[2, s])), self.seq[s, :int(rb[2, s])].clone()) for s in self._ended(rb)]
 
     @torch.no_grad()
     def run(self) -> Dict[int, torch.Tensor]:
@@ -280,13 +364,20 @@ class ContinuousCosyDecoder:
             idx = torch.tensor(flat, dtype=torch.int64).to(self.device, non_blocking=True)
             pieces = self.seq.view(-1).index_select(0, idx).split([n for _, n in counts])
             for s in sorted(ended):
-                cur.finish(self.sched.retire(s).handle)
+                cur.finish(self._retire(s, int(rb[2, s])))
             for (s, h, _), piece in zip(running, pieces):
                 yield h, piece, s in ended
 
     # ---- internals -----------------------------------------------------------------------------------------------------------
     def _ended(self, rb) -> List[int]:
         return [s for s in sorted(self.sched.busy) if not rb[0, s]]
+
+    def _retire(self, s: int, n: int) -> int:
+        """Slot s is free again: the handle of its request, whose n emitted ids' log-probabilities are kept for take_logprobs()."""
+        h = self.sched.retire(s).handle
+        if self.logprobs:
+            self._lp_done[h] = (self.tok_lp[s, :n].clone(), self.cum_lp[s].clone(), self.end_lp[s].clone())
+        return h
 
     def _cycle(self):
         """Admission, up to check_every replays, and the read-back: host int64 [3, slots] = (live, step, n_out), or None when no
@@ -309,25 +400,54 @@ class ContinuousCosyDecoder:
         if not took:
             return
         m, dev = self.model, self.device
-        slots = [s for s, _ in took]
+        # the requests that prefill: all of them, but for the candidates of a submit_n group after its first, which get a copy of its rows
+        heads = [(s, r) for s, r in took if r.leader is None]
+        slots = [s for s, _ in heads]
         if self.prefill is not None:
-            h_last = self.prefill.run([r.embeds for _, r in took], slots, fresh=True)
+            h_last = self.prefill.run([r.embeds for _, r in heads], slots, fresh=True)
+            logits = m.lm_head(h_last).float()
+            if len(heads) < len(took):
+                logits, slots = self._fan_out(took, heads, logits)
             row_slot = torch.tensor(slots, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
-            return self._admit_draw(took, m.lm_head(h_last).float(), row_slot.long(), row_slot)
+            return self._admit_draw(took, logits, row_slot.long(), row_slot)
         cu = [0]
-        for _, r in took:
+        for _, r in heads:
             cu.append(cu[-1] + r.embeds.shape[0])
         rows64 = torch.tensor(slots, dtype=torch.int64).to(dev, non_blocking=True)
         for st in self.cache.states:   # a fresh state for every admitted request
             st.att_x_prev.index_fill_(0, rows64, 0)
             st.att_kv.index_fill_(0, rows64, 0)
             st.ffn_x_prev.index_fill_(0, rows64, 0)
-        packed = torch.cat([r.embeds for _, r in took], 0).unsqueeze(0)
+        packed = torch.cat([r.embeds for _, r in heads], 0).unsqueeze(0)
         h = m.model(inputs_embeds=packed, cu_seqlens=torch.tensor(cu, dtype=torch.int32), past_key_values=self.cache,
                     cache_rows=torch.tensor(slots)).last_hidden_state
         last = torch.tensor([c - 1 for c in cu[1:]], dtype=torch.int64).to(dev, non_blocking=True)
         logits = m.lm_head(h[0].index_select(0, last)).float()
+        if len(heads) < len(took):
+            logits, slots = self._fan_out(took, heads, logits)
+            rows64 = torch.tensor(slots, dtype=torch.int64).to(dev, non_blocking=True)
         self._admit_draw(took, logits, rows64, torch.tensor(slots, dtype=torch.int32).to(dev, non_blocking=True))
+
+    def _fan_out(self, took, heads, logits):
+        """submit_n: the prefilled rows of the groups' first candidates -> their siblings' rows, every field of every layer, for all
+        groups admitted together in ONE rwkv7_cache_rows_commit_bf16 launch over the cache's own field table (a repeated source row
+        fans out; no row is both read and written: sources are first candidates, destinations are not).  Returns (one logits row per
+        admitted request -- its prompt's, gathered --, every admitted slot in `took` order)."""
+        from .prefill import cache_field_table, cache_rows_commit, check_commit_rows
+        dev, cfg = self.device, self.model.config
+        slot_of = {r.handle: s for s, r in heads}
+        row_of = {r.handle: i for i, (_, r) in enumerate(heads)}
+        sibs = [(slot_of[r.leader], s) for s, r in took if r.leader is not None]
+        src, dst = check_commit_rows([a for a, _ in sibs], [b for _, b in sibs], self.slots, self.slots)
+        if set(src) & set(dst):
+            raise RuntimeError(f"fan-out rows {src} -> {dst}: a row is both read and written")
+        if self._fan_tbl is None:
+            self._fan_tbl = cache_field_table(self.cache)
+        tbl = self._fan_tbl
+        rows = torch.tensor([src, dst], dtype=torch.int32).to(dev, non_blocking=True)
+        cache_rows_commit(tbl, tbl, rows[0], rows[1], len(sibs), len(self.cache), cfg.hidden_size, cfg.num_heads)
+        pick = torch.tensor([row_of[r.handle if r.leader is None else r.leader] for _, r in took], dtype=torch.int64).to(dev, non_blocking=True)
+        return logits.index_select(0, pick), [s for s, _ in took]
 
     def _admit_draw(self, took, logits, rows64, row_slot):
         # the slots' parameters: host mirror -> one copy per field; loop index, emitted count and ring pointer 0, an empty ring and
@@ -347,4 +467,7 @@ class ContinuousCosyDecoder:
         self.ptr.index_fill_(0, rows64, 0)
         self.recent.index_fill_(0, rows64, -1)
         self.live.index_fill_(0, rows64, 1)
-        ras_slots(logits.contiguous(), self.st, row_slot)
+        if self.logprobs:
+            self.cum_lp.index_fill_(0, rows64, 0)
+            self.end_lp.index_fill_(0, rows64, 0)
+        ras_slots(logits.contiguous(), self.st, row_slot, self.lp)

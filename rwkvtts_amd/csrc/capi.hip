@@ -726,16 +726,25 @@ int rwkv7_xy_slots_frame_bf16(int rows, const int *row_slot, const rwkv7_xy_slot
     if (rows <= 0 || !xy_slot_state_ok(st)) return RWKV7_EINVAL;
     return rwkv7::xy_slots_frame_bf16(rows, row_slot, st, (hipStream_t)stream);
 }
+// what rwkv7_ras_slots_f32 and rwkv7_ras_slots_lp_f32 both refuse before a launch
+static bool ras_slots_args_ok(int rows, int V, const float *logits, const rwkv7_ras_slot_state *st) {
+    if (rows <= 0 || V <= 0 || !st || !logits) return false;
+    return !(any_null({(const void *)st->step, (const void *)st->limit, (const void *)st->n_ignore, (const void *)st->seed,
+                       (const void *)st->top_k, (const void *)st->top_p, (const void *)st->tau_r, (const void *)st->live,
+                       (const void *)st->recent, (const void *)st->ptr, (const void *)st->ids, (const void *)st->n_out,
+                       (const void *)st->seq}) ||
+             st->slots <= 0 || st->seq_ld <= 0 || (st->emb && (!st->x || st->D <= 0)));
+}
 int rwkv7_ras_slots_f32(int rows, int V, const float *logits, long ld, const int *row_slot, const rwkv7_ras_slot_state *st,
                         rwkv7_stream_t stream) {
-    if (rows <= 0 || V <= 0 || !st || !logits) return RWKV7_EINVAL;
-    if (any_null({(const void *)st->step, (const void *)st->limit, (const void *)st->n_ignore, (const void *)st->seed,
-                  (const void *)st->top_k, (const void *)st->top_p, (const void *)st->tau_r, (const void *)st->live,
-                  (const void *)st->recent, (const void *)st->ptr, (const void *)st->ids, (const void *)st->n_out,
-                  (const void *)st->seq}) ||
-        st->slots <= 0 || st->seq_ld <= 0 || (st->emb && (!st->x || st->D <= 0)))
-        return RWKV7_EINVAL;
+    if (!ras_slots_args_ok(rows, V, logits, st)) return RWKV7_EINVAL;
     return rwkv7::ras_slots_f32(rows, V, logits, ld, row_slot, st, (hipStream_t)stream);
+}
+int rwkv7_ras_slots_lp_f32(int rows, int V, const float *logits, long ld, const int *row_slot, const rwkv7_ras_slot_state *st,
+                           const rwkv7_ras_slot_logprob *lp, rwkv7_stream_t stream) {
+    if (!ras_slots_args_ok(rows, V, logits, st)) return RWKV7_EINVAL;
+    if (!lp || !lp->tok_lp || !lp->cum_lp || !lp->end_lp) return RWKV7_EINVAL;
+    return rwkv7::ras_slots_lp_f32(rows, V, logits, ld, row_slot, st, lp->tok_lp, lp->cum_lp, lp->end_lp, (hipStream_t)stream);
 }
 int rwkv7_debug_tr16(const void *in, const int *addr, void *out, rwkv7_stream_t stream) {
     if (!in || !addr || !out) return RWKV7_EINVAL;

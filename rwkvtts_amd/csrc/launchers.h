@@ -181,6 +181,8 @@ int xy_slots_draw_f32(int rows, const float *logits, long ld, const int *row_slo
                       const int *allow_lo, const int *allow_hi, int max_domain, const void *st, hipStream_t stream);
 int xy_slots_frame_bf16(int rows, const int *row_slot, const void *st, hipStream_t stream);
 int ras_slots_f32(int rows, int V, const float *logits, long ld, const int *row_slot, const void *st, hipStream_t stream);
+int ras_slots_lp_f32(int rows, int V, const float *logits, long ld, const int *row_slot, const void *st, float *tok_lp, double *cum_lp,
+                     float *end_lp, hipStream_t stream);
 
 // ---- decode step (decode_step.hip: B <= 32; decode_step_wide.hip: 32 < B <= 128).  layer_tbl: device table of decode_layer_ptrs()
 //      pointers per layer, layer_tbl_host its host copy or NULL; head_b may be NULL.  RWKV7_ESHAPE (workspace size 0) for shapes

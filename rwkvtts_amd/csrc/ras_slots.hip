@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "launchers.h"
 #include "sampling_common.h"
 
@@ -30,12 +32,26 @@ struct RasSlotState {
     long eos;
 };
 
+// = rwkv7_ras_slot_state followed by the members of rwkv7_ras_slot_logprob: what the LP instantiation gets
+struct RasSlotStateLp : RasSlotState {
+    float *tok_lp;    // [slots][seq_ld]
+    double *cum_lp;   // [slots]
+    float *end_lp;    // [slots]
+};
+
 // The body repeats ras_step_kernel's draw statement for statement, with the slot's fields in place of the launch's arguments, so
 // that the id equals that kernel's bit for bit and csrc/sampling.hip stays as it is.  Every lane reads live[s], step[s] and the
 // ring before the first barrier; lane 0 writes them after the last one, so the early exit is uniform over the workgroup.
-template <int EPT>
+//
+// LP (rwkv7_ras_slots_lp_f32): the log-probability of the drawn id as well.  Everything under `if constexpr (LP)` is extra; with
+// LP = false the body is the draw as it always was.  The probability is the one of the RAW logits (temperature 1, before top-k /
+// top-p and the repetition test): the draw already holds the row's maximum mx and z = sum exp(x - mx) in registers.  While EOS is
+// barred it cannot be drawn, so it is left out of the sum: the masked terms are added up on their own (per thread, wave butterfly,
+// the four waves in fixed order, as z is), never as z - exp(x[eos] - mx), which cancels when EOS holds the row's mass.
+template <int EPT, bool LP>
 __global__ __launch_bounds__(kSmpThreads) void ras_slots_kernel(int V, const float *__restrict__ logits_, long ld,
-                                                                const int *__restrict__ row_slot, RasSlotState a) {
+                                                                const int *__restrict__ row_slot,
+                                                                typename std::conditional<LP, RasSlotStateLp, RasSlotState>::type a) {
     __shared__ SmpShared sm;
     const int tid = threadIdx.x;
     const int s = row_slot ? row_slot[blockIdx.x] : (int)blockIdx.x;
@@ -66,6 +82,15 @@ __global__ __launch_bounds__(kSmpThreads) void ras_slots_kernel(int V, const flo
 #pragma unroll
     for (int e = 0; e < EPT; e++) zs += __expf(x.v[e] - mx);
     const float z = block_sum(zs, sm);
+    float lp_z = z;   // LP: the exp-sum over the ids this draw can produce
+    if constexpr (LP) {
+        if (ignore_eos) {   // uniform over the workgroup
+            float ws = 0.f;
+#pragma unroll
+            for (int e = 0; e < EPT; e++) ws += tid + kSmpThreads * e == eos ? 0.f : __expf(x.v[e] - mx);
+            lp_z = block_sum(ws, sm);
+        }
+    }
     int full, alt;
     draw_full(x, sm, mx, ignore_eos ? eos : -1, u01(r.x), u01(r.y), full, alt);
     if (full < 0) full = imx;
@@ -112,6 +137,17 @@ __global__ __launch_bounds__(kSmpThreads) void ras_slots_kernel(int V, const flo
         }
         a.step[s] = st + 1;
         a.live[s] = emit && st + 1 < a.limit[s];
+        if constexpr (LP) {
+            // no finite logit in the row, or none with any mass next to a barred EOS (the id is a fall-back): -inf, not a NaN
+            const float lp = mx == -INFINITY || !(lp_z > 0.f) ? -INFINITY : (logits[id] - mx) - __logf(lp_z);
+            if (emit) {
+                const long n = a.n_out[s] - 1;   // the column seq got above
+                if (n >= 0 && n < a.seq_ld) a.tok_lp[(long)s * a.seq_ld + n] = lp;
+                a.cum_lp[s] += (double)lp;   // one workgroup owns the slot: a plain read, add, store
+            } else {
+                a.end_lp[s] = lp;
+            }
+        }
     }
     if (emit && a.emb) {
         const uint16_t *src = a.emb + id * a.D;
@@ -122,20 +158,34 @@ __global__ __launch_bounds__(kSmpThreads) void ras_slots_kernel(int V, const flo
 
 }  // namespace
 
-int ras_slots_f32(int rows, int V, const float *logits, long ld, const int *row_slot, const void *st_, hipStream_t stream) {
-    const RasSlotState st = *(const RasSlotState *)st_;
+template <bool LP, typename State>
+static int launch_ras_slots(int rows, int V, const float *logits, long ld, const int *row_slot, const State &st, hipStream_t stream) {
     if (V > kSmpMaxN || st.win_size < 1 || st.win_size > 128 || st.win_size > st.win_ld || st.top_k_max < 1 || st.top_k_max > kSmpMaxCand ||
         (st.emb && st.D % 8 != 0))
         return -4;   // RWKV7_ESHAPE
     (void)hipGetLastError();
     const dim3 grid(rows), block(kSmpThreads);
     if (V <= kEptS * kSmpThreads)
-        ras_slots_kernel<kEptS><<<grid, block, 0, stream>>>(V, logits, ld, row_slot, st);
+        ras_slots_kernel<kEptS, LP><<<grid, block, 0, stream>>>(V, logits, ld, row_slot, st);
     else if (V <= kEptM * kSmpThreads)
-        ras_slots_kernel<kEptM><<<grid, block, 0, stream>>>(V, logits, ld, row_slot, st);
+        ras_slots_kernel<kEptM, LP><<<grid, block, 0, stream>>>(V, logits, ld, row_slot, st);
     else
-        ras_slots_kernel<kEptL><<<grid, block, 0, stream>>>(V, logits, ld, row_slot, st);
+        ras_slots_kernel<kEptL, LP><<<grid, block, 0, stream>>>(V, logits, ld, row_slot, st);
     return (int)hipGetLastError();
+}
+
+int ras_slots_f32(int rows, int V, const float *logits, long ld, const int *row_slot, const void *st_, hipStream_t stream) {
+    return launch_ras_slots<false>(rows, V, logits, ld, row_slot, *(const RasSlotState *)st_, stream);
+}
+
+int ras_slots_lp_f32(int rows, int V, const float *logits, long ld, const int *row_slot, const void *st_, float *tok_lp, double *cum_lp,
+                     float *end_lp, hipStream_t stream) {
+    RasSlotStateLp st;
+    static_cast<RasSlotState &>(st) = *(const RasSlotState *)st_;
+    st.tok_lp = tok_lp;
+    st.cum_lp = cum_lp;
+    st.end_lp = end_lp;
+    return launch_ras_slots<true>(rows, V, logits, ld, row_slot, st, stream);
 }
 
 }  // namespace rwkv7
