@@ -46,6 +46,78 @@ def _hip_gate(x, labels, *more):
             and all(m is None or (m.is_cuda and m.dtype == torch.bfloat16) for m in more))
 
 
+# ---- what every head shares: the chunk walk, the reused logits buffer, the gradient accumulator --------------------------------------
+def _chunk_plan(N, V, esize, hip, chunk, align=1, overlap_last=False):
+    """The walk of every head over N rows: (rows per chunk, [(s, rows, skip) of every chunk]) -- the chunk is rows s .. s + rows - 1,
+    of which the first `skip` belong to its predecessor already.  chunk: rows per round (None: EVAL_CHUNK_ROWS if set, else
+    auto_chunk).  On the HIP route it is rounded up to a multiple of `align`, and with overlap_last a shorter last chunk is taken as
+    the LAST `chunk` rows, so that every GEMM call has `chunk` rows: skip is non-zero for that chunk alone."""
+    if chunk is None:
+        # torch route: fp32 logits and one fp32 temporary of that size
+        chunk = EVAL_CHUNK_ROWS or auto_chunk(N, V, esize if hip else 8)
+    if hip:
+        chunk = -(-max(1, chunk) // align) * align
+    chunk = max(1, min(chunk, N))
+    starts = list(range(0, N, chunk))
+    if hip and overlap_last:
+        starts[-1] = N - chunk   # N rows when one chunk holds them all
+    walk, done = [], 0
+    for s in starts:
+        rows = min(chunk, N - s)
+        walk.append((s, rows, done - s))
+        done = s + rows
+    return chunk, walk
+
+
+def _logits_buffer(chunk, weight):
+    """(buf, wt) of the routes that keep ONE bf16 logits buffer for all chunks: buf [chunk, ld], ld = V rounded up to 16-byte rows."""
+    return torch.empty(chunk, -(-weight.shape[0] // 8) * 8, dtype=weight.dtype, device=weight.device), weight.t()
+
+
+def _fill_logits(buf, h, wt, bias):
+    """F.linear(h, wt.t(), bias) into the first rows of buf: the GEMM writes the V logits of a row, nothing reads the rest of it."""
+    logits = buf[:h.shape[0], :wt.shape[1]]
+    if bias is None:
+        torch.mm(h, wt, out=logits)
+    else:
+        torch.addmm(bias, h, wt, out=logits)
+    return logits
+
+
+class _HeadGrads:
+    """dh, dw and db of a head (each None where needs_input_grad says so), accumulated chunk by chunk from pd = d loss / d logits.
+    What the three nodes keep apart, because another leading dimension or output type can make the library take another GEMM kernel,
+    with other bits and another speed:
+      _FusedLinearCE         : logits by F.linear into a fresh tensor per chunk (padded head: rwkv7_gemm_nt_bf16 into a fresh
+                               [rows, Vp], `weight` here the zero-padded [Vp, D] copy, dw[:V] taken at the end); bf16 GEMMs
+      _FusedLinearKLAcc      : logits by F.linear; fp32 GEMMs (fp32=True: dh is an fp32 buffer, no bf16 rounding of a chunk's dw)
+      _FusedLinearSeqLogprob : logits in the reused [chunk, ld] buffer (_logits_buffer, overlapping last chunk); bf16 GEMMs"""
+
+    def __init__(self, need, hidden, weight, bias, fp32=False):
+        self.weight, self.fp32 = weight, fp32
+        self.dh = torch.empty_like(hidden, dtype=torch.float32 if fp32 else hidden.dtype) if need[0] else None
+        self.dw = torch.zeros_like(weight, dtype=torch.float32) if need[1] else None
+        self.db = torch.zeros_like(bias, dtype=torch.float32) if (bias is not None and need[2]) else None
+
+    def add(self, pd, h, lo, hi, p32=None):
+        """Rows lo .. hi - 1: pd [hi - lo, V] and their hidden states h.  p32: the fp32 rows pd was rounded from, where the caller has
+        them (the torch routes): db sums those."""
+        if self.dh is not None:
+            self.dh[lo:hi] = torch.mm(pd, self.weight, out_dtype=torch.float32) if self.fp32 else pd @ self.weight
+        if self.dw is not None:
+            self.dw += torch.mm(pd.t(), h, out_dtype=torch.float32) if self.fp32 else (pd.t() @ h).float()
+        if self.db is not None:
+            self.db += pd.sum(0, dtype=torch.float32) if p32 is None else p32.sum(0)
+
+    @staticmethod
+    def scaled(dh, dw, db, g, hdtype, wdtype):
+        """The backward triple: scaled in fp32 and rounded once -- rounding the scalar to bf16 first would put a systematic error of
+        up to 2^-9 on every hidden-state gradient relative to the (fp32-scaled) head-weight gradient."""
+        return ((dh.float() * g).to(hdtype) if dh is not None else None,
+                (dw * g).to(wdtype) if dw is not None else None,
+                (db * g).to(wdtype) if db is not None else None)
+
+
 class _FusedLinearCE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, hidden, weight, bias, labels, ignore_index, chunk, label_smoothing):
@@ -55,9 +127,6 @@ class _FusedLinearCE(torch.autograd.Function):
         inv = 1.0 / n_valid.float()
         loss = torch.zeros((), dtype=torch.float32, device=hidden.device)
         need = ctx.needs_input_grad
-        dh = torch.empty_like(hidden) if need[0] else None
-        dw = None   # allocated below (the padded head accumulates into its own [Vp, D] buffer)
-        db = torch.zeros_like(bias, dtype=torch.float32) if (bias is not None and need[2]) else None
         # bias and label smoothing (the XY heads, xy_llm.py:233-240) ride on the same kernel since round 4: at configs[3] the torch
         # chain behind them (fp32 logits, logsumexp, softmax, scatter, casts) was ~40 ms of a 417 ms step
         # NUMERICS of the HIP path (also for the XY heads since round 4): the logits are the bf16 output of the head GEMM -- logsumexp,
@@ -76,38 +145,25 @@ class _FusedLinearCE(torch.autograd.Function):
         Vp = -(-V // 256) * 256
         padded = (hip_ce and PADDED_HEAD and bias is None and Vp != V and D % 1024 == 0 and N % 256 == 0 and chunk % 256 == 0
                   and hidden.is_contiguous())
-        if need[1] and not padded:
-            dw = torch.zeros_like(weight, dtype=torch.float32)
         if padded:
             w_pad = torch.zeros(Vp, D, dtype=weight.dtype, device=weight.device)
             w_pad[:V].copy_(weight)
-            dw_pad = torch.zeros(Vp, D, dtype=torch.float32, device=weight.device) if need[1] else None
             PADDED_HEAD_HITS[0] += 1
-        for s in range(0, N, chunk):
-            h = hidden[s:s + chunk]
-            lab = labels[s:s + chunk]
+        grads = _HeadGrads(need, hidden, w_pad if padded else weight, bias)   # padded: dw is [Vp, D] until the end
+        for s, rows, _ in _chunk_plan(N, V, hidden.element_size(), hip_ce, chunk)[1]:
+            h, lab = hidden[s:s + rows], labels[s:s + rows]
             if hip_ce:
                 # bf16 logits straight from the GEMM; one kernel turns them into per-row losses and d loss / d logits
-                rows = h.shape[0]
                 if padded:
                     pd = torch.empty(rows, Vp, dtype=h.dtype, device=h.device)
                     _lib.call("rwkv7_gemm_nt_bf16", h, rows, Vp, D, h, w_pad, pd, 0)
                 else:
                     pd = F.linear(h, weight, bias)   # bf16 logits as nn.Linear gives them (the bias inside the GEMM's fp32 epilogue)
                 loss_rows = torch.empty(rows, dtype=torch.float32, device=pd.device)
-                lab_c = lab.contiguous()
-                _lib.call("rwkv7_ce_fwd_bwd_ld_bf16", pd, rows, V, pd.shape[1], pd, lab_c, ignore_index, 1.0, loss_rows,
+                _lib.call("rwkv7_ce_fwd_bwd_ld_bf16", pd, rows, V, pd.shape[1], pd, lab.contiguous(), ignore_index, 1.0, loss_rows,
                           float(label_smoothing))
                 loss += loss_rows.sum()
-                if need[0]:
-                    dh[s:s + chunk] = pd @ (w_pad if padded else weight)
-                if need[1]:
-                    if padded:
-                        dw_pad += (pd.t() @ h).float()
-                    else:
-                        dw += (pd.t() @ h).float()
-                if db is not None:
-                    db += pd.sum(0, dtype=torch.float32)
+                grads.add(pd, h, s, s + rows)
                 continue
             logits = (h @ weight.t()).float()
             if bias is not None:
@@ -124,26 +180,12 @@ class _FusedLinearCE(torch.autograd.Function):
                 per = nll
             loss += (per * vmask).sum()
             if need[0] or need[1]:
-                p = torch.softmax(logits, dim=-1)
-                if label_smoothing > 0:
-                    p = p - label_smoothing / logits.shape[-1]
-                    p.scatter_add_(1, safe.unsqueeze(1), torch.full_like(tgt, -(1 - label_smoothing)).unsqueeze(1))
-                else:
-                    p.scatter_add_(1, safe.unsqueeze(1), torch.full_like(tgt, -1.0).unsqueeze(1))
-                p = p * (vmask.unsqueeze(1) * inv)
-                pd = p.to(hidden.dtype)
-                if need[0]:
-                    dh[s:s + chunk] = pd @ weight
-                if need[1]:
-                    dw += (pd.t() @ h).float()
-                if db is not None:
-                    db += p.sum(0)
+                p = _grad_rows_torch(logits, lab, label_smoothing, vmask * inv)
+                grads.add(p.to(hidden.dtype), h, s, s + rows, p)
         # the HIP path leaves dh / dw unscaled (scale = 1 in the kernel: 1/n_valid lives on the device); backward folds
         # 1/n_valid into the incoming gradient
-        if padded and need[1]:
-            dw = dw_pad[:V]
-        ctx.save_for_backward(dh, dw, db, inv if hip_ce else None)
-        ctx.wdtype = weight.dtype
+        ctx.save_for_backward(grads.dh, grads.dw[:V] if need[1] else None, grads.db, inv if hip_ce else None)
+        ctx.hdtype, ctx.wdtype = hidden.dtype, weight.dtype
         return loss * inv
 
     @staticmethod
@@ -151,11 +193,7 @@ class _FusedLinearCE(torch.autograd.Function):
         dh, dw, db, post = ctx.saved_tensors
         if post is not None:
             g = g * post
-        # scale in fp32 and round once: rounding the scalar to bf16 first would put a systematic error of up to 2^-9 on
-        # every hidden-state gradient relative to the (fp32-scaled) head-weight gradient
-        return ((dh.float() * g).to(dh.dtype) if dh is not None else None,
-                (dw * g).to(ctx.wdtype) if dw is not None else None,
-                (db * g).to(ctx.wdtype) if db is not None else None, None, None, None, None)
+        return _HeadGrads.scaled(dh, dw, db, g, ctx.hdtype, ctx.wdtype) + (None, None, None, None)
 
 
 LOGITS_CHUNK_BYTES = int(os.environ.get("RWKV7_CE_CHUNK_BYTES", str(1 << 30)))
@@ -246,23 +284,17 @@ class _FusedLinearKLAcc(torch.autograd.Function):
         need = ctx.needs_input_grad
         loss = torch.zeros((), dtype=torch.float32, device=hidden.device)
         ncorrect = torch.zeros((), dtype=torch.int64, device=hidden.device)
-        dh = torch.empty_like(hidden, dtype=torch.float32) if need[0] else None   # 4 N D bytes: small next to a chunk's [rows, V]
-        dw = torch.zeros_like(weight, dtype=torch.float32) if need[1] else None
-        db = torch.zeros_like(bias, dtype=torch.float32) if (bias is not None and need[2]) else None
-        for s in range(0, N, chunk):
-            h = hidden[s:s + chunk]
+        # fp32 out of the GEMMs: dh (4 N D bytes: small next to a chunk's [rows, V]) is rounded after the scale
+        grads = _HeadGrads(need, hidden, weight, bias, fp32=True)
+        for s, rows, _ in _chunk_plan(N, V, hidden.element_size(), True, chunk)[1]:
+            h = hidden[s:s + rows]
             pd = F.linear(h, weight, bias)   # bf16 logits as nn.Linear gives them
-            loss_rows, correct = _kl_acc_rows(pd, pd, labels[s:s + chunk], V, ignore_index, smoothing, scale)
+            loss_rows, correct = _kl_acc_rows(pd, pd, labels[s:s + rows], V, ignore_index, smoothing, scale)
             loss += loss_rows.sum()
             ncorrect += correct.sum()
-            if need[0]:
-                dh[s:s + chunk] = torch.mm(pd, weight, out_dtype=torch.float32)   # fp32 out of the GEMM: rounded after the scale
-            if need[1]:
-                dw += torch.mm(pd.t(), h, out_dtype=torch.float32)   # ... and no bf16 rounding of a chunk's partial sum
-            if db is not None:
-                db += pd.sum(0, dtype=torch.float32)
+            grads.add(pd, h, s, s + rows)
         denom = total if normalize_length else batch_size
-        ctx.save_for_backward(dh, dw, db, total)
+        ctx.save_for_backward(grads.dh, grads.dw, grads.db, total)
         ctx.on_device, ctx.wdtype, ctx.hdtype = host_denom is None, weight.dtype, hidden.dtype
         acc = ncorrect / total
         ctx.mark_non_differentiable(acc)
@@ -272,9 +304,7 @@ class _FusedLinearKLAcc(torch.autograd.Function):
     def backward(ctx, g, _gacc):
         dh, dw, db, total = ctx.saved_tensors
         g = g.float() / total if ctx.on_device else g.float()
-        return ((dh * g).to(ctx.hdtype) if dh is not None else None,   # fp32 buffers: scaled in fp32, rounded once
-                (dw * g).to(ctx.wdtype) if dw is not None else None,
-                (db * g).to(ctx.wdtype) if db is not None else None, None, None, None, None, None, None, None)
+        return _HeadGrads.scaled(dh, dw, db, g, ctx.hdtype, ctx.wdtype) + (None,) * 7
 
 
 def fused_linear_kl_accuracy(hidden, labels, weight, bias, batch_size, smoothing, normalize_length, ignore_index=-1, chunk=None,
@@ -386,18 +416,14 @@ def _eval_rows_torch(logits, labels, ignore_index, kind, smoothing):
     return per.masked_fill(~valid, 0.0), correct
 
 
-def _chunk_plan(N, V, esize, hip, chunk, align=1, overlap_last=False):
-    """(rows per chunk, first row of every chunk) of _eval_chunks' walk over N rows (see there)."""
-    if chunk is None:
-        # torch route: fp32 logits and one fp32 temporary of that size
-        chunk = EVAL_CHUNK_ROWS or auto_chunk(N, V, esize if hip else 8)
-    if hip:
-        chunk = -(-max(1, chunk) // align) * align
-    chunk = max(1, min(chunk, N))
-    starts = list(range(0, N, chunk))
-    if hip and overlap_last:
-        starts[-1] = N - chunk   # N rows when one chunk holds them all
-    return chunk, starts
+def _grad_rows_torch(logits, labels, smoothing, row_scale):
+    """d (row loss) / d logits of the cross-entropy with label smoothing in torch, fp32 [rows, V] from fp32 logits: (softmax - smoothed
+    one-hot) * row_scale[row]; row_scale fp32 [rows] carries the upstream scale and the 0 of an ignored row."""
+    p = torch.softmax(logits, dim=-1)
+    if smoothing > 0:
+        p = p - smoothing / logits.shape[-1]
+    p.scatter_add_(1, labels.clamp(min=0).unsqueeze(1), torch.full_like(p[:, :1], -(1 - smoothing)))
+    return p * row_scale.unsqueeze(1)
 
 
 def _eval_chunks(hidden, labels, weight, bias, ignore_index, kind, smoothing, chunk, *, align=1, overlap_last=False, out=None):
@@ -405,8 +431,7 @@ def _eval_chunks(hidden, labels, weight, bias, ignore_index, kind, smoothing, ch
     F.linear(hidden, weight, bias) for one chunk of rows after the other; hip: which route the call takes.
     HIP route (_hip_gate): the head GEMM into ONE reused bf16 buffer of [chunk, ld] logits (ld = V rounded up to 16-byte rows), then
     rwkv7_head_eval_bf16 on it (correct_rows int32).  Anything else: _eval_rows_torch of the chunk's logits (correct_rows bool).
-    chunk: rows per round (None: EVAL_CHUNK_ROWS if set, else auto_chunk).  On the HIP route it is rounded up to a multiple of `align`,
-    and with overlap_last a shorter last chunk is taken as the LAST `chunk` rows, so that every GEMM call has `chunk` rows.
+    chunk, align, overlap_last: the walk (_chunk_plan).
     out: None -- on the HIP route the yielded rows live in chunk-sized buffers that the next round overwrites; or full-length
     (loss_rows fp32 [N], correct_rows int32 [N]), which every round fills at its rows' positions (the kernel writes there directly)."""
     if kind not in (EVAL_CE, EVAL_KL) or not 0 <= smoothing < 1:
@@ -415,28 +440,22 @@ def _eval_chunks(hidden, labels, weight, bias, ignore_index, kind, smoothing, ch
     h2, lab = hidden.reshape(-1, D), labels.reshape(-1)
     N, dev = h2.shape[0], h2.device
     hip = _hip_gate(h2, lab, weight, bias)
-    chunk, starts = _chunk_plan(N, V, h2.element_size(), hip, chunk, align, overlap_last)
+    chunk, walk = _chunk_plan(N, V, h2.element_size(), hip, chunk, align, overlap_last)
     whole = out is not None
     if hip:
         _check_labels(lab, V, ignore_index)
-        ld = -(-V // 8) * 8
-        buf = torch.empty(chunk, ld, dtype=h2.dtype, device=dev)
+        buf, wt = _logits_buffer(chunk, weight)
         if not whole:
             out = (torch.empty(chunk, dtype=torch.float32, device=dev), torch.empty(chunk, dtype=torch.int32, device=dev))
         lab = lab.contiguous()
-        wt = weight.t()
-    for s in starts:
-        h, lb = h2[s:s + chunk], lab[s:s + chunk]
-        rows = h.shape[0]
+    for s, rows, _ in walk:
+        h, lb = h2[s:s + rows], lab[s:s + rows]
         if hip:
             o = s if whole else 0
             per, ok = out[0][o:o + rows], out[1][o:o + rows]
-            logits = buf[:rows, :V]   # rows of ld elements: the GEMM writes the V logits, the kernel never reads the rest
-            if bias is None:
-                torch.mm(h, wt, out=logits)
-            else:
-                torch.addmm(bias, h, wt, out=logits)
-            _lib.call("rwkv7_head_eval_bf16", buf, rows, V, ld, buf, lb, ignore_index, kind, float(smoothing), per, ok, None)
+            _fill_logits(buf, h, wt, bias)
+            _lib.call("rwkv7_head_eval_bf16", buf, rows, V, buf.stride(0), buf, lb, ignore_index, kind, float(smoothing), per, ok,
+                      None)
             EVAL_HITS[0] += 1
         else:
             per, ok = _eval_rows_torch(F.linear(h, weight, bias), lb, ignore_index, kind, smoothing)
@@ -589,49 +608,27 @@ class _FusedLinearSeqLogprob(torch.autograd.Function):
     def backward(ctx, g):
         hidden, weight, bias, lab, st = ctx.saved_tensors
         need, hip, ignore_index = ctx.needs_input_grad, ctx.hip, ctx.ignore_index
-        (N, D), V, dev = hidden.shape, weight.shape[0], hidden.device
+        N, V = hidden.shape[0], weight.shape[0]
         n_seq = st.numel() - 1
         seq_scale = (-g).float().contiguous()   # d(-loss_sum[s]) / d(row loss) = -1: the kernel's gradient is the loss's
-        dh = torch.empty_like(hidden) if need[0] else None
-        dw = torch.zeros_like(weight, dtype=torch.float32) if need[1] else None
-        db = torch.zeros_like(bias, dtype=torch.float32) if (bias is not None and need[2]) else None
-        chunk, starts = _chunk_plan(N, V, hidden.element_size(), hip, ctx.chunk, SCORE_CHUNK_ALIGN, True)
+        grads = _HeadGrads(need, hidden, weight, bias)
+        chunk, walk = _chunk_plan(N, V, hidden.element_size(), hip, ctx.chunk, SCORE_CHUNK_ALIGN, True)
         if hip:
-            ld = -(-V // 8) * 8
-            buf = torch.empty(chunk, ld, dtype=hidden.dtype, device=dev)
-            wt = weight.t()
-        done = 0   # rows [0, done) have their gradients: an overlapping last chunk contributes its remaining rows only
-        for s in starts:
-            h = hidden[s:s + chunk]
-            rows, skip = h.shape[0], done - s
+            buf, wt = _logits_buffer(chunk, weight)
+        for s, rows, skip in walk:   # an overlapping last chunk contributes the rows behind its first `skip` only
+            h, lo = hidden[s:s + rows], s + skip
             if hip:
-                logits = buf[:rows, :V]
-                if bias is None:
-                    torch.mm(h, wt, out=logits)
-                else:
-                    torch.addmm(bias, h, wt, out=logits)
-                _lib.call("rwkv7_ce_seq_bwd_bf16", buf, rows - skip, V, ld, buf[skip:], lab[done:], ignore_index, done, n_seq, st,
-                          seq_scale, None)
+                logits = _fill_logits(buf, h, wt, bias)
+                _lib.call("rwkv7_ce_seq_bwd_bf16", buf, rows - skip, V, buf.stride(0), buf[skip:], lab[lo:], ignore_index, lo, n_seq,
+                          st, seq_scale, None)
                 SEQLP_HITS[0] += 1
-                pd = logits[skip:]
-                col = pd.sum(0, dtype=torch.float32) if db is not None else None
+                grads.add(logits[skip:], h[skip:], lo, s + rows)
             else:
-                x = F.linear(h, weight, bias).float()
                 lb = lab[s:s + rows]
-                p = torch.softmax(x, dim=1)
-                p.scatter_add_(1, lb.clamp(min=0).unsqueeze(1), torch.full_like(p[:, :1], -1.0))
-                p = p * (_row_scales(st, seq_scale, s, rows) * (lb != ignore_index)).unsqueeze(1)
-                pd = p.to(hidden.dtype)
-                col = p.sum(0) if db is not None else None
-            h = h[skip:]
-            if need[0]:
-                dh[done:s + rows] = pd @ weight
-            if need[1]:
-                dw += (pd.t() @ h).float()
-            if db is not None:
-                db += col
-            done = s + rows
-        return (dh, dw.to(weight.dtype) if dw is not None else None, db.to(bias.dtype) if db is not None else None,
+                p = _grad_rows_torch(F.linear(h, weight, bias).float(), lb, 0.0,
+                                     _row_scales(st, seq_scale, s, rows) * (lb != ignore_index))
+                grads.add(p.to(hidden.dtype), h, s, s + rows, p)
+        return (grads.dh, grads.dw.to(weight.dtype) if need[1] else None, grads.db.to(bias.dtype) if grads.db is not None else None,
                 None, None, None, None, None)
 
 
