@@ -944,6 +944,42 @@ typedef struct rwkv7_xy_slot_state {
 int rwkv7_xy_slots_draw_f32(int rows, const float *logits, long ld, const int *row_slot, const int *seg_off, const int *seg_len,
                             const int *allow_lo, const int *allow_hi, int max_domain, const rwkv7_xy_slot_state *st, rwkv7_stream_t stream);
 int rwkv7_xy_slots_frame_bf16(int rows, const int *row_slot, const rwkv7_xy_slot_state *st, rwkv7_stream_t stream);
+/* rwkv7_xy_slots_draw_lp_f32 / rwkv7_xy_slots_frame_lp_bf16: the two entries above, which also report the log-probability of what a
+ * frame drew (ContinuousXYDecoder(logprobs=True): ranking n candidates of one prompt without a second pass).  A frame is the two LP
+ * calls in this order on one stream, with the same st and lp.  For a live slot every field of `st` -- nt; seq, row, x, step, needs,
+ * live -- is written bit for bit as the plain entries write it.
+ * rwkv7_xy_slots_draw_lp_f32 writes in addition, for every channel c it draws,
+ *   ch_lp[s][c] = (x[id] - m) - log sum_j exp(x[j] - m)        (m = the maximum over j)
+ * with x the RAW fp32 logits of channel c -- temperature 1, before top-k / top-p -- and j over the ids [allow_lo[c], allow_hi[c]).  A
+ * channel whose allowed logits are all -INFINITY gives -INFINITY, not NaN.  Where the plain entry writes no nt[s][c] (slot not live,
+ * row without a slot, empty range), ch_lp[s][c] is left as it is.  The reductions run thread -> wave -> workgroup in a fixed order:
+ * the same logits and slot parameters give the same bits whatever row, slot or grid they are drawn in.
+ * rwkv7_xy_slots_frame_lp_bf16 decides which of the C draws COUNT -- the frame rules may replace a drawn id by a forced one -- from the
+ * slot's state alone, never by comparing ids (a drawn id that happens to equal the pad id is not misjudged):
+ *   channel 0 counts iff needs[s] < 0 on entry: the flush had not started before this frame, so the drawn id was the model's free
+ *             choice -- also on the frame that starts the flush, where eos0 is written in its place;
+ *   channel i >= 1 counts iff the frame keeps its drawn id: not (flushing and needs < C - i), with `needs` as the frame rule sees it
+ *             (after a flush start set it to C - 1, before the decrement).
+ * With pw = the row of seq the frame is written to (step[s] on entry, clamped to [0, seq_ld - 1]):
+ *   frame_lp[s][pw][c] = ch_lp[s][c] for a counted channel, +0.0f for a forced one
+ *   cum_lp[s]         += the counted values in channel order 0 .. C-1, each converted to double and added on its own (plain read,
+ *                        add, store: one workgroup owns a slot)
+ *   n_lp[s]           += the number of counted channels (the length for a per-draw mean)
+ * A slot that is not live, and a row whose slot is outside [0, slots), leave all four arrays untouched.  Errors: those of the plain
+ * entries, and RWKV7_EINVAL for a null lp or a null member of it (one struct serves both calls: either entry wants all four);
+ * nothing is launched then.  (A struct plus a typedef, like rwkv7_slot_logprob; the Python mirror is continuous_xy.XYSlotLogprob.) */
+struct rwkv7_xy_slot_logprob {
+    float *ch_lp;               /* [slots][C]: log-probability of every channel's drawn id of the current frame (draw -> frame) */
+    float *frame_lp;            /* [slots][seq_ld][C]: per emitted frame, the counted channels' values; +0 where the id was forced */
+    double *cum_lp;             /* [slots]: running fp64 sum of the counted values, in (frame, channel) order */
+    long *n_lp;                 /* [slots]: number of counted values so far */
+};
+typedef struct rwkv7_xy_slot_logprob rwkv7_xy_slot_logprob;
+int rwkv7_xy_slots_draw_lp_f32(int rows, const float *logits, long ld, const int *row_slot, const int *seg_off, const int *seg_len,
+                               const int *allow_lo, const int *allow_hi, int max_domain, const rwkv7_xy_slot_state *st,
+                               const rwkv7_xy_slot_logprob *lp, rwkv7_stream_t stream);
+int rwkv7_xy_slots_frame_lp_bf16(int rows, const int *row_slot, const rwkv7_xy_slot_state *st, const rwkv7_xy_slot_logprob *lp,
+                                 rwkv7_stream_t stream);
 
 /* ---- CosyVoice's repetition-aware draw per SLOT of a continuous-batching engine (csrc/ras_slots.hip; rwkvtts_amd/continuous_cosy.py),
  * where every slot runs its own utterance.  Logits row r (fp32, V ids, row stride ld) belongs to slot s = row_slot[r] (row_slot NULL:

@@ -222,6 +222,25 @@ class GroupScheduler(SlotScheduler):
         return out
 
 
+def fan_out_rows(cache, tbl, n_rows, cfg, device, took, heads, logits):
+    """submit_n in every engine: the prefilled rows of the groups' first candidates (`heads`, the requests of `took` without a
+    leader) -> their siblings' rows of `cache` (n_rows rows), every field of every layer, for all groups admitted together in ONE
+    rwkv7_cache_rows_commit_bf16 launch over the cache's own field table `tbl` (prefill.cache_field_table; a repeated source row fans
+    out; no row is both read and written: sources are first candidates, destinations are not).  Returns (one logits row per admitted
+    request -- its prompt's, gathered --, every admitted slot in `took` order)."""
+    from .prefill import cache_rows_commit, check_commit_rows
+    slot_of = {r.handle: s for s, r in heads}
+    row_of = {r.handle: i for i, (_, r) in enumerate(heads)}
+    sibs = [(slot_of[r.leader], s) for s, r in took if r.leader is not None]
+    src, dst = check_commit_rows([a for a, _ in sibs], [b for _, b in sibs], n_rows, n_rows)
+    if set(src) & set(dst):
+        raise RuntimeError(f"fan-out rows {src} -> {dst}: a row is both read and written")
+    rows = torch.tensor([src, dst], dtype=torch.int32).to(device, non_blocking=True)
+    cache_rows_commit(tbl, tbl, rows[0], rows[1], len(sibs), len(cache), cfg.hidden_size, cfg.num_heads)
+    pick = torch.tensor([row_of[r.handle if r.leader is None else r.leader] for _, r in took], dtype=torch.int64).to(device, non_blocking=True)
+    return logits.index_select(0, pick), [s for s, _ in took]
+
+
 class SlotState(ctypes.Structure):
     """rwkv7_slot_state (include/rwkv7_hip.h)."""
     _fields_ = [("step", ctypes.c_void_p), ("limit", ctypes.c_void_p), ("min_until", ctypes.c_void_p), ("seed", ctypes.c_void_p),
@@ -594,19 +613,7 @@ class ContinuousDecoder:
         admitted together in ONE rwkv7_cache_rows_commit_bf16 launch over the cache's own field table (a repeated source row fans out; no
         row is both read and written: sources are first candidates, destinations are not).  Returns (one logits row per admitted
         request -- its prompt's, gathered --, every admitted slot in `took` order)."""
-        from .prefill import cache_rows_commit, check_commit_rows
-        dev, cfg = self.device, self.model.config
-        slot_of = {r.handle: s for s, r in heads}
-        row_of = {r.handle: i for i, (_, r) in enumerate(heads)}
-        sibs = [(slot_of[r.leader], s) for s, r in took if r.leader is not None]
-        src, dst = check_commit_rows([a for a, _ in sibs], [b for _, b in sibs], self.slots, self.slots)
-        if set(src) & set(dst):
-            raise RuntimeError(f"fan-out rows {src} -> {dst}: a row is both read and written")
-        tbl = self._cache_tbl()
-        rows = torch.tensor([src, dst], dtype=torch.int32).to(dev, non_blocking=True)
-        cache_rows_commit(tbl, tbl, rows[0], rows[1], len(sibs), len(self.cache), cfg.hidden_size, cfg.num_heads)
-        pick = torch.tensor([row_of[r.handle if r.leader is None else r.leader] for _, r in took], dtype=torch.int64).to(dev, non_blocking=True)
-        return logits.index_select(0, pick), [s for s, _ in took]
+        return fan_out_rows(self.cache, self._cache_tbl(), self.slots, self.model.config, self.device, took, heads, logits)
 
     # ---- admission="overlap" -------------------------------------------------------------------------------------------------
     def _init_overlap(self, max_seqs, buckets):

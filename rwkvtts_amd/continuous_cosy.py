@@ -30,7 +30,7 @@ import torch
 from . import _lib
 from .backbone import Cache
 from .decode import check_slots, step_class, step_for
-from .continuous import GroupScheduler, candidate_seed
+from .continuous import GroupScheduler, candidate_seed, fan_out_rows
 from .sampling import MAX_DOMAIN, fresh_seed
 
 MAX_WIN = 128          # entries of a slot's ring (rwkv7_ras_slots_f32)
@@ -433,21 +433,10 @@ class ContinuousCosyDecoder:
         groups admitted together in ONE rwkv7_cache_rows_commit_bf16 launch over the cache's own field table (a repeated source row
         fans out; no row is both read and written: sources are first candidates, destinations are not).  Returns (one logits row per
         admitted request -- its prompt's, gathered --, every admitted slot in `took` order)."""
-        from .prefill import cache_field_table, cache_rows_commit, check_commit_rows
-        dev, cfg = self.device, self.model.config
-        slot_of = {r.handle: s for s, r in heads}
-        row_of = {r.handle: i for i, (_, r) in enumerate(heads)}
-        sibs = [(slot_of[r.leader], s) for s, r in took if r.leader is not None]
-        src, dst = check_commit_rows([a for a, _ in sibs], [b for _, b in sibs], self.slots, self.slots)
-        if set(src) & set(dst):
-            raise RuntimeError(f"fan-out rows {src} -> {dst}: a row is both read and written")
+        from .prefill import cache_field_table
         if self._fan_tbl is None:
             self._fan_tbl = cache_field_table(self.cache)
-        tbl = self._fan_tbl
-        rows = torch.tensor([src, dst], dtype=torch.int32).to(dev, non_blocking=True)
-        cache_rows_commit(tbl, tbl, rows[0], rows[1], len(sibs), len(self.cache), cfg.hidden_size, cfg.num_heads)
-        pick = torch.tensor([row_of[r.handle if r.leader is None else r.leader] for _, r in took], dtype=torch.int64).to(dev, non_blocking=True)
-        return logits.index_select(0, pick), [s for s, _ in took]
+        return fan_out_rows(self.cache, self._fan_tbl, self.slots, self.model.config, self.device, took, heads, logits)
 
     def _admit_draw(self, took, logits, rows64, row_slot):
         # the slots' parameters: host mirror -> one copy per field; loop index, emitted count and ring pointer 0, an empty ring and

@@ -17,6 +17,16 @@ sampling parameters, and a Philox counter that contains the batch row.  Here eve
 A request's draws use (its seed, its frame index, the channel) only, so its frames do not depend on its slot or on when it was
 admitted (graph admission: for the same pack composition, see ContinuousDecoder).  head_column_map is the device-free part of the
 setup: where each channel's logits sit in a row of the concatenated head.
+
+Best-of-n (submit_n, logprobs=True, take_logprobs): n candidates of one prompt share one prefill -- the first candidate's cache row
+is copied to its siblings' rows in one rwkv7_cache_rows_commit_bf16 launch (continuous.fan_out_rows) -- and the LP entries
+rwkv7_xy_slots_draw_lp_f32 / rwkv7_xy_slots_frame_lp_bf16 write the log-probability of what every frame drew.  The frame rules may
+replace a drawn id by a forced one (eos0 on channel 0 while flushing, the pad id on channel i once the countdown has passed it), so
+a frame's value is known only after them: channel 0 COUNTS iff the flush had not started before the frame (the frame that starts it
+still counts: the non-audio id was the model's choice), channel i >= 1 counts iff the frame keeps its drawn id; a forced entry is
++0.0 in frame_lp and adds nothing to cum_lp / n_lp.  rank_candidates orders a group by cum_lp with n_lp as the lengths; XY has no
+teacher-forced scoring pass, so this is the model's only cheap ranking signal.  Not supported: stored states and overlapped
+admission (this engine has neither).
 """
 from __future__ import annotations
 
@@ -30,7 +40,7 @@ import torch
 from . import _lib
 from .backbone import Cache
 from .decode import check_slots, step_class, step_for
-from .continuous import SlotScheduler
+from .continuous import GroupScheduler, candidate_seed, fan_out_rows
 from .sampling import MAX_DOMAIN, MAX_TOP_K, RowSampler, XYEmbed, fresh_seed
 
 MAX_CHANNELS = 16
@@ -79,22 +89,36 @@ class XYSlotState(ctypes.Structure):
                 ("n_eos", ctypes.c_int), ("reference_termination", ctypes.c_int)]
 
 
+class XYSlotLogprob(ctypes.Structure):
+    """rwkv7_xy_slot_logprob (include/rwkv7_hip.h)."""
+    _fields_ = [("ch_lp", ctypes.c_void_p), ("frame_lp", ctypes.c_void_p), ("cum_lp", ctypes.c_void_p), ("n_lp", ctypes.c_void_p)]
+
+
 def xy_slots_draw(logits: torch.Tensor, st: XYSlotState, seg_off, seg_len, allow_lo, allow_hi, max_domain: int,
-                  row_slot: Optional[torch.Tensor] = None):
+                  row_slot: Optional[torch.Tensor] = None, lp: Optional[XYSlotLogprob] = None):
     """rwkv7_xy_slots_draw_f32 on the current stream: logits fp32 [rows, width] (unit column stride); seg_off / seg_len / allow_lo /
-    allow_hi int32 [C] device tensors (allow_*: both or None); row_slot int32 [rows] or None (row r is slot r)."""
+    allow_hi int32 [C] device tensors (allow_*: both or None); row_slot int32 [rows] or None (row r is slot r).  With lp (ch_lp fp32
+    [slots, C], frame_lp fp32 [slots, seq_ld, C], cum_lp fp64 [slots], n_lp int64 [slots]): rwkv7_xy_slots_draw_lp_f32, the same
+    draw plus ch_lp."""
     assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
     if row_slot is not None:
         assert row_slot.dtype == torch.int32 and row_slot.is_contiguous() and row_slot.numel() == logits.shape[0]
-    _lib.call("rwkv7_xy_slots_draw_f32", logits, logits.shape[0], logits, logits.stride(0), row_slot, seg_off, seg_len, allow_lo, allow_hi,
-              int(max_domain), ctypes.byref(st))
+    args = (logits.shape[0], logits, logits.stride(0), row_slot, seg_off, seg_len, allow_lo, allow_hi, int(max_domain), ctypes.byref(st))
+    if lp is None:
+        _lib.call("rwkv7_xy_slots_draw_f32", logits, *args)
+    else:
+        _lib.call("rwkv7_xy_slots_draw_lp_f32", logits, *args, ctypes.byref(lp))
 
 
-def xy_slots_frame(rows: int, st: XYSlotState, device, row_slot: Optional[torch.Tensor] = None):
-    """rwkv7_xy_slots_frame_bf16 on the current stream of `device`, for `rows` rows (row_slot as in xy_slots_draw)."""
+def xy_slots_frame(rows: int, st: XYSlotState, device, row_slot: Optional[torch.Tensor] = None, lp: Optional[XYSlotLogprob] = None):
+    """rwkv7_xy_slots_frame_bf16 on the current stream of `device`, for `rows` rows (row_slot as in xy_slots_draw).  With lp:
+    rwkv7_xy_slots_frame_lp_bf16, the same frame plus the accounting of the counted channels (frame_lp, cum_lp, n_lp)."""
     if row_slot is not None:
         assert row_slot.dtype == torch.int32 and row_slot.is_contiguous() and row_slot.numel() == rows
-    _lib.call("rwkv7_xy_slots_frame_bf16", device, int(rows), row_slot, ctypes.byref(st))
+    if lp is None:
+        _lib.call("rwkv7_xy_slots_frame_bf16", device, int(rows), row_slot, ctypes.byref(st))
+    else:
+        _lib.call("rwkv7_xy_slots_frame_lp_bf16", device, int(rows), row_slot, ctypes.byref(st), ctypes.byref(lp))
 
 
 class ContinuousXYDecoder:
@@ -105,12 +129,31 @@ class ContinuousXYDecoder:
     [n, C] tensor: the frames up to and including the one on which the request ended (budget, EOS on channel 0, or the end of a
     flush) -- the rows RWKV7XYLM.generate would append for B = 1.  Channel 0 is restricted to the audio range, as in generate, and
     its head is sliced to those rows (the full 66 661-id head is outside the draw's domain).  eos_token_id: a channel-0 id that ends a
-    request when it is drawn.  admission / prefill_max_seqs / prefill_buckets: as in ContinuousDecoder."""
+    request when it is drawn.  admission / prefill_max_seqs / prefill_buckets: as in ContinuousDecoder.
+
+    Best-of-n: submit_n(n, ...) queues n candidates of one prompt, admitted together (GroupScheduler), the prompt prefilled once and
+    its cache row copied to the siblings' rows (_fan_out).  logprobs=True makes the captured step and the admission draw call the
+    LP entries, which also write, per emitted frame, the log-probability under the raw logits of every channel whose drawn id the
+    frame rules kept (frame_lp [slots, cap, C] fp32; +0.0 where the id was forced -- see the module docstring for the rule), their
+    running fp64 sum (cum_lp [slots]) and their number (n_lp [slots]).  take_logprobs(handle) hands them out once the handle has
+    been reported finished, and continuous.rank_candidates orders a group:
+
+        hs = eng.submit_n(4, prompt, do_sample=True, top_k=50, seed=7); out = eng.run()
+        lp = [eng.take_logprobs(h) for h in hs]                                   # (frame_lp[:n], cum_lp, n_lp) per candidate
+        best = hs[rank_candidates([c for _, c, _ in lp], [n for _, _, n in lp])[0]]
+
+    logprobs=True changes no frame; with logprobs=False and no submit_n every launch is the one of before.  Stored states and
+    overlapped admission are not supported (this engine has neither)."""
+
+    logprobs = False   # the default of the constructor's switch; nothing below looks at frame_lp / cum_lp / n_lp without it
+    lp = None          # XYSlotLogprob with logprobs=True: the frames go through the LP entries
 
     def __init__(self, model, slots: int = 32, max_new_frames_cap: int = 3000, eos_token_id: Optional[int] = None, check_every: int = 16,
-                 admission: str = "eager", prefill_max_seqs: int = 8, prefill_buckets: Sequence[int] = (256, 512, 1024, 2048, 4096)):
+                 admission: str = "eager", prefill_max_seqs: int = 8, prefill_buckets: Sequence[int] = (256, 512, 1024, 2048, 4096),
+                 logprobs: bool = False):
         if admission not in ("eager", "graph"):
             raise ValueError(f"admission = {admission!r}: 'eager' or 'graph'")
+        self.logprobs = bool(logprobs)
         check_slots(slots)   # 1..32, or 64 / 96 / 128: ValueError before anything touches the device
         if max_new_frames_cap < 1 or check_every < 1:
             raise ValueError("max_new_frames_cap and check_every must be >= 1")
@@ -184,8 +227,16 @@ class ContinuousXYDecoder:
         st.eos_list, st.n_eos = (None, 0) if self.eos_list is None else (self.eos_list.data_ptr(), 1)
         st.reference_termination = 0
         self.st = st
+        if self.logprobs:   # what the LP entries write next to nt / seq
+            self.ch_lp = torch.zeros(S, C, dtype=torch.float32, device=dev)
+            self.frame_lp = torch.zeros(S, self.cap, C, dtype=torch.float32, device=dev)
+            self.cum_lp = torch.zeros(S, dtype=torch.float64, device=dev)
+            self.n_lp = torch.zeros(S, **l64)
+            self.lp = XYSlotLogprob(self.ch_lp.data_ptr(), self.frame_lp.data_ptr(), self.cum_lp.data_ptr(), self.n_lp.data_ptr())
+        self._lp_done: Dict[int, Tuple[torch.Tensor, torch.Tensor, int]] = {}   # handle -> its values until take_logprobs()
+        self._fan_tbl = None   # submit_n: the cache's own field table, source and destination of the fan-out copy
 
-        self.sched = SlotScheduler(slots)
+        self.sched = GroupScheduler(slots)   # for groups of one its admit() is SlotScheduler's
         self.dstep = step_for(m.model, self.head, self.cache)
         # capture the step with every slot idle (live = 0): the frame kernels write nothing, and what the warm-up does to the state
         # of idle rows does not matter (admission resets a row before it is used)
@@ -204,8 +255,8 @@ class ContinuousXYDecoder:
             self.prefill = PackedPrefill(m.model, self.cache, max_seqs=prefill_max_seqs, buckets=prefill_buckets)
 
     def _frame(self, logits, row_slot=None):
-        xy_slots_draw(logits, self.st, self.seg_off, self.seg_len, self.allow_lo, self.allow_hi, self.cols.max_domain, row_slot)
-        xy_slots_frame(logits.shape[0], self.st, self.device, row_slot)
+        xy_slots_draw(logits, self.st, self.seg_off, self.seg_len, self.allow_lo, self.allow_hi, self.cols.max_domain, row_slot, self.lp)
+        xy_slots_frame(logits.shape[0], self.st, self.device, row_slot, self.lp)
 
     def _step(self):
         self._frame(self.dstep(self.x))
@@ -215,6 +266,44 @@ class ContinuousXYDecoder:
     def submit(self, input_ids, max_new_frames: int = 256, do_sample: bool = False, temperature: float = 1.0, top_k: int = 0,
                top_p: float = 1.0, seed: Optional[int] = None) -> int:
         """Queue one request (a prompt of T frames: int64 ids [T, C] or [1, T, C]); returns its handle.  Non-blocking."""
+        fields = self._request_fields(input_ids, max_new_frames, do_sample, temperature, top_k, top_p)
+        seed = int(fresh_seed() if seed is None else seed) & ((1 << 64) - 1)
+        return self.sched.submit(seed=seed, **fields)
+
+    @torch.no_grad()
+    def submit_n(self, n: int, input_ids, max_new_frames: int = 256, do_sample: bool = False, temperature: float = 1.0, top_k: int = 0,
+                 top_p: float = 1.0, seed: Optional[int] = None) -> List[int]:
+        """Queue n candidates of ONE prompt (submit()'s arguments): their handles in candidate order.  Candidate i draws with the key
+        candidate_seed(seed, i) and is, frame for frame, the request submit(..., seed=candidate_seed(seed, i)) would be.  The group is
+        admitted whole, when n slots are free: the prompt is prefilled once and its cache row copied to the other candidates' rows.
+        n < 1 or n > slots: ValueError; n > 1 needs a seed (the candidates' keys are derived from it, and a result that cannot be
+        reproduced cannot be ranked again): ValueError without one.  Nothing is queued then."""
+        n = int(n)
+        if n < 1 or n > self.slots:
+            raise ValueError(f"n = {n} candidates outside 1..{self.slots} (slots): a group is admitted whole")
+        if n > 1 and seed is None:
+            raise ValueError(f"submit_n with n = {n} needs a seed: candidate i draws with candidate_seed(seed, i)")
+        fields = self._request_fields(input_ids, max_new_frames, do_sample, temperature, top_k, top_p)
+        seed = int(fresh_seed() if seed is None else seed) & ((1 << 64) - 1)
+        if n == 1:
+            return [self.sched.submit(seed=seed, **fields)]
+        return self.sched.submit_group(n, [candidate_seed(seed, i) for i in range(n)], **fields)
+
+    def take_logprobs(self, handle: int) -> Tuple[torch.Tensor, torch.Tensor, int]:
+        """(frame_lp [n, C] fp32, cum_lp fp64 scalar, n_lp int) of a request that step() / run() has reported finished, the tensors on
+        the device: per emitted frame and channel the log-probability of the drawn id under the raw logits (temperature 1, before
+        top-k / top-p, over the channel's allowed ids) where the frame rules kept the draw and +0.0 where they forced the id; the sum
+        of the counted values, added in (frame, channel) order in fp64; and their number, the length for
+        rank_candidates(length_normalize=True).  Needs logprobs=True; a handle's result can be taken once."""
+        if not self.logprobs:
+            raise ValueError("take_logprobs needs ContinuousXYDecoder(..., logprobs=True)")
+        try:
+            return self._lp_done.pop(handle)
+        except KeyError:
+            raise KeyError(f"handle {handle}: not finished yet (step() / run() has not reported it), unknown, or already taken") from None
+
+    def _request_fields(self, input_ids, max_new_frames, do_sample, temperature, top_k, top_p) -> dict:
+        """submit()'s argument checks and the prompt's embeddings: the scheduler request's fields but the handle and the seed."""
         if not 1 <= int(max_new_frames) <= self.cap:
             raise ValueError(f"max_new_frames = {max_new_frames} outside 1..{self.cap} (max_new_frames_cap)")
         top_k, top_p = int(top_k or 0), 1.0 if top_p is None else float(top_p)
@@ -227,9 +316,8 @@ class ContinuousXYDecoder:
         if ids.dim() != 2 or ids.shape[1] != self.C or ids.shape[0] < 1 or ids.dtype != torch.int64:
             raise ValueError(f"input_ids must be int64 of shape (T, {self.C}) with T >= 1, got {tuple(ids.shape)} {ids.dtype}")
         e = self.model.embed(ids.to(self.device).unsqueeze(0))[0]
-        seed = int(fresh_seed() if seed is None else seed) & ((1 << 64) - 1)
-        return self.sched.submit(embeds=e.detach(), max_new_tokens=int(max_new_frames), do_sample=bool(do_sample),
-                                 temperature=float(temperature or 1.0), top_k=top_k, top_p=top_p, seed=seed)
+        return dict(embeds=e.detach(), max_new_tokens=int(max_new_frames), do_sample=bool(do_sample),
+                    temperature=float(temperature or 1.0), top_k=top_k, top_p=top_p)
 
     @torch.no_grad()
     def step(self) -> List[Tuple[int, torch.Tensor]]:
@@ -269,11 +357,14 @@ class ContinuousXYDecoder:
 
     # ---- internals -----------------------------------------------------------------------------------------------------------
     def _retire(self, slots, steps) -> List[Tuple[int, torch.Tensor]]:
-        out = []
+        out, counted = [], None
         for s in slots:
             req = self.sched.retire(s)
             n = req.max_new_tokens if steps is None else int(steps[s])
             out.append((req.handle, self.seq[s, :n].clone()))
+            if self.logprobs:
+                counted = self.n_lp.cpu() if counted is None else counted   # one read-back for all slots retired together
+                self._lp_done[req.handle] = (self.frame_lp[s, :n].clone(), self.cum_lp[s].clone(), int(counted[s]))
         return out
 
     def _head(self, h):
@@ -284,24 +375,41 @@ class ContinuousXYDecoder:
         if not took:
             return
         m, dev = self.model, self.device
-        slots = [s for s, _ in took]
+        # the requests that prefill: all of them, but for the candidates of a submit_n group after its first, which get a copy of its rows
+        heads = [(s, r) for s, r in took if r.leader is None]
+        slots = [s for s, _ in heads]
         if self.prefill is not None:
-            h_last = self.prefill.run([r.embeds for _, r in took], slots, fresh=True)
+            h_last = self.prefill.run([r.embeds for _, r in heads], slots, fresh=True)
+            logits = self._head(h_last)
+            if len(heads) < len(took):
+                logits, slots = self._fan_out(took, heads, logits)
             row_slot = torch.tensor(slots, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
-            return self._admit_draw(took, self._head(h_last), row_slot.long(), row_slot)
+            return self._admit_draw(took, logits, row_slot.long(), row_slot)
         cu = [0]
-        for _, r in took:
+        for _, r in heads:
             cu.append(cu[-1] + r.embeds.shape[0])
         rows64 = torch.tensor(slots, dtype=torch.int64).to(dev, non_blocking=True)
         for st in self.cache.states:   # a fresh state for every admitted request
             st.att_x_prev.index_fill_(0, rows64, 0)
             st.att_kv.index_fill_(0, rows64, 0)
             st.ffn_x_prev.index_fill_(0, rows64, 0)
-        packed = torch.cat([r.embeds for _, r in took], 0).unsqueeze(0)
+        packed = torch.cat([r.embeds for _, r in heads], 0).unsqueeze(0)
         h = m.model(inputs_embeds=packed, cu_seqlens=torch.tensor(cu, dtype=torch.int32), past_key_values=self.cache,
                     cache_rows=torch.tensor(slots)).last_hidden_state
         last = torch.tensor([c - 1 for c in cu[1:]], dtype=torch.int64).to(dev, non_blocking=True)
-        self._admit_draw(took, self._head(h[0].index_select(0, last)), rows64, torch.tensor(slots, dtype=torch.int32).to(dev, non_blocking=True))
+        logits = self._head(h[0].index_select(0, last))
+        if len(heads) < len(took):
+            logits, slots = self._fan_out(took, heads, logits)
+            rows64 = torch.tensor(slots, dtype=torch.int64).to(dev, non_blocking=True)
+        self._admit_draw(took, logits, rows64, torch.tensor(slots, dtype=torch.int32).to(dev, non_blocking=True))
+
+    def _fan_out(self, took, heads, logits):
+        """submit_n: continuous.fan_out_rows over this engine's cache -- the first candidates' prefilled rows -> their siblings' rows
+        in one launch; (one logits row per admitted request, every admitted slot in `took` order)."""
+        if self._fan_tbl is None:
+            from .prefill import cache_field_table
+            self._fan_tbl = cache_field_table(self.cache)
+        return fan_out_rows(self.cache, self._fan_tbl, self.slots, self.model.config, self.device, took, heads, logits)
 
     def _admit_draw(self, took, logits, rows64, row_slot):
         # the slots' parameters: host mirror -> one copy per field; step = 0, needs = -1 and live = 1 for the admitted slots only (the
@@ -320,4 +428,7 @@ class ContinuousXYDecoder:
         self.step_t.index_fill_(0, rows64, 0)
         self.needs.index_fill_(0, rows64, -1)
         self.live.index_fill_(0, rows64, 1)
+        if self.logprobs:
+            self.cum_lp.index_fill_(0, rows64, 0)
+            self.n_lp.index_fill_(0, rows64, 0)
         self._frame(logits.contiguous(), row_slot)

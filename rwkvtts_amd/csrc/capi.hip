@@ -715,16 +715,36 @@ static bool xy_slot_state_ok(const rwkv7_xy_slot_state *st) {
         if (!st->tables[c]) return false;
     return true;
 }
+// what rwkv7_xy_slots_draw_f32 and rwkv7_xy_slots_draw_lp_f32 both refuse before a launch
+static bool xy_slots_draw_args_ok(int rows, const float *logits, const int *seg_off, const int *seg_len, const int *allow_lo,
+                                  const int *allow_hi, int max_domain, const rwkv7_xy_slot_state *st) {
+    return !(rows <= 0 || max_domain <= 0 || !xy_slot_state_ok(st) || (!allow_lo != !allow_hi) ||
+             any_null({(const void *)logits, (const void *)seg_off, (const void *)seg_len}));
+}
 int rwkv7_xy_slots_draw_f32(int rows, const float *logits, long ld, const int *row_slot, const int *seg_off, const int *seg_len,
                             const int *allow_lo, const int *allow_hi, int max_domain, const rwkv7_xy_slot_state *st, rwkv7_stream_t stream) {
-    if (rows <= 0 || max_domain <= 0 || !xy_slot_state_ok(st) || (!allow_lo != !allow_hi) ||
-        any_null({(const void *)logits, (const void *)seg_off, (const void *)seg_len}))
-        return RWKV7_EINVAL;
+    if (!xy_slots_draw_args_ok(rows, logits, seg_off, seg_len, allow_lo, allow_hi, max_domain, st)) return RWKV7_EINVAL;
     return rwkv7::xy_slots_draw_f32(rows, logits, ld, row_slot, seg_off, seg_len, allow_lo, allow_hi, max_domain, st, (hipStream_t)stream);
 }
 int rwkv7_xy_slots_frame_bf16(int rows, const int *row_slot, const rwkv7_xy_slot_state *st, rwkv7_stream_t stream) {
     if (rows <= 0 || !xy_slot_state_ok(st)) return RWKV7_EINVAL;
     return rwkv7::xy_slots_frame_bf16(rows, row_slot, st, (hipStream_t)stream);
+}
+// one struct serves the two calls of a frame: both entries want all of it
+static bool xy_slot_logprob_ok(const rwkv7_xy_slot_logprob *lp) { return lp && lp->ch_lp && lp->frame_lp && lp->cum_lp && lp->n_lp; }
+int rwkv7_xy_slots_draw_lp_f32(int rows, const float *logits, long ld, const int *row_slot, const int *seg_off, const int *seg_len,
+                               const int *allow_lo, const int *allow_hi, int max_domain, const rwkv7_xy_slot_state *st,
+                               const rwkv7_xy_slot_logprob *lp, rwkv7_stream_t stream) {
+    if (!xy_slots_draw_args_ok(rows, logits, seg_off, seg_len, allow_lo, allow_hi, max_domain, st)) return RWKV7_EINVAL;
+    if (!xy_slot_logprob_ok(lp)) return RWKV7_EINVAL;
+    return rwkv7::xy_slots_draw_lp_f32(rows, logits, ld, row_slot, seg_off, seg_len, allow_lo, allow_hi, max_domain, st, lp,
+                                       (hipStream_t)stream);
+}
+int rwkv7_xy_slots_frame_lp_bf16(int rows, const int *row_slot, const rwkv7_xy_slot_state *st, const rwkv7_xy_slot_logprob *lp,
+                                 rwkv7_stream_t stream) {
+    if (rows <= 0 || !xy_slot_state_ok(st)) return RWKV7_EINVAL;
+    if (!xy_slot_logprob_ok(lp)) return RWKV7_EINVAL;
+    return rwkv7::xy_slots_frame_lp_bf16(rows, row_slot, st, lp, (hipStream_t)stream);
 }
 // what rwkv7_ras_slots_f32 and rwkv7_ras_slots_lp_f32 both refuse before a launch
 static bool ras_slots_args_ok(int rows, int V, const float *logits, const rwkv7_ras_slot_state *st) {

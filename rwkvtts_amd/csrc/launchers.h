@@ -180,6 +180,10 @@ int xy_embed_bf16(int B, int C, int D, const void *const *tables_host, const lon
 int xy_slots_draw_f32(int rows, const float *logits, long ld, const int *row_slot, const int *seg_off, const int *seg_len,
                       const int *allow_lo, const int *allow_hi, int max_domain, const void *st, hipStream_t stream);
 int xy_slots_frame_bf16(int rows, const int *row_slot, const void *st, hipStream_t stream);
+// lp: the header's rwkv7_xy_slot_logprob, copied by the launcher like st
+int xy_slots_draw_lp_f32(int rows, const float *logits, long ld, const int *row_slot, const int *seg_off, const int *seg_len,
+                         const int *allow_lo, const int *allow_hi, int max_domain, const void *st, const void *lp, hipStream_t stream);
+int xy_slots_frame_lp_bf16(int rows, const int *row_slot, const void *st, const void *lp, hipStream_t stream);
 int ras_slots_f32(int rows, int V, const float *logits, long ld, const int *row_slot, const void *st, hipStream_t stream);
 int ras_slots_lp_f32(int rows, int V, const float *logits, long ld, const int *row_slot, const void *st, float *tok_lp, double *cum_lp,
                      float *end_lp, hipStream_t stream);

@@ -165,14 +165,6 @@ struct SlotStateLp : SlotState {
     float *tok_lp;    // [slots][seq_ld]
     double *cum_lp;   // [slots]
 };
-__device__ __forceinline__ float block_fmax(float v, SmpShared &sm) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sm.red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(sm.red[0], sm.red[1]), fmaxf(sm.red[2], sm.red[3]));
-}
 template <int EPT, bool LP>
 __global__ __launch_bounds__(kSmpThreads) void sample_slots_kernel(const float *__restrict__ logits, long ld, const int *__restrict__ row_slot,
                                                                    const int *__restrict__ allow_lo, const int *__restrict__ allow_hi,

@@ -89,6 +89,15 @@ __device__ __forceinline__ float block_sum(float v, SmpShared &sm) {
     __syncthreads();
     return (sm.red[0] + sm.red[1]) + (sm.red[2] + sm.red[3]);
 }
+// the float maximum the same way (the draw-time log-probabilities: with block_sum, thread -> wave butterfly -> the four waves in fixed order)
+__device__ __forceinline__ float block_fmax(float v, SmpShared &sm) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sm.red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(sm.red[0], sm.red[1]), fmaxf(sm.red[2], sm.red[3]));
+}
 
 // A thread's share of the segment: elements tid + 256 e, e < EPT, in registers (-inf beyond the segment).
 template <int EPT>

@@ -9,8 +9,15 @@
 //      (pos = step[s], total = limit[s], still running) and leaves the row in LDS; after the barrier every lane adds the C embedding
 //      rows like xy_embed_kernel (bf16 rounding after each addition, channel order) with 16-byte loads.
 // A slot with live[s] == 0, and a row whose row_slot entry lies outside [0, slots), is left completely untouched by both launches.
+//
+// LP (rwkv7_xy_slots_draw_lp_f32 / rwkv7_xy_slots_frame_lp_bf16; ContinuousXYDecoder(logprobs=True)): the log-probability of what a
+// frame drew as well.  The draw writes every channel's value (ch_lp); which of them COUNT is only known once the frame rules have
+// decided which drawn ids the frame keeps, so the frame kernel does the accounting (frame_lp, cum_lp, n_lp).  Everything new sits
+// under `if constexpr (LP)`; with LP = false both bodies are what they always were.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "launchers.h"
 #include "sampling_common.h"
@@ -39,13 +46,28 @@ struct XYSlotState {
     int n_eos, reference_termination;
 };
 
+// = rwkv7_xy_slot_state followed by the members of rwkv7_xy_slot_logprob: what the LP instantiations get
+struct XYSlotStateLp : XYSlotState {
+    float *ch_lp;      // [slots][C]
+    float *frame_lp;   // [slots][seq_ld][C]
+    double *cum_lp;    // [slots]
+    long *n_lp;        // [slots]
+};
+template <bool LP>
+using XYState = typename std::conditional<LP, XYSlotStateLp, XYSlotState>::type;
+
 // The body repeats sample_rows_kernel's draw (csrc/sampling.hip) with the slot's parameters in place of the launch's: same loads, same
 // selection, same Philox counter for workgroup index = channel, so the id equals that kernel's bit for bit.
-template <int EPT>
+//
+// LP: ch_lp[s][c] = the drawn id's log-probability under the RAW logits (temperature 1, no top-k / top-p) over the channel's allowed
+// range.  A second copy of the range stays unscaled in registers until its maximum and its exp-sum are known, which is before
+// select_bins needs the registers for its bins.  Both reductions go thread -> wave butterfly -> the four waves in fixed order
+// (block_fmax, block_sum): the value depends on the range's contents and the thread layout only, never on the row, the slot or the grid.
+template <int EPT, bool LP>
 __global__ __launch_bounds__(kSmpThreads) void xy_slot_draw_kernel(const float *__restrict__ logits, long ld, const int *__restrict__ row_slot,
                                                                    const int *__restrict__ seg_off, const int *__restrict__ seg_len,
                                                                    const int *__restrict__ allow_lo, const int *__restrict__ allow_hi,
-                                                                   XYSlotState st) {
+                                                                   XYState<LP> st) {
     __shared__ SmpShared sm;
     const int C = st.C;
     const int seg = blockIdx.x % C, row = blockIdx.x / C, tid = threadIdx.x;
@@ -62,11 +84,25 @@ __global__ __launch_bounds__(kSmpThreads) void xy_slot_draw_kernel(const float *
     const int m = hi - lo;
     if (m < 1) return;   // an empty allowed range: nothing is read (uniform)
     Vals<EPT> x;
+    Vals<LP ? EPT : 1> raw;   // LP: the same elements at temperature 1
 #pragma unroll
     for (int e = 0; e < EPT; e++) {
         const int j = tid + kSmpThreads * e;
         const float t = xg[lo + min(j, m - 1)];
         x.v[e] = j < m ? t * inv_temp : -INFINITY;
+        if constexpr (LP) raw.v[e] = j < m ? t : -INFINITY;
+    }
+    float lp_max = 0.f, lp_logz = 0.f;   // LP: max and log sum exp(. - max) over the allowed range
+    if constexpr (LP) {
+        float mx = raw.v[0];
+#pragma unroll
+        for (int e = 1; e < EPT; e++) mx = fmaxf(mx, raw.v[e]);
+        lp_max = block_fmax(mx, sm);
+        float z = 0.f;
+#pragma unroll
+        for (int e = 0; e < EPT; e++) z += __expf(raw.v[e] - lp_max);   // beyond the range: exp(-inf) = 0
+        lp_logz = __logf(block_sum(z, sm));
+        __syncthreads();   // sm.red is free again: select_bins writes it without a barrier of its own
     }
     int choice;
     if (!do_sample) {
@@ -101,11 +137,22 @@ __global__ __launch_bounds__(kSmpThreads) void xy_slot_draw_kernel(const float *
         }
     }
     choice = min(max(choice, 0), m - 1);
-    if (tid == 0) st.nt[(long)s * C + seg] = lo + choice;
+    if (tid == 0) {
+        st.nt[(long)s * C + seg] = lo + choice;
+        // no finite logit in the range (the id is the fall-back): -inf, not the NaN of (-inf) - (-inf)
+        if constexpr (LP) st.ch_lp[(long)s * C + seg] = lp_max == -INFINITY ? -INFINITY : (xg[lo + choice] - lp_max) - lp_logz;
+    }
 }
 
 // Frame rules (xy_frame_kernel for B = 1, pos = step[s], total = limit[s], all_done = 0) + the next input (xy_embed_kernel).
-__global__ __launch_bounds__(256) void xy_slot_frame_kernel(const int *__restrict__ row_slot, XYSlotState st) {
+//
+// LP: which of the C draws COUNT is a function of the slot's state alone (ids are never compared: a drawn id that happens to equal the
+// pad id is not misjudged).  Channel 0 counts iff the flush had not started before this frame (needs < 0 at entry): its id was the
+// model's free choice, even when eos0 is written in its place.  Channel i >= 1 counts iff the rule below keeps its drawn id.  Lane 0
+// writes frame_lp (the counted channels' ch_lp, +0 for a forced one) at the frame's row of seq, adds the counted values to cum_lp in
+// channel order in fp64 (one workgroup owns the slot: a plain read, add, store) and their number to n_lp.
+template <bool LP>
+__global__ __launch_bounds__(256) void xy_slot_frame_kernel(const int *__restrict__ row_slot, XYState<LP> st) {
     __shared__ long frame[kXYSlotMaxC];
     __shared__ long next[3];   // needs, step, live after this frame
     const int C = st.C, D = st.D, tid = threadIdx.x;
@@ -114,6 +161,7 @@ __global__ __launch_bounds__(256) void xy_slot_frame_kernel(const int *__restric
     if (tid == 0) {
         const long p0 = st.step[s];
         long needs = st.needs[s];
+        [[maybe_unused]] const long needs_in = needs;   // LP: the countdown as this frame found it
         const long *t = st.nt + (long)s * C;
         const long t0 = t[0];
         const bool is_audio = t0 >= st.text_shift && t0 < st.text_shift + st.speech_vocab;
@@ -122,6 +170,24 @@ __global__ __launch_bounds__(256) void xy_slot_frame_kernel(const int *__restric
         const long c0 = (st.eos0 >= 0 && flushing) ? st.eos0 : t0;
         frame[0] = c0;
         for (int i = 1; i < C; i++) frame[i] = (flushing && needs < C - i) ? st.pad : t[i];
+        if constexpr (LP) {
+            const long pw = min(max(p0, 0L), st.seq_ld - 1);   // the row seq gets below
+            float *fl = st.frame_lp + ((long)s * st.seq_ld + pw) * C;
+            const float *cl = st.ch_lp + (long)s * C;
+            double cum = st.cum_lp[s];
+            long counted = 0;
+            for (int i = 0; i < C; i++) {
+                const bool counts = i == 0 ? needs_in < 0 : !(flushing && needs < C - i);
+                const float v = counts ? cl[i] : 0.f;
+                fl[i] = v;
+                if (counts) {
+                    cum += (double)v;
+                    counted++;
+                }
+            }
+            st.cum_lp[s] = cum;
+            st.n_lp[s] += counted;
+        }
         if (flushing) needs -= 1;
         const long p1 = p0 + 1;
         const long total = st.limit[s];
@@ -180,27 +246,62 @@ __global__ __launch_bounds__(256) void xy_slot_frame_kernel(const int *__restric
 
 }  // namespace
 
-int xy_slots_draw_f32(int rows, const float *logits, long ld, const int *row_slot, const int *seg_off, const int *seg_len,
-                      const int *allow_lo, const int *allow_hi, int max_domain, const void *st_, hipStream_t stream) {
-    const XYSlotState st = *(const XYSlotState *)st_;
+template <bool LP>
+static int launch_xy_draw(int rows, const float *logits, long ld, const int *row_slot, const int *seg_off, const int *seg_len,
+                          const int *allow_lo, const int *allow_hi, int max_domain, const XYState<LP> &st, hipStream_t stream) {
     if (max_domain > kSmpMaxN || st.top_k_max < 0 || st.top_k_max > 64 || st.C > kXYSlotMaxC || st.D % 8 != 0) return -4;   // RWKV7_ESHAPE
     (void)hipGetLastError();
     const dim3 grid(rows * st.C), block(kSmpThreads);
     if (max_domain <= kEptS * kSmpThreads)
-        xy_slot_draw_kernel<kEptS><<<grid, block, 0, stream>>>(logits, ld, row_slot, seg_off, seg_len, allow_lo, allow_hi, st);
+        xy_slot_draw_kernel<kEptS, LP><<<grid, block, 0, stream>>>(logits, ld, row_slot, seg_off, seg_len, allow_lo, allow_hi, st);
     else if (max_domain <= kEptM * kSmpThreads)
-        xy_slot_draw_kernel<kEptM><<<grid, block, 0, stream>>>(logits, ld, row_slot, seg_off, seg_len, allow_lo, allow_hi, st);
+        xy_slot_draw_kernel<kEptM, LP><<<grid, block, 0, stream>>>(logits, ld, row_slot, seg_off, seg_len, allow_lo, allow_hi, st);
     else
-        xy_slot_draw_kernel<kEptL><<<grid, block, 0, stream>>>(logits, ld, row_slot, seg_off, seg_len, allow_lo, allow_hi, st);
+        xy_slot_draw_kernel<kEptL, LP><<<grid, block, 0, stream>>>(logits, ld, row_slot, seg_off, seg_len, allow_lo, allow_hi, st);
     return (int)hipGetLastError();
 }
 
-int xy_slots_frame_bf16(int rows, const int *row_slot, const void *st_, hipStream_t stream) {
-    const XYSlotState st = *(const XYSlotState *)st_;
+template <bool LP>
+static int launch_xy_frame(int rows, const int *row_slot, const XYState<LP> &st, hipStream_t stream) {
     if (st.C > kXYSlotMaxC || st.D % 8 != 0) return -4;
     (void)hipGetLastError();
-    xy_slot_frame_kernel<<<dim3(rows), dim3(256), 0, stream>>>(row_slot, st);
+    xy_slot_frame_kernel<LP><<<dim3(rows), dim3(256), 0, stream>>>(row_slot, st);
     return (int)hipGetLastError();
+}
+
+// st + lp (the header's rwkv7_xy_slot_logprob: four pointers in the order of XYSlotStateLp's own members)
+static XYSlotStateLp with_lp(const void *st_, const void *lp_) {
+    struct Lp {
+        float *ch_lp, *frame_lp;
+        double *cum_lp;
+        long *n_lp;
+    };
+    const Lp lp = *(const Lp *)lp_;
+    XYSlotStateLp st;
+    static_cast<XYSlotState &>(st) = *(const XYSlotState *)st_;
+    st.ch_lp = lp.ch_lp;
+    st.frame_lp = lp.frame_lp;
+    st.cum_lp = lp.cum_lp;
+    st.n_lp = lp.n_lp;
+    return st;
+}
+
+int xy_slots_draw_f32(int rows, const float *logits, long ld, const int *row_slot, const int *seg_off, const int *seg_len,
+                      const int *allow_lo, const int *allow_hi, int max_domain, const void *st_, hipStream_t stream) {
+    return launch_xy_draw<false>(rows, logits, ld, row_slot, seg_off, seg_len, allow_lo, allow_hi, max_domain, *(const XYSlotState *)st_, stream);
+}
+
+int xy_slots_draw_lp_f32(int rows, const float *logits, long ld, const int *row_slot, const int *seg_off, const int *seg_len,
+                         const int *allow_lo, const int *allow_hi, int max_domain, const void *st_, const void *lp_, hipStream_t stream) {
+    return launch_xy_draw<true>(rows, logits, ld, row_slot, seg_off, seg_len, allow_lo, allow_hi, max_domain, with_lp(st_, lp_), stream);
+}
+
+int xy_slots_frame_bf16(int rows, const int *row_slot, const void *st_, hipStream_t stream) {
+    return launch_xy_frame<false>(rows, row_slot, *(const XYSlotState *)st_, stream);
+}
+
+int xy_slots_frame_lp_bf16(int rows, const int *row_slot, const void *st_, const void *lp_, hipStream_t stream) {
+    return launch_xy_frame<true>(rows, row_slot, with_lp(st_, lp_), stream);
 }
 
 }  // namespace rwkv7
