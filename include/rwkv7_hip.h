@@ -458,6 +458,26 @@ int rwkv7_cache_rows_commit_bf16(int layers, int n, const void *const *src_tbl, 
 #define RWKV7_SEED_ZERO (-1)
 int rwkv7_cache_rows_seed_bf16(int layers, int n, const void *const *src_tbl, void *const *dst_tbl, const int *src_row,
                                const int *dst_row, int D, int H, rwkv7_stream_t stream);
+/*   rwkv7_cache_rows_retain_bf16: the same copy body (csrc/cache_rows.hip) as the last launch of a continuous-batching step
+ *      (ContinuousDecoder(..., state_store=..., retain=True)): the state a request leaves behind goes to a row of a StateStore in the
+ *      very step in which the request ends, before a later step runs the dead slot's row through stale inputs.  Tables, field order,
+ *      alignment and error codes as for rwkv7_cache_rows_commit_bf16; the source cache has at least `slots` rows.
+ *        live        DEVICE uint8 [slots]  the engine's live flags (rwkv7_slot_state.live), read only
+ *        armed       DEVICE uint8 [slots]  != 0: the slot's request is to be retained; cleared by the launch that copies the slot
+ *        retain_row  DEVICE int32 [slots]  the destination row of slot s, or a negative value (no row), read only
+ *        ticket      DEVICE int32 [slots]  zero between launches; workspace of the launch
+ *      Slot s is copied -- row s of the source -> row retain_row[s] of the destination, all three fields of all layers, bits
+ *      preserved -- when armed[s] != 0, live[s] == 0 and retain_row[s] >= 0, and then armed[s] is 0 when the launch completes, so the
+ *      copy happens once.  In every other case nothing of slot s is read or written beyond the flags.  Many workgroups serve one
+ *      slot; each reads the flags, copies its piece and draws a ticket with a device-scope atomic add on ticket[s], and the one
+ *      that draws the last ticket clears armed[s] and ticket[s]: no workgroup sees armed[s] cleared within its own launch.
+ *      retain_row is NOT range-checked (device data): the caller guarantees rows inside the destination cache, distinct among the
+ *      non-negative entries (the Python wrapper validates on the host), and a destination that is not the source cache.
+ *      slots = 0 returns RWKV7_OK without a launch.  RWKV7_EINVAL: NULL table, NULL live / armed / retain_row / ticket (whatever
+ *      slots is), slots < 0, layers < 1, slots or layers > 65535, D or H < 1; RWKV7_ESHAPE: D % 8 != 0 or D > 4096; RWKV7_EHEAD:
+ *      D != 64 * H.  Nothing is launched then. */
+int rwkv7_cache_rows_retain_bf16(int layers, int slots, const void *const *src_tbl, void *const *dst_tbl, const unsigned char *live,
+                                 unsigned char *armed, const int *retain_row, int *ticket, int D, int H, rwkv7_stream_t stream);
 /* ---- state tuning (rwkvtts_amd/state_tune.py, csrc/state_tune.hip): every weight frozen, the initial states of named voices are
  *      the trained tensors.  The MASTER state of voice v is fp32, per layer att_x_prev [V,D], att_kv [V,H,64,64], ffn_x_prev [V,D];
  *      its AdamW moments m and v are fp32 of the same shapes.  Every table below is a DEVICE table of 3 * layers pointers in the

@@ -13,7 +13,9 @@ every one of up to 128 SLOTS (rows of the step kernel's batch) runs its own requ
     admission="overlap" that prefill runs on a side stream into a staging cache while the step keeps replaying, and the decode stream
     later copies the staged rows into the slots' rows in one launch (rwkv7_cache_rows_commit_bf16) and draws the first ids;
   * retirement: without EOS the host knows every budget and retires slots on the exact step with no read-back; with EOS it reads
-    the live flags and step counters back every `check_every` replays.
+    the live flags and step counters back every `check_every` replays;
+  * with retain=True a last launch of the captured step (rwkv7_cache_rows_retain_bf16, csrc/cache_rows.hip) copies the cache row of a
+    slot whose request just ended into a row of the attached StateStore, for requests submitted with retain=name.
 
 A request's draws use (its seed, its step) only, so its ids do not depend on its slot or on when it was admitted.  Slots without a
 request keep stepping on stale state; admission resets the row.  The scheduling lives in SlotScheduler, which never touches the
@@ -49,12 +51,23 @@ class Request:
     leader: Optional[int] = None    # handle of the group's first candidate, whose prefill this one shares; None: it prefills itself
     state: Optional[str] = None     # name of the stored state the prompt continues from (state_store.StateStore); None: from zero
     state_row: Optional[int] = None  # that state's row in the store, resolved (and pinned) at submit
+    base_tokens: int = 0            # the tokens that stored state had seen, read at submit
+    retain: Optional[str] = None    # name under which the state this request leaves behind is published (ContinuousDecoder retain=True)
+    retain_row: Optional[int] = None  # the pending row of the store held for it since submit
 
 
 def candidate_seed(seed: int, i: int) -> int:
     """The Philox key of candidate i of submit_n(..., seed=seed): (seed + i) mod 2^64.  Candidate i draws what a stand-alone
     submit(..., seed=candidate_seed(seed, i)) draws."""
     return (int(seed) + int(i)) & ((1 << 64) - 1)
+
+
+def retained_tokens(base_tokens: int, prompt_len: int, n_ids: int) -> int:
+    """Tokens a retained state has seen: those of the stored state the request continued from (0: from zero), its prompt, and all of
+    its n_ids returned ids but the last, which was drawn and never fed back."""
+    if prompt_len < 1 or n_ids < 1 or base_tokens < 0:
+        raise ValueError(f"base_tokens = {base_tokens}, prompt_len = {prompt_len}, n_ids = {n_ids}: a request has a prompt and at least one id")
+    return int(base_tokens) + int(prompt_len) + int(n_ids) - 1
 
 
 def rank_candidates(cum_lp, lengths, length_normalize: bool = True) -> List[int]:
@@ -304,18 +317,38 @@ class ContinuousDecoder:
     overlap: ahead of a PackedPrefill whose zero marks are per sequence; overlap: on the side stream into the staging rows).  The
     name is pinned in the store from submit() until its admission has read the row.  A seeded request's ids do not depend on its
     slot or on when it is admitted, as for any request (graph / overlap: for the same pack composition).  Without a store every
-    code path and launch is the one of before."""
+    code path and launch is the one of before.
+
+    Retained states: with state_store=store and retain=True a request may name the state it leaves behind, submit(..., retain="turn1"),
+    and that state becomes an ordinary stored state "turn1" when step() / run() returns the handle.  The store row is taken at submit
+    (StateStore.reserve_pending: not servable, not free); the captured step ends with one rwkv7_cache_rows_retain_bf16 launch, which
+    copies the row of a slot it finds armed and dead into the slot's store row and disarms the slot -- in the very step in which the
+    request ends, because later steps run the dead slot's row through stale inputs and, with an EOS, the host learns of the end up to
+    check_every replays late.  Admission issues the same launch after its draw, so a request that ends with its first id is retained
+    too.  THE RETAINED STATE is the state after the prompt and all returned ids BUT THE LAST: the last id was drawn and never fed
+    back.  To continue, submit(state="turn1", input_ids=[ids[-1], ...]) -- without ids[-1] if it is the EOS; store.tokens counts base
+    state + prompt + n - 1 (retained_tokens).  retain= and state= may be combined: the source row stays pinned until admission, the
+    target is another, pending row.  retain=True needs a store and is not supported with admission="overlap" (ValueError), nor is
+    submit_n(n > 1, retain=...).  An engine that is dropped with requests in flight leaves their names pending: store.abandon(name)
+    frees the rows (store.pending() lists them).  retain=True changes no id; without it every code path and launch is the one of before."""
 
     logprobs = False   # the default of the constructor's switch; nothing below looks at tok_lp / cum_lp without it
     lp = None          # SlotLogprob with logprobs=True: the draws go through rwkv7_sample_slots_lp_f32
     store = None       # the attached StateStore; without one nothing below seeds a row
+    retain = False     # the default of the constructor's switch; without it no launch below retains a row
 
     def __init__(self, model, slots: int = 32, max_new_tokens_cap: int = 3000, eos_token_id: Optional[int] = None,
                  pad_token_id: Optional[int] = None, suppress_tokens: Optional[Sequence[int]] = None, check_every: int = 16,
                  admission: str = "eager", prefill_max_seqs: int = 8, prefill_buckets: Sequence[int] = (256, 512, 1024, 2048, 4096),
-                 overlap_replays: int = 8, logprobs: bool = False, state_store=None):
+                 overlap_replays: int = 8, logprobs: bool = False, state_store=None, retain: bool = False):
         if admission not in ("eager", "graph", "overlap"):
             raise ValueError(f"admission = {admission!r}: 'eager', 'graph' or 'overlap'")
+        if retain and state_store is None:
+            raise ValueError("retain=True needs a state_store: retained states are rows of it")
+        if retain and admission == "overlap":
+            raise ValueError("retain=True is not supported with admission='overlap': its commit step does not carry the slots' retain "
+                             "rows; use admission='eager' or 'graph'")
+        self.retain = bool(retain)
         if overlap_replays < 0:
             raise ValueError("overlap_replays must be >= 0")
         self.admission, self.overlap_replays, self.logprobs = admission, int(overlap_replays), bool(logprobs)
@@ -389,6 +422,12 @@ class ContinuousDecoder:
             self.lp = SlotLogprob(self.tok_lp.data_ptr(), self.cum_lp.data_ptr())
         self._lp_done: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}   # handle -> (tok_lp[:n], cum_lp) until take_logprobs()
         self._fan_tbl = None   # submit_n: the cache's own field table, source and destination of the fan-out copy
+        if self.retain:   # what rwkv7_cache_rows_retain_bf16 reads and writes; retain_row crosses with the parameter block
+            self.armed = torch.zeros(S, dtype=torch.uint8, device=dev)
+            self.ticket = torch.zeros(S, dtype=torch.int32, device=dev)
+            self._par_host["retain_row"] = torch.full((S,), -1, dtype=torch.int32)
+            self._par_dev["retain_row"] = self.retain_row = torch.full((S,), -1, dtype=torch.int32, device=dev)
+            self._cache_tbl()   # built here, not under the capture
 
         self.sched = OverlapScheduler(slots) if admission == "overlap" else GroupScheduler(slots)
         self.dstep = step_for(m.model, m.lm_head, self.cache)
@@ -413,36 +452,52 @@ class ContinuousDecoder:
 
     def _step(self):
         sample_slots(self.dstep(self.x), self.st, None, self.allow_lo, self.allow_hi, self.suppress, self.max_domain, self.lp)
+        if self.retain:
+            self._retain_rows()
+
+    def _retain_rows(self):
+        """The rows of the slots that the draw just ended (armed, dead) -> their store rows, and those slots disarmed: one launch."""
+        from .prefill import cache_rows_retain
+        cfg = self.model.config
+        cache_rows_retain(self._cache_tbl(), self.store.table, self.live, self.armed, self.retain_row, self.ticket, len(self.cache),
+                          cfg.hidden_size, cfg.num_heads)
 
     # ---- public interface ----------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def submit(self, input_ids=None, inputs_embeds=None, max_new_tokens: int = 256, min_new_tokens: int = 0, do_sample: bool = False,
-               temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: Optional[int] = None, state: Optional[str] = None) -> int:
+               temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: Optional[int] = None, state: Optional[str] = None,
+               retain: Optional[str] = None) -> int:
         """Queue one request (a prompt of T ids [T] / [1, T] or embeddings [T, D] / [1, T, D]); returns its handle.  Non-blocking.
         state: the name of a state in the attached store; the prompt (>= 1 token) is then the suffix that continues from it.
-        ValueError without a store, KeyError for a name the store does not hold."""
+        ValueError without a store, KeyError for a name the store does not hold.
+        retain: the name under which the state this request leaves behind is stored once step() / run() has returned the handle: the
+        state after the prompt and all returned ids but the last (continue with state=name, input_ids=[ids[-1], ...]).  ValueError
+        without ContinuousDecoder(..., retain=True) or for a name that is stored or pending, RuntimeError when the store is full."""
         seed = int(fresh_seed() if seed is None else seed) & ((1 << 64) - 1)
         fields = self._request_fields(input_ids, inputs_embeds, max_new_tokens, min_new_tokens, do_sample, temperature, top_k, top_p)
-        return self.sched.submit(seed=seed, **fields, **self._state_fields(state))
+        return self.sched.submit(seed=seed, **fields, **self._store_fields(state, retain))
 
     @torch.no_grad()
     def submit_n(self, n: int, input_ids=None, inputs_embeds=None, max_new_tokens: int = 256, min_new_tokens: int = 0,
                  do_sample: bool = False, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: Optional[int] = None,
-                 state: Optional[str] = None) -> List[int]:
+                 state: Optional[str] = None, retain: Optional[str] = None) -> List[int]:
         """Queue n candidates of ONE prompt (submit()'s arguments): their handles in candidate order.  Candidate i draws with the key
         candidate_seed(seed, i) and is, id for id, the request submit(..., seed=candidate_seed(seed, i)) would be.  The group is admitted
         whole, when n slots are free: the prompt is prefilled once and its cache row copied to the other candidates' rows.
         n > slots: ValueError.  n > 1 with admission="overlap": ValueError (the staging index arrays hold one entry per prompt).
-        state: as for submit(); the group's first candidate is seeded from the stored row and its row fans out as ever."""
+        state: as for submit(); the group's first candidate is seeded from the stored row and its row fans out as ever.
+        retain: as for submit(), for n = 1 only; n > 1: ValueError (one name cannot hold the states of several candidates)."""
         n = int(n)
         if n < 1 or n > self.slots:
             raise ValueError(f"n = {n} candidates outside 1..{self.slots} (slots): a group is admitted whole")
+        if n > 1 and retain is not None:
+            raise ValueError(f"submit_n with n = {n} and retain = {retain!r}: one name holds one state; retain a single request")
         if n > 1 and self.admission == "overlap":
             raise ValueError("submit_n with n > 1 is not supported with admission='overlap': its staging rows and index arrays are sized "
                              "to prompts; use admission='eager' or 'graph'")
         fields = self._request_fields(input_ids, inputs_embeds, max_new_tokens, min_new_tokens, do_sample, temperature, top_k, top_p)
         seed = int(fresh_seed() if seed is None else seed) & ((1 << 64) - 1)
-        fields.update(self._state_fields(state))   # pinned once per group: the first candidate's admission unpins
+        fields.update(self._store_fields(state, retain))   # pinned once per group: the first candidate's admission unpins
         if n == 1:
             return [self.sched.submit(seed=seed, **fields)]
         return self.sched.submit_group(n, [candidate_seed(seed, i) for i in range(n)], **fields)
@@ -464,7 +519,21 @@ class ContinuousDecoder:
             return {}
         if self.store is None:
             raise ValueError(f"state = {state!r} needs ContinuousDecoder(..., state_store=...)")
-        return dict(state=state, state_row=self.store.pin(state))   # KeyError for an unknown name
+        row = self.store.pin(state)   # KeyError for an unknown name
+        return dict(state=state, state_row=row, base_tokens=self.store.tokens[row])
+
+    def _store_fields(self, state, retain) -> dict:
+        """submit(state=..., retain=...): _state_fields plus the pending row of the name to retain under.  Call it last too."""
+        if retain is None:
+            return self._state_fields(state)
+        if not self.retain:
+            raise ValueError(f"retain = {retain!r} needs ContinuousDecoder(..., state_store=..., retain=True)")
+        keep = dict(retain=retain, retain_row=self.store.reserve_pending(retain))   # ValueError: stored or pending; RuntimeError: full
+        try:
+            return dict(keep, **self._state_fields(state))
+        except BaseException:
+            self.store.abandon(retain)
+            raise
 
     def _unpin(self, took):
         for _, r in took:
@@ -557,6 +626,10 @@ class ContinuousDecoder:
             out.append((req.handle, self.seq[s, :n].clone()))
             if self.logprobs:
                 self._lp_done[req.handle] = (self.tok_lp[s, :n].clone(), self.cum_lp[s].clone())
+            if req.retain is not None:   # the step in which the request ended has written the row; the slot's entry goes back to rest
+                self.store.publish(req.retain, retained_tokens(req.base_tokens, req.embeds.shape[0], n))
+                self._par_host["retain_row"][s] = -1
+                self.retain_row[s:s + 1].fill_(-1)
         return out
 
     def _admit(self):
@@ -736,10 +809,20 @@ class ContinuousDecoder:
             ph["top_k"][s] = r.top_k if r.do_sample else 0
             ph["top_p"][s] = r.top_p
             ph["do_sample"][s] = int(r.do_sample)
+            if self.retain:
+                ph["retain_row"][s] = -1 if r.retain_row is None else r.retain_row
+        if self.retain:
+            from .prefill import check_retain_rows
+            check_retain_rows(ph["retain_row"].tolist(), self.store.capacity)
         for k, v in ph.items():
             self._par_dev[k].copy_(v.pin_memory(), non_blocking=True)
         self.step_t.index_fill_(0, rows64, 0)
         self.live.index_fill_(0, rows64, 1)
         if self.logprobs:
             self.cum_lp.index_fill_(0, rows64, 0)
+        arm = [s for s, r in took if r.retain_row is not None]
+        if arm:
+            self.armed.index_fill_(0, torch.tensor(arm, dtype=torch.int64).to(self.device, non_blocking=True), 1)
         sample_slots(logits, self.st, row_slot, self.allow_lo, self.allow_hi, self.suppress, self.max_domain, self.lp)
+        if self.retain:
+            self._retain_rows()   # a request that ends with its first id leaves the state after its prompt

@@ -244,6 +244,15 @@ int rwkv7_cache_rows_seed_bf16(int layers, int n, const void *const *src_tbl, vo
     if (rc) return rc < 0 ? rc : RWKV7_OK;
     return rwkv7::cache_rows_seed_bf16(layers, n, src_tbl, dst_tbl, src_row, dst_row, D, H, (hipStream_t)stream);
 }
+// slot rows -> stored rows inside the captured step (rwkvtts_amd/continuous.py, retain=True): which slots are copied is device data
+int rwkv7_cache_rows_retain_bf16(int layers, int slots, const void *const *src_tbl, void *const *dst_tbl, const unsigned char *live,
+                                 unsigned char *armed, const int *retain_row, int *ticket, int D, int H, rwkv7_stream_t stream) {
+    const int rc = cache_rows_check(layers, slots, src_tbl, dst_tbl, retain_row, ticket, D, H);
+    if (rc < 0) return rc;
+    if (!live || !armed || !retain_row || !ticket) return RWKV7_EINVAL;
+    if (rc) return RWKV7_OK;
+    return rwkv7::cache_rows_retain_bf16(layers, slots, src_tbl, dst_tbl, live, armed, retain_row, ticket, D, H, (hipStream_t)stream);
+}
 // state tuning (rwkvtts_amd/state_tune.py): master rows -> training cache rows, and the AdamW step of the voices of a batch.  The
 // shape checks are cache_rows_check's (a table stands in for the index arrays it also wants).
 int rwkv7_state_rows_expand_f32(int layers, int n, const void *const *master_tbl, void *const *dst_tbl, const int *voice, int D, int H,

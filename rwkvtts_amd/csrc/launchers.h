@@ -121,6 +121,8 @@ int cache_rows_commit_bf16(int layers, int n, const void *const *src_tbl, void *
                            int D, int H, hipStream_t stream);
 int cache_rows_seed_bf16(int layers, int n, const void *const *src_tbl, void *const *dst_tbl, const int *src_row, const int *dst_row,
                          int D, int H, hipStream_t stream);   // src_row == RWKV7_SEED_ZERO: zeros instead of a copy
+int cache_rows_retain_bf16(int layers, int slots, const void *const *src_tbl, void *const *dst_tbl, const unsigned char *live,
+                           unsigned char *armed, const int *retain_row, int *ticket, int D, int H, hipStream_t stream);   // slots >= 1
 
 // ---- state tuning (state_tune.hip): fp32 master states of named voices -> rows of a bf16 cache, and their AdamW step from the
 //      cache's leaf gradients straight into the serving cache's rows.  skip_flag may be NULL; A >= 1, n >= 1

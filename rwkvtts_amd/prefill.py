@@ -219,6 +219,28 @@ def cache_rows_seed(src_tbl, dst_tbl, src_row, dst_row, n: int, layers: int, D: 
     _lib.call("rwkv7_cache_rows_seed_bf16", dst_tbl, int(layers), int(n), src_tbl, dst_tbl, src_row, dst_row, int(D), int(H))
 
 
+def check_retain_rows(rows: Sequence[int], capacity: int) -> List[int]:
+    """Host check of the per-slot destination rows of rwkv7_cache_rows_retain_bf16 before they go to the device (the kernel does not
+    check them): a negative entry names no row; the others lie in [0, capacity) -- inside the store -- and are distinct."""
+    rows = [int(r) for r in rows]
+    act = [r for r in rows if r >= 0]
+    if any(r >= capacity for r in act) or len(set(act)) != len(act):
+        raise ValueError(f"retain rows {rows}: the non-negative entries must be distinct rows in [0, {capacity})")
+    return rows
+
+
+def cache_rows_retain(src_tbl, dst_tbl, live, armed, retain_row, ticket, layers: int, D: int, H: int):
+    """rwkv7_cache_rows_retain_bf16 on the current stream, one entry per slot (live.numel() slots): src_tbl / dst_tbl from
+    cache_field_table (the engine's cache of at least that many rows, the store's cache), live / armed uint8 and retain_row / ticket
+    int32 device tensors of one entry per slot; ticket is zero between launches, and the values of retain_row are the caller's
+    guarantee (check_retain_rows)."""
+    slots = live.numel()
+    for t, dt in ((live, torch.uint8), (armed, torch.uint8), (retain_row, torch.int32), (ticket, torch.int32)):
+        assert t.dtype == dt and t.is_contiguous() and t.is_cuda and t.numel() == slots
+    assert src_tbl.dtype == torch.int64 and dst_tbl.dtype == torch.int64 and src_tbl.numel() == dst_tbl.numel() == 3 * layers
+    _lib.call("rwkv7_cache_rows_retain_bf16", dst_tbl, int(layers), slots, src_tbl, dst_tbl, live, armed, retain_row, ticket, int(D), int(H))
+
+
 class _Bucket:
     def __init__(self, t_al, max_seqs, D, dev):
         self.t_al = t_al

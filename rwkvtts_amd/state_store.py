@@ -7,7 +7,9 @@ suffix) continues from the stored row instead of prefilling the prefix again.
 A StateStore is a Cache of `capacity` rows plus host bookkeeping (name -> row, a free list, tokens per row, pin counts).  Rows get
 in by capture() (the model's own packed-row forward into the row), by put() (a row of any compatible Cache, for instance a tuned
 initial state) or by load(); they get out through rwkv7_cache_rows_seed_bf16 (csrc/cache_rows.hip), which copies stored rows and
-zero rows into an engine's rows in one launch with the choice as device data.
+zero rows into an engine's rows in one launch with the choice as device data.  A running engine can also write a row itself: a
+request submitted with retain=name holds a PENDING row (reserve_pending) that the engine's captured step fills when the request ends
+(rwkv7_cache_rows_retain_bf16) and publish() then turns into an ordinary stored state.
 
 The store issues its device work on the current stream and is meant to be used from the stream the engine steps on: a capture()
 issued before a submit() is then visible to the admission that reads it (overlapped admission orders its side stream after that
@@ -49,6 +51,7 @@ class StateStore:
         self._free: List[int] = list(range(capacity))   # ascending; a new name takes the lowest free row
         self.tokens: List[int] = [0] * capacity  # per row: tokens the state has seen (bookkeeping only)
         self._pins: Dict[str, int] = {}          # name -> queued requests that refer to it
+        self._pending: Dict[str, int] = {}       # name -> row held for a state an engine has yet to write (reserve_pending)
         self._table = None
 
     # ---- bookkeeping (host only) ---------------------------------------------------------------------------------------------------
@@ -72,6 +75,8 @@ class StateStore:
         already stored keeps its row unless it is pinned; a full store raises."""
         if not isinstance(name, str) or not name:
             raise ValueError(f"a state's name is a non-empty string, got {name!r}")
+        if name in self._pending:
+            raise ValueError(f"state {name!r} is pending: a running request will write it (publish or abandon it first)")
         if name in self._rows:
             if self._pins.get(name):
                 raise RuntimeError(f"state {name!r} is pinned by {self._pins[name]} queued request(s): it cannot be replaced")
@@ -112,6 +117,42 @@ class StateStore:
 
     def pinned(self, name: str) -> int:
         return self._pins.get(name, 0)
+
+    # A PENDING name holds a row that a running request will write when it ends (ContinuousDecoder(..., retain=True).submit(retain=
+    # name)).  Until publish() it is not servable: `in`, len(), names(), row(), pin() and save() do not see it, and the row is not free.
+    def reserve_pending(self, name: str) -> int:
+        """Take the lowest free row for `name` without making the name servable: the row.  ValueError for a name that is stored or
+        already pending, RuntimeError when the store is full."""
+        if not isinstance(name, str) or not name:
+            raise ValueError(f"a state's name is a non-empty string, got {name!r}")
+        if name in self._rows or name in self._pending:
+            raise ValueError(f"state {name!r} is already {'stored' if name in self._rows else 'pending'}: evict it or choose another name")
+        if not self._free:
+            raise RuntimeError(f"the state store is full ({self.capacity} rows): evict a name first")
+        row = self._free.pop(0)
+        self._pending[name] = row
+        return row
+
+    def _take_pending(self, name: str) -> int:
+        try:
+            return self._pending.pop(name)
+        except KeyError:
+            raise KeyError(f"no pending state named {name!r} (pending: {self.pending()})") from None
+
+    def publish(self, name: str, tokens: int = 0) -> int:
+        """The pending row has been written: `name` is an ordinary stored state of `tokens` tokens from now on.  Its row."""
+        row = self._take_pending(name)
+        self._rows[name] = row
+        self.tokens[row] = int(tokens)
+        return row
+
+    def abandon(self, name: str):
+        """Give a pending name's row back (its request will never finish, for instance because its engine was dropped)."""
+        self._free.append(self._take_pending(name))
+        self._free.sort()
+
+    def pending(self) -> List[str]:
+        return list(self._pending)
 
     def compatible(self, cfg, dtype, device) -> Optional[str]:
         """None if rows of this store fit a cache of (cfg, dtype) on `device`, else why not."""
