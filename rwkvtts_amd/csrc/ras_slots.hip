@@ -39,8 +39,8 @@ struct RasSlotStateLp : RasSlotState {
     float *end_lp;    // [slots]
 };
 
-// The body repeats ras_step_kernel's draw statement for statement, with the slot's fields in place of the launch's arguments, so
-// that the id equals that kernel's bit for bit and csrc/sampling.hip stays as it is.  Every lane reads live[s], step[s] and the
+// The draw is the one body that ras_step_kernel calls too (ras_row_stats + ras_pick, csrc/sampling_common.h), with the slot's fields
+// in place of the launch's arguments, so the id equals that kernel's bit for bit.  Every lane reads live[s], step[s] and the
 // ring before the first barrier; lane 0 writes them after the last one, so the early exit is uniform over the workgroup.
 //
 // LP (rwkv7_ras_slots_lp_f32): the log-probability of the drawn id as well.  Everything under `if constexpr (LP)` is extra; with
@@ -75,13 +75,9 @@ __global__ __launch_bounds__(kSmpThreads) void ras_slots_kernel(int V, const flo
     const bool ignore_eos = st < a.n_ignore[s];
     const uint2 key = make_uint2((uint32_t)a.seed[s], (uint32_t)(a.seed[s] >> 32));
     const uint4 r = philox(make_uint4((uint32_t)st, (uint32_t)((uint64_t)st >> 32), 0u, 0x7a5u), key);
-    const unsigned long long kmx = block_max(x.local_max(), sm, 0);
-    const float mx = key_val(kmx);
-    const int imx = key_idx(kmx);
-    float zs = 0.f;
-#pragma unroll
-    for (int e = 0; e < EPT; e++) zs += __expf(x.v[e] - mx);
-    const float z = block_sum(zs, sm);
+    float mx, z;
+    int imx;
+    ras_row_stats(x, sm, mx, imx, z);
     float lp_z = z;   // LP: the exp-sum over the ids this draw can produce
     if constexpr (LP) {
         if (ignore_eos) {   // uniform over the workgroup
@@ -91,36 +87,8 @@ __global__ __launch_bounds__(kSmpThreads) void ras_slots_kernel(int V, const flo
             lp_z = block_sum(ws, sm);
         }
     }
-    int full, alt;
-    draw_full(x, sm, mx, ignore_eos ? eos : -1, u01(r.x), u01(r.y), full, alt);
-    if (full < 0) full = imx;
-    if (alt < 0) alt = imx;
-    const int nc = select_bins(x, sm, min(top_k, V), false);
-    const float pj = tid < nc ? __expf(sm.cand_v[tid] - mx) / z : 0.f;
-    float tot;
-    const float cj = block_scan(pj, tot, sm);
-    const bool keep = tid < nc && cj - pj < top_p;
-    const float wj = keep && !(ignore_eos && sm.cand_i[min(tid, kSmpMaxCand - 1)] == eos) ? pj : 0.f;
-    float mass;
-    const float mj = block_scan(wj, mass, sm);
-    if (tid == 0) {
-        sm.pick[0] = 0x7fffffff;
-        sm.pick[1] = -1;
-    }
-    __syncthreads();
-    const float target = u01(r.z) * mass;
-    if (wj > 0.f) {
-        if (mj > target) atomicMin(&sm.pick[0], tid);
-        atomicMax(&sm.pick[1], tid);
-    }
-    __syncthreads();
-    if (tid < 64) {
-        int cand = alt;
-        if (mass > 0.f) cand = sm.cand_i[sm.pick[0] != 0x7fffffff ? sm.pick[0] : sm.pick[1]];
-        int rep = 0;
-        for (int w0 = 0; w0 < win_size; w0 += 64) rep += __popcll(__ballot(w0 + tid < win_size && rc[w0 / 64] == (long)cand));
-        if (tid == 0) sm.sel[3] = (unsigned)((float)rep >= (float)win_size * tau_r ? full : cand);
-    }
+    const int pick = ras_pick(x, sm, V, mx, imx, z, ignore_eos, eos, top_p, top_k, win_size, tau_r, r, rc);
+    if (tid == 0) sm.sel[3] = (unsigned)pick;   // lane 0 of wave 0, which knows the id
     __syncthreads();
     // every thread holds the same id (it came out of LDS after a barrier); all reads of the slot's state that other lanes make lie
     // before that barrier
@@ -149,11 +117,7 @@ __global__ __launch_bounds__(kSmpThreads) void ras_slots_kernel(int V, const flo
             }
         }
     }
-    if (emit && a.emb) {
-        const uint16_t *src = a.emb + id * a.D;
-        uint16_t *dst = a.x + (long)s * a.D;
-        for (int d = tid * 8; d < a.D; d += kSmpThreads * 8) *reinterpret_cast<uint4 *>(dst + d) = *reinterpret_cast<const uint4 *>(src + d);
-    }
+    if (emit && a.emb) copy_emb_row(a.emb + id * a.D, a.x + (long)s * a.D, a.D);
 }
 
 }  // namespace
@@ -165,12 +129,7 @@ static int launch_ras_slots(int rows, int V, const float *logits, long ld, const
         return -4;   // RWKV7_ESHAPE
     (void)hipGetLastError();
     const dim3 grid(rows), block(kSmpThreads);
-    if (V <= kEptS * kSmpThreads)
-        ras_slots_kernel<kEptS, LP><<<grid, block, 0, stream>>>(V, logits, ld, row_slot, st);
-    else if (V <= kEptM * kSmpThreads)
-        ras_slots_kernel<kEptM, LP><<<grid, block, 0, stream>>>(V, logits, ld, row_slot, st);
-    else
-        ras_slots_kernel<kEptL, LP><<<grid, block, 0, stream>>>(V, logits, ld, row_slot, st);
+    for_ept(V, [&](auto ept) { ras_slots_kernel<decltype(ept)::value, LP><<<grid, block, 0, stream>>>(V, logits, ld, row_slot, st); });
     return (int)hipGetLastError();
 }
 

@@ -69,45 +69,7 @@ __global__ __launch_bounds__(kSmpThreads) void sample_rows_kernel(int nseg, cons
         const int sidx = min_id - lo;
         if (sidx >= 0 && sidx < m && (sidx & (kSmpThreads - 1)) == tid) x.drop(sidx);
     }
-    int choice;
-    if (!do_sample) {
-        choice = key_idx(block_max(x.local_max(), sm, 0));
-    } else {
-        const long st = *step;
-        const uint4 r = philox(make_uint4((uint32_t)st, (uint32_t)((uint64_t)st >> 32), blockIdx.x, 0x5a17u), key);
-        if (top_k > 0) {
-            const int nc = select_bins(x, sm, min(top_k, m), true);
-            // probabilities over the candidates (softmax of the filtered logits), nucleus = the ranks whose strictly-higher mass is
-            // below top_p (TopPLogitsWarper: ascending cumulative <= 1 - top_p is removed, the largest always stays)
-            const float ej = tid < nc ? __expf(sm.cand_v[tid] - sm.cand_v[0]) : 0.f;
-            float z;
-            const float cj = block_scan(ej, z, sm);                     // inclusive mass of ranks 0 .. tid
-            const bool keep = tid < nc && (tid == 0 || cj - ej < top_p * z);   // the kept ranks are a prefix
-            float kept;
-            (void)block_scan(keep ? ej : 0.f, kept, sm);
-            const float target = u01(r.x) * kept;
-            if (tid == 0) sm.pick[1] = 0;
-            __syncthreads();
-            if (keep && cj <= target) atomicAdd(&sm.pick[1], 1);        // ranks passed before the draw's rank
-            __syncthreads();
-            int nk = 0;                                                 // (kept count: the last kept rank catches rounding)
-            {
-                float f;
-                nk = (int)block_scan(keep ? 1.f : 0.f, f, sm);
-                nk = (int)f;
-            }
-            // no candidate survived (every allowed logit is -inf / NaN, or suppression + min_eos cover the allowed range): the torch
-            // chain would raise; here the draw falls back to the first allowed id instead of reading cand_i[-1]
-            if (tid == 0) sm.pick[0] = nk > 0 ? sm.cand_i[min(sm.pick[1], nk - 1)] : 0;
-            __syncthreads();
-            choice = sm.pick[0];
-        } else {   // plain multinomial over the whole segment
-            const unsigned long long k = block_max(x.local_max(), sm, 0);
-            int i0, i1;
-            draw_full(x, sm, key_val(k), -1, u01(r.x), 0.f, i0, i1);
-            choice = i0 >= 0 ? i0 : key_idx(k);
-        }
-    }
+    int choice = warper_draw(x, sm, m, do_sample, top_k, top_p, key, do_sample ? *step : 0L, blockIdx.x);
     choice = min(max(choice, 0), m - 1);   // an id outside [lo, lo + m) never reaches the output or the embedding lookup below
     if (tid == 0) out[(long)row * nseg + seg] = lo + choice;
     if (tail.ids) {   // nseg == 1
@@ -125,11 +87,7 @@ __global__ __launch_bounds__(kSmpThreads) void sample_rows_kernel(int nseg, cons
             sm.sel[0] = (unsigned)id;
         }
         __syncthreads();
-        if (tail.emb) {
-            const uint16_t *src = tail.emb + (long)sm.sel[0] * tail.D;
-            uint16_t *dst = tail.x + (long)row * tail.D;
-            for (int d = tid * 8; d < tail.D; d += kSmpThreads * 8) *reinterpret_cast<uint4 *>(dst + d) = *reinterpret_cast<const uint4 *>(src + d);
-        }
+        if (tail.emb) copy_emb_row(tail.emb + (long)sm.sel[0] * tail.D, tail.x + (long)row * tail.D, tail.D);
     }
 }
 
@@ -153,14 +111,14 @@ struct SlotState {
 // Row r of `logits` belongs to slot s = row_slot[r] (row_slot NULL: s = r).  The draw is the one of sample_rows_kernel for a ONE-row
 // launch (workgroup 0) with the slot's key, step counter, parameters and min-EOS bound, so a request's ids do not depend on the slot
 // it occupies or on when it was admitted; then the slot's bookkeeping (output column, next id, its embedding row, step, live flag).
-// The body repeats sample_rows_kernel's draw instead of sharing it so that the existing kernels stay byte-for-byte as they were.
+// Both kernels call the one draw body, warper_draw (csrc/sampling_common.h); this one passes counter word 0 and the slot's key.
 //
 // LP (rwkv7_sample_slots_lp_f32): the log-probability of the drawn id as well.  Everything under `if constexpr (LP)` is extra; with
 // LP = false the body is the draw as it always was.  The probability is the one of the RAW logits (temperature 1, no top-k / top-p)
 // over the ids the draw could produce at this step -- the allowed range minus `suppress`, minus EOS while it is barred -- so a second
-// copy of the row stays unscaled in registers until its maximum and its exp-sum are known, which is before select_bins needs the
-// registers for its bins.  Both reductions go thread -> wave butterfly -> the four waves in fixed order: the value depends on the
-// row's contents and the thread layout only, never on the row, the slot or the grid.
+// copy of the row stays unscaled in registers until its maximum and its exp-sum are known (raw_logprob_stats), which is before
+// select_bins needs the registers for its bins: the value depends on the row's contents and the thread layout only, never on the
+// row, the slot or the grid.
 struct SlotStateLp : SlotState {
     float *tok_lp;    // [slots][seq_ld]
     double *cum_lp;   // [slots]
@@ -206,49 +164,9 @@ __global__ __launch_bounds__(kSmpThreads) void sample_slots_kernel(const float *
         }
     }
     float lp_max = 0.f, lp_logz = 0.f;   // LP: max and log sum exp(. - max) over the ids that were not dropped
-    if constexpr (LP) {
-        float mx = raw.v[0];
-#pragma unroll
-        for (int e = 1; e < EPT; e++) mx = fmaxf(mx, raw.v[e]);
-        lp_max = block_fmax(mx, sm);
-        float z = 0.f;
-#pragma unroll
-        for (int e = 0; e < EPT; e++) z += __expf(raw.v[e] - lp_max);   // a dropped id: exp(-inf) = 0
-        lp_logz = __logf(block_sum(z, sm));
-        __syncthreads();   // sm.red is free again: select_bins writes it without a barrier of its own
-    }
-    int choice;
-    if (!do_sample) {
-        choice = key_idx(block_max(x.local_max(), sm, 0));
-    } else {
-        const uint2 key = make_uint2((uint32_t)st.seed[s], (uint32_t)(st.seed[s] >> 32));
-        const uint4 r = philox(make_uint4((uint32_t)step, (uint32_t)((uint64_t)step >> 32), 0u, 0x5a17u), key);
-        if (top_k > 0) {
-            const int nc = select_bins(x, sm, min(top_k, m), true);
-            const float ej = tid < nc ? __expf(sm.cand_v[tid] - sm.cand_v[0]) : 0.f;
-            float z;
-            const float cj = block_scan(ej, z, sm);
-            const bool keep = tid < nc && (tid == 0 || cj - ej < top_p * z);
-            float kept;
-            (void)block_scan(keep ? ej : 0.f, kept, sm);
-            const float target = u01(r.x) * kept;
-            if (tid == 0) sm.pick[1] = 0;
-            __syncthreads();
-            if (keep && cj <= target) atomicAdd(&sm.pick[1], 1);
-            __syncthreads();
-            float f;
-            (void)block_scan(keep ? 1.f : 0.f, f, sm);
-            const int nk = (int)f;
-            if (tid == 0) sm.pick[0] = nk > 0 ? sm.cand_i[min(sm.pick[1], nk - 1)] : 0;
-            __syncthreads();
-            choice = sm.pick[0];
-        } else {
-            const unsigned long long k = block_max(x.local_max(), sm, 0);
-            int i0, i1;
-            draw_full(x, sm, key_val(k), -1, u01(r.x), 0.f, i0, i1);
-            choice = i0 >= 0 ? i0 : key_idx(k);
-        }
-    }
+    if constexpr (LP) raw_logprob_stats(raw, sm, lp_max, lp_logz);
+    const uint2 key = make_uint2((uint32_t)st.seed[s], (uint32_t)(st.seed[s] >> 32));
+    const int choice = warper_draw(x, sm, m, do_sample, top_k, top_p, key, step, 0u);
     // every thread holds the same choice (it came out of LDS after a barrier), and every read of the slot's state lies before that barrier
     const long id = lo + min(max(choice, 0), m - 1);
     if (tid == 0) {
@@ -263,11 +181,7 @@ __global__ __launch_bounds__(kSmpThreads) void sample_slots_kernel(const float *
             st.cum_lp[s] += (double)lp;   // one workgroup owns the slot: a plain read, add, store
         }
     }
-    if (st.emb) {
-        const uint16_t *src = st.emb + id * st.D;
-        uint16_t *dst = st.x + (long)s * st.D;
-        for (int d = tid * 8; d < st.D; d += kSmpThreads * 8) *reinterpret_cast<uint4 *>(dst + d) = *reinterpret_cast<const uint4 *>(src + d);
-    }
+    if (st.emb) copy_emb_row(st.emb + id * st.D, st.x + (long)s * st.D, st.D);
 }
 
 // ---- CosyVoice streaming step: draw + bookkeeping --------------------------------------------------------------------------------
@@ -291,55 +205,19 @@ __global__ __launch_bounds__(kSmpThreads) void ras_step_kernel(int V, const floa
     rc[1] = recent[min(64 + tid, win_size - 1)];
     const bool ignore_eos = st < n_ignore;
     const uint4 r = philox(make_uint4((uint32_t)st, (uint32_t)((uint64_t)st >> 32), 0u, 0x7a5u), key);
-    const unsigned long long kmx = block_max(x.local_max(), sm, 0);
-    const float mx = key_val(kmx);
-    const int imx = key_idx(kmx);
-    // softmax denominator over everything (the nucleus is cut on these probabilities, EOS included)
-    float zs = 0.f;
-#pragma unroll
-    for (int e = 0; e < EPT; e++) zs += __expf(x.v[e] - mx);
-    const float z = block_sum(zs, sm);
-    // random_sampling (and the "nucleus is EOS alone" case) from the full distribution, without EOS while it is being rejected
-    int full, alt;
-    draw_full(x, sm, mx, ignore_eos ? eos : -1, u01(r.x), u01(r.y), full, alt);
-    if (full < 0) full = imx;
-    if (alt < 0) alt = imx;
-    const int nc = select_bins(x, sm, min(top_k, V), false);
-    // nucleus_sampling: the sorted prefix with cumulative probability (before adding) < top_p and rank < top_k, without EOS while it
-    // is being rejected; one thread per candidate
-    const float pj = tid < nc ? __expf(sm.cand_v[tid] - mx) / z : 0.f;
-    float tot;
-    const float cj = block_scan(pj, tot, sm);
-    const bool keep = tid < nc && cj - pj < top_p;
-    const float wj = keep && !(ignore_eos && sm.cand_i[min(tid, kSmpMaxCand - 1)] == eos) ? pj : 0.f;
-    float mass;
-    const float mj = block_scan(wj, mass, sm);
-    if (tid == 0) {
-        sm.pick[0] = 0x7fffffff;   // first kept rank whose inclusive mass exceeds the target
-        sm.pick[1] = -1;           // last kept rank (a target that rounding pushed past the end)
-    }
-    __syncthreads();
-    const float target = u01(r.z) * mass;
-    if (wj > 0.f) {
-        if (mj > target) atomicMin(&sm.pick[0], tid);
-        atomicMax(&sm.pick[1], tid);
-    }
-    __syncthreads();
-    if (tid < 64) {
-        int cand = alt;   // the kept set holds nothing but EOS
-        if (mass > 0.f) cand = sm.cand_i[sm.pick[0] != 0x7fffffff ? sm.pick[0] : sm.pick[1]];
-        int rep = 0;
-        for (int w0 = 0; w0 < win_size; w0 += 64) rep += __popcll(__ballot(w0 + tid < win_size && rc[w0 / 64] == (long)cand));
-        if (tid == 0) {
-            const long id = (float)rep >= (float)win_size * tau_r ? (long)full : (long)cand;
-            *tok = id;
-            if (id != (long)eos) {   // the reference appends emitted ids only
-                const long p = *ptr;
-                recent[p] = id;
-                *ptr = (p + 1) % win_size;
-            }
-            *step_i = st + 1;
+    float mx, z;
+    int imx;
+    ras_row_stats(x, sm, mx, imx, z);
+    const int pick = ras_pick(x, sm, V, mx, imx, z, ignore_eos, eos, top_p, top_k, win_size, tau_r, r, rc);
+    if (tid == 0) {   // lane 0 of wave 0, which knows the id
+        const long id = pick;
+        *tok = id;
+        if (id != (long)eos) {   // the reference appends emitted ids only
+            const long p = *ptr;
+            recent[p] = id;
+            *ptr = (p + 1) % win_size;
         }
+        *step_i = st + 1;
     }
 }
 
@@ -407,44 +285,13 @@ __global__ __launch_bounds__(64) void xy_frame_kernel(XYFrameArgs a, const long 
     }
 }
 
-// the next frame's input: x[b] = emb_0[row[b][0]] + emb_1[row[b][1]] + ... in bf16, added in channel order like the module
-// (model/llm/xy_llm.py:189-200: a chain of bf16 tensor additions)
-constexpr int kXYMaxC = 16;
+// the next frame's input: x[b] = emb_0[row[b][0]] + emb_1[row[b][1]] + ... in bf16 (xy_embed_sum, csrc/sampling_common.h)
 struct XYTables {
     const uint16_t *t[kXYMaxC];
 };
 __global__ __launch_bounds__(256) void xy_embed_kernel(int C, int D, XYTables tb, const long *__restrict__ row, uint16_t *__restrict__ x) {
     const int b = blockIdx.x;
-    for (int d = threadIdx.x * 8; d < D; d += 256 * 8) {
-        float acc[8];
-#pragma unroll
-        for (int c = 0; c < kXYMaxC; c++) {
-            if (c < C) {
-                const uint4 r = *reinterpret_cast<const uint4 *>(tb.t[c] + row[(long)b * C + c] * D + d);
-                const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const float lo = __uint_as_float(w[j] << 16), hi = __uint_as_float(w[j] & 0xffff0000u);
-                    if (c == 0) {
-                        acc[2 * j] = lo;
-                        acc[2 * j + 1] = hi;
-                    } else {   // bf16 + bf16 -> bf16 (round to nearest even), as torch adds two bf16 tensors
-                        float s0 = acc[2 * j] + lo, s1 = acc[2 * j + 1] + hi;
-                        uint32_t u0 = __float_as_uint(s0), u1 = __float_as_uint(s1);
-                        u0 += 0x7fffu + ((u0 >> 16) & 1u);
-                        u1 += 0x7fffu + ((u1 >> 16) & 1u);
-                        acc[2 * j] = __uint_as_float(u0 & 0xffff0000u);
-                        acc[2 * j + 1] = __uint_as_float(u1 & 0xffff0000u);
-                    }
-                }
-            }
-        }
-        uint4 o;
-        uint32_t *ow = reinterpret_cast<uint32_t *>(&o);
-#pragma unroll
-        for (int j = 0; j < 4; j++) ow[j] = (__float_as_uint(acc[2 * j]) >> 16) | (__float_as_uint(acc[2 * j + 1]) & 0xffff0000u);
-        *reinterpret_cast<uint4 *>(x + (long)b * D + d) = o;
-    }
+    xy_embed_sum(C, D, tb.t, row + (long)b * C, x + (long)b * D);
 }
 
 }  // namespace
@@ -464,31 +311,29 @@ int sample_rows_f32(int rows, int nseg, const float *logits, long ld, const int 
     const float it = do_sample ? 1.f / temperature : 1.f;
     const uint2 key = make_uint2((uint32_t)seed, (uint32_t)(seed >> 32));
     const dim3 grid(rows * nseg), block(kSmpThreads);
-    if (max_domain <= kEptS * kSmpThreads)
-        sample_rows_kernel<kEptS><<<grid, block, 0, st>>>(nseg, logits, ld, seg_off, seg_len, allow_lo, allow_hi, suppress, nsuppress, do_sample,
-                                                          top_k, top_p, it, key, step, out, tail, min_id, min_until);
-    else if (max_domain <= kEptM * kSmpThreads)
-        sample_rows_kernel<kEptM><<<grid, block, 0, st>>>(nseg, logits, ld, seg_off, seg_len, allow_lo, allow_hi, suppress, nsuppress, do_sample,
-                                                          top_k, top_p, it, key, step, out, tail, min_id, min_until);
-    else
-        sample_rows_kernel<kEptL><<<grid, block, 0, st>>>(nseg, logits, ld, seg_off, seg_len, allow_lo, allow_hi, suppress, nsuppress, do_sample,
-                                                          top_k, top_p, it, key, step, out, tail, min_id, min_until);
+    for_ept(max_domain, [&](auto ept) {
+        sample_rows_kernel<decltype(ept)::value><<<grid, block, 0, st>>>(nseg, logits, ld, seg_off, seg_len, allow_lo, allow_hi, suppress, nsuppress,
+                                                                         do_sample, top_k, top_p, it, key, step, out, tail, min_id, min_until);
+    });
+    return (int)hipGetLastError();
+}
+
+template <bool LP, typename State>
+static int launch_sample_slots(int rows, const float *logits, long ld, const int *row_slot, const int *allow_lo, const int *allow_hi,
+                               const int *suppress, int nsuppress, int max_domain, const State &st, hipStream_t stream) {
+    if (max_domain > kSmpMaxN || nsuppress > 256 || st.top_k_max < 0 || st.top_k_max > 64 || (st.emb && st.D % 8 != 0)) return -4;
+    (void)hipGetLastError();
+    const dim3 grid(rows), block(kSmpThreads);
+    for_ept(max_domain, [&](auto ept) {
+        sample_slots_kernel<decltype(ept)::value, LP><<<grid, block, 0, stream>>>(logits, ld, row_slot, allow_lo, allow_hi, suppress, nsuppress,
+                                                                                  max_domain, st);
+    });
     return (int)hipGetLastError();
 }
 
 int sample_slots_f32(int rows, const float *logits, long ld, const int *row_slot, const int *allow_lo, const int *allow_hi,
                      const int *suppress, int nsuppress, int max_domain, const void *st_, hipStream_t stream) {
-    const SlotState st = *(const SlotState *)st_;
-    if (max_domain > kSmpMaxN || nsuppress > 256 || st.top_k_max < 0 || st.top_k_max > 64 || (st.emb && st.D % 8 != 0)) return -4;
-    (void)hipGetLastError();
-    const dim3 grid(rows), block(kSmpThreads);
-    if (max_domain <= kEptS * kSmpThreads)
-        sample_slots_kernel<kEptS, false><<<grid, block, 0, stream>>>(logits, ld, row_slot, allow_lo, allow_hi, suppress, nsuppress, max_domain, st);
-    else if (max_domain <= kEptM * kSmpThreads)
-        sample_slots_kernel<kEptM, false><<<grid, block, 0, stream>>>(logits, ld, row_slot, allow_lo, allow_hi, suppress, nsuppress, max_domain, st);
-    else
-        sample_slots_kernel<kEptL, false><<<grid, block, 0, stream>>>(logits, ld, row_slot, allow_lo, allow_hi, suppress, nsuppress, max_domain, st);
-    return (int)hipGetLastError();
+    return launch_sample_slots<false>(rows, logits, ld, row_slot, allow_lo, allow_hi, suppress, nsuppress, max_domain, *(const SlotState *)st_, stream);
 }
 
 int sample_slots_lp_f32(int rows, const float *logits, long ld, const int *row_slot, const int *allow_lo, const int *allow_hi,
@@ -497,16 +342,7 @@ int sample_slots_lp_f32(int rows, const float *logits, long ld, const int *row_s
     static_cast<SlotState &>(st) = *(const SlotState *)st_;
     st.tok_lp = tok_lp;
     st.cum_lp = cum_lp;
-    if (max_domain > kSmpMaxN || nsuppress > 256 || st.top_k_max < 0 || st.top_k_max > 64 || (st.emb && st.D % 8 != 0)) return -4;
-    (void)hipGetLastError();
-    const dim3 grid(rows), block(kSmpThreads);
-    if (max_domain <= kEptS * kSmpThreads)
-        sample_slots_kernel<kEptS, true><<<grid, block, 0, stream>>>(logits, ld, row_slot, allow_lo, allow_hi, suppress, nsuppress, max_domain, st);
-    else if (max_domain <= kEptM * kSmpThreads)
-        sample_slots_kernel<kEptM, true><<<grid, block, 0, stream>>>(logits, ld, row_slot, allow_lo, allow_hi, suppress, nsuppress, max_domain, st);
-    else
-        sample_slots_kernel<kEptL, true><<<grid, block, 0, stream>>>(logits, ld, row_slot, allow_lo, allow_hi, suppress, nsuppress, max_domain, st);
-    return (int)hipGetLastError();
+    return launch_sample_slots<true>(rows, logits, ld, row_slot, allow_lo, allow_hi, suppress, nsuppress, max_domain, st, stream);
 }
 
 int ras_step_f32(int V, const float *logits, long *tok, long *recent, long *ptr, long *step_i, long n_ignore, int eos, float top_p,
@@ -514,12 +350,10 @@ int ras_step_f32(int V, const float *logits, long *tok, long *recent, long *ptr,
     if (V > kSmpMaxN || top_k < 1 || top_k > kSmpMaxCand || win_size < 1 || win_size > 128) return -4;
     (void)hipGetLastError();
     const uint2 key = make_uint2((uint32_t)seed, (uint32_t)(seed >> 32));
-    if (V <= kEptS * kSmpThreads)
-        ras_step_kernel<kEptS><<<dim3(1), dim3(kSmpThreads), 0, st>>>(V, logits, tok, recent, ptr, step_i, n_ignore, eos, top_p, top_k, win_size, tau_r, key);
-    else if (V <= kEptM * kSmpThreads)
-        ras_step_kernel<kEptM><<<dim3(1), dim3(kSmpThreads), 0, st>>>(V, logits, tok, recent, ptr, step_i, n_ignore, eos, top_p, top_k, win_size, tau_r, key);
-    else
-        ras_step_kernel<kEptL><<<dim3(1), dim3(kSmpThreads), 0, st>>>(V, logits, tok, recent, ptr, step_i, n_ignore, eos, top_p, top_k, win_size, tau_r, key);
+    for_ept(V, [&](auto ept) {
+        ras_step_kernel<decltype(ept)::value><<<dim3(1), dim3(kSmpThreads), 0, st>>>(V, logits, tok, recent, ptr, step_i, n_ignore, eos, top_p, top_k,
+                                                                                     win_size, tau_r, key);
+    });
     return (int)hipGetLastError();
 }
 

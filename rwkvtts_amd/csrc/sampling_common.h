@@ -1,9 +1,12 @@
 // rwkvtts_amd/csrc/sampling_common.h -- what the token-draw kernels share (csrc/sampling.hip, csrc/xy_slots.hip, csrc/ras_slots.hip): the Philox generator,
-// the (value, index) keys and block-wide reductions, the top-k selections and the multinomial draw.  Everything here is inline
-// device code in an anonymous namespace: each translation unit gets its own copy.
+// the (value, index) keys and block-wide reductions, the top-k selections and the multinomial draw, then the draw bodies themselves
+// (warper_draw, raw_logprob_stats, ras_row_stats + ras_pick), the embedding helpers and the host-side choice of the elements-per-thread
+// class.  Everything here is inline code in an anonymous namespace: each translation unit gets its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 namespace rwkv7 {
 namespace {
@@ -378,8 +381,178 @@ __device__ __forceinline__ void draw_full(const Vals<EPT> &x, SmpShared &sm, flo
     i1 = sm.pick[1];
 }
 
+
+// ---- the draw bodies: each is written once here and called by the closed-batch kernel and by its per-slot twins --------------------
+// Everything below holds barriers: all 256 threads of the workgroup call it, with workgroup-uniform scalar arguments.
+
+// HF's warper chain for one segment of m ids in x (already scaled by 1 / temperature): argmax, or top-k -> top-p -> a Philox inverse
+// CDF over the kept ranks, or (top_k == 0) plain multinomial over the whole segment.  Returns the index inside the segment on every
+// thread, not yet clamped.  Philox counter = (step lo, step hi, word2, 0x5a17); the callers differ in what they pass:
+//   sample_rows_kernel (csrc/sampling.hip)   word2 = workgroup index   key = the launch's
+//   sample_slots_kernel (csrc/sampling.hip)  word2 = 0                 key = seed[s]     (a one-row launch: workgroup 0)
+//   xy_slot_draw_kernel (csrc/xy_slots.hip)  word2 = channel           key = seed[s]     (a one-row launch of C segments)
+template <int EPT>
+__device__ __forceinline__ int warper_draw(Vals<EPT> &x, SmpShared &sm, int m, int do_sample, int top_k, float top_p, uint2 key, long step,
+                                           uint32_t word2) {
+    const int tid = threadIdx.x;
+    if (!do_sample) return key_idx(block_max(x.local_max(), sm, 0));
+    const uint4 r = philox(make_uint4((uint32_t)step, (uint32_t)((uint64_t)step >> 32), word2, 0x5a17u), key);
+    if (top_k > 0) {
+        const int nc = select_bins(x, sm, min(top_k, m), true);
+        // probabilities over the candidates (softmax of the filtered logits), nucleus = the ranks whose strictly-higher mass is
+        // below top_p (TopPLogitsWarper: ascending cumulative <= 1 - top_p is removed, the largest always stays)
+        const float ej = tid < nc ? __expf(sm.cand_v[tid] - sm.cand_v[0]) : 0.f;
+        float z;
+        const float cj = block_scan(ej, z, sm);                     // inclusive mass of ranks 0 .. tid
+        const bool keep = tid < nc && (tid == 0 || cj - ej < top_p * z);   // the kept ranks are a prefix
+        float kept;
+        (void)block_scan(keep ? ej : 0.f, kept, sm);
+        const float target = u01(r.x) * kept;
+        if (tid == 0) sm.pick[1] = 0;
+        __syncthreads();
+        if (keep && cj <= target) atomicAdd(&sm.pick[1], 1);        // ranks passed before the draw's rank
+        __syncthreads();
+        float f;                                                    // (kept count: the last kept rank catches rounding)
+        (void)block_scan(keep ? 1.f : 0.f, f, sm);
+        const int nk = (int)f;
+        // no candidate survived (every allowed logit is -inf / NaN, or suppression + min_eos cover the allowed range): the torch
+        // chain would raise; here the draw falls back to the first allowed id instead of reading cand_i[-1]
+        if (tid == 0) sm.pick[0] = nk > 0 ? sm.cand_i[min(sm.pick[1], nk - 1)] : 0;
+        __syncthreads();
+        return sm.pick[0];
+    }
+    // plain multinomial over the whole segment
+    const unsigned long long k = block_max(x.local_max(), sm, 0);
+    int i0, i1;
+    draw_full(x, sm, key_val(k), -1, u01(r.x), 0.f, i0, i1);
+    return i0 >= 0 ? i0 : key_idx(k);
+}
+
+// The draw-time log-probabilities of the LP instantiations (sample_slots_kernel, xy_slot_draw_kernel): maximum and log sum exp(. - max)
+// of the RAW logits over the ids that were not dropped.  Both reductions go thread -> wave butterfly -> the four waves in fixed order.
+template <int EPT>
+__device__ __forceinline__ void raw_logprob_stats(const Vals<EPT> &raw, SmpShared &sm, float &lp_max, float &lp_logz) {
+    float mx = raw.v[0];
+#pragma unroll
+    for (int e = 1; e < EPT; e++) mx = fmaxf(mx, raw.v[e]);
+    lp_max = block_fmax(mx, sm);
+    float z = 0.f;
+#pragma unroll
+    for (int e = 0; e < EPT; e++) z += __expf(raw.v[e] - lp_max);   // a dropped id, or beyond the range: exp(-inf) = 0
+    lp_logz = __logf(block_sum(z, sm));
+    __syncthreads();   // sm.red is free again: select_bins writes it without a barrier of its own
+}
+
+// CosyVoice's repetition-aware draw in two halves (ras_step_kernel in csrc/sampling.hip; ras_slots_kernel in csrc/ras_slots.hip, whose
+// LP form needs mx and z -- and x intact for its EOS-masked exp-sum -- before the selection destroys x).
+// 1. the row's maximum (value mx, index imx) and the softmax denominator z over everything (the nucleus is cut on these
+//    probabilities, EOS included)
+template <int EPT>
+__device__ __forceinline__ void ras_row_stats(const Vals<EPT> &x, SmpShared &sm, float &mx, int &imx, float &z) {
+    const unsigned long long kmx = block_max(x.local_max(), sm, 0);
+    mx = key_val(kmx);
+    imx = key_idx(kmx);
+    float zs = 0.f;
+#pragma unroll
+    for (int e = 0; e < EPT; e++) zs += __expf(x.v[e] - mx);
+    z = block_sum(zs, sm);
+}
+// 2. the pick.  r = philox((step lo, step hi, 0, 0x7a5), key): r.x draws `full`, r.y `alt`, r.z the nucleus rank.  rc = the ring of
+//    recent ids, one entry per lane of wave 0 (win_size <= 128).  The id is returned on wave 0 only (other waves get 0), unclamped.
+template <int EPT>
+__device__ __forceinline__ int ras_pick(Vals<EPT> &x, SmpShared &sm, int V, float mx, int imx, float z, bool ignore_eos, int eos, float top_p,
+                                        int top_k, int win_size, float tau_r, uint4 r, const long (&rc)[2]) {
+    const int tid = threadIdx.x;
+    // random_sampling (and the "nucleus is EOS alone" case) from the full distribution, without EOS while it is being rejected
+    int full, alt;
+    draw_full(x, sm, mx, ignore_eos ? eos : -1, u01(r.x), u01(r.y), full, alt);
+    if (full < 0) full = imx;
+    if (alt < 0) alt = imx;
+    const int nc = select_bins(x, sm, min(top_k, V), false);
+    // nucleus_sampling: the sorted prefix with cumulative probability (before adding) < top_p and rank < top_k, without EOS while it
+    // is being rejected; one thread per candidate
+    const float pj = tid < nc ? __expf(sm.cand_v[tid] - mx) / z : 0.f;
+    float tot;
+    const float cj = block_scan(pj, tot, sm);
+    const bool keep = tid < nc && cj - pj < top_p;
+    const float wj = keep && !(ignore_eos && sm.cand_i[min(tid, kSmpMaxCand - 1)] == eos) ? pj : 0.f;
+    float mass;
+    const float mj = block_scan(wj, mass, sm);
+    if (tid == 0) {
+        sm.pick[0] = 0x7fffffff;   // first kept rank whose inclusive mass exceeds the target
+        sm.pick[1] = -1;           // last kept rank (a target that rounding pushed past the end)
+    }
+    __syncthreads();
+    const float target = u01(r.z) * mass;
+    if (wj > 0.f) {
+        if (mj > target) atomicMin(&sm.pick[0], tid);
+        atomicMax(&sm.pick[1], tid);
+    }
+    __syncthreads();
+    int id = 0;
+    if (tid < 64) {
+        int cand = alt;   // the kept set holds nothing but EOS
+        if (mass > 0.f) cand = sm.cand_i[sm.pick[0] != 0x7fffffff ? sm.pick[0] : sm.pick[1]];
+        int rep = 0;
+        for (int w0 = 0; w0 < win_size; w0 += 64) rep += __popcll(__ballot(w0 + tid < win_size && rc[w0 / 64] == (long)cand));
+        id = (float)rep >= (float)win_size * tau_r ? full : cand;
+    }
+    return id;
+}
+
+// ---- the next step's input ---------------------------------------------------------------------------------------------------------
+// one embedding row (D bf16, D % 8 == 0) copied by the workgroup's 256 threads with 16-byte accesses
+__device__ __forceinline__ void copy_emb_row(const uint16_t *src, uint16_t *dst, int D) {
+    for (int d = (int)threadIdx.x * 8; d < D; d += kSmpThreads * 8) *reinterpret_cast<uint4 *>(dst + d) = *reinterpret_cast<const uint4 *>(src + d);
+}
+// dst = t[0][ids[0]] + t[1][ids[1]] + ... in bf16, added in channel order like the module (model/llm/xy_llm.py:189-200: a chain of
+// bf16 tensor additions); 256 threads, 16-byte loads.  xy_embed_kernel (csrc/sampling.hip) and xy_slot_frame_kernel (csrc/xy_slots.hip).
+constexpr int kXYMaxC = 16;
+__device__ __forceinline__ void xy_embed_sum(int C, int D, const uint16_t *const (&t)[kXYMaxC], const long *ids, uint16_t *dst) {
+    for (int d = (int)threadIdx.x * 8; d < D; d += 256 * 8) {
+        float acc[8];
+#pragma unroll
+        for (int c = 0; c < kXYMaxC; c++) {
+            if (c < C) {
+                const uint4 r = *reinterpret_cast<const uint4 *>(t[c] + ids[c] * D + d);
+                const uint32_t w[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const float lo = __uint_as_float(w[j] << 16), hi = __uint_as_float(w[j] & 0xffff0000u);
+                    if (c == 0) {
+                        acc[2 * j] = lo;
+                        acc[2 * j + 1] = hi;
+                    } else {   // bf16 + bf16 -> bf16 (round to nearest even), as torch adds two bf16 tensors
+                        float s0 = acc[2 * j] + lo, s1 = acc[2 * j + 1] + hi;
+                        uint32_t u0 = __float_as_uint(s0), u1 = __float_as_uint(s1);
+                        u0 += 0x7fffu + ((u0 >> 16) & 1u);
+                        u1 += 0x7fffu + ((u1 >> 16) & 1u);
+                        acc[2 * j] = __uint_as_float(u0 & 0xffff0000u);
+                        acc[2 * j + 1] = __uint_as_float(u1 & 0xffff0000u);
+                    }
+                }
+            }
+        }
+        uint4 o;
+        uint32_t *ow = reinterpret_cast<uint32_t *>(&o);
+#pragma unroll
+        for (int j = 0; j < 4; j++) ow[j] = (__float_as_uint(acc[2 * j]) >> 16) | (__float_as_uint(acc[2 * j + 1]) & 0xffff0000u);
+        *reinterpret_cast<uint4 *>(dst + d) = o;
+    }
+}
+
 // elements per thread: the XY channels (1025 ids), the Spark / Cosy vocabularies (8193, 6562), the LDS-free maximum
 constexpr int kEptS = 5, kEptM = 33, kEptL = kSmpMaxN / kSmpThreads;
+// host side: launch(std::integral_constant<int, EPT>) for the smallest class that holds `domain` ids
+template <typename Launch>
+inline void for_ept(int domain, Launch &&launch) {
+    if (domain <= kEptS * kSmpThreads)
+        launch(std::integral_constant<int, kEptS>{});
+    else if (domain <= kEptM * kSmpThreads)
+        launch(std::integral_constant<int, kEptM>{});
+    else
+        launch(std::integral_constant<int, kEptL>{});
+}
 
 }  // namespace
 }  // namespace rwkv7

@@ -25,8 +25,6 @@
 namespace rwkv7 {
 namespace {
 
-constexpr int kXYSlotMaxC = 16;
-
 // = rwkv7_xy_slot_state (include/rwkv7_hip.h).  Every per-slot field is a DEVICE array of `slots` entries.
 struct XYSlotState {
     long *step, *limit;
@@ -38,7 +36,7 @@ struct XYSlotState {
     long *needs;
     long *nt, *row, *seq;
     long seq_ld;
-    const uint16_t *tables[kXYSlotMaxC];
+    const uint16_t *tables[kXYMaxC];
     uint16_t *x;
     int D, C, slots, top_k_max;
     long text_shift, speech_vocab, pad, eos0;
@@ -56,13 +54,13 @@ struct XYSlotStateLp : XYSlotState {
 template <bool LP>
 using XYState = typename std::conditional<LP, XYSlotStateLp, XYSlotState>::type;
 
-// The body repeats sample_rows_kernel's draw (csrc/sampling.hip) with the slot's parameters in place of the launch's: same loads, same
-// selection, same Philox counter for workgroup index = channel, so the id equals that kernel's bit for bit.
+// The draw is the body sample_rows_kernel (csrc/sampling.hip) calls too, warper_draw (csrc/sampling_common.h), with the slot's
+// parameters in place of the launch's: same loads, counter word 2 = channel, key = seed[s], so the id equals that kernel's bit for bit.
 //
 // LP: ch_lp[s][c] = the drawn id's log-probability under the RAW logits (temperature 1, no top-k / top-p) over the channel's allowed
-// range.  A second copy of the range stays unscaled in registers until its maximum and its exp-sum are known, which is before
-// select_bins needs the registers for its bins.  Both reductions go thread -> wave butterfly -> the four waves in fixed order
-// (block_fmax, block_sum): the value depends on the range's contents and the thread layout only, never on the row, the slot or the grid.
+// range.  A second copy of the range stays unscaled in registers until its maximum and its exp-sum are known (raw_logprob_stats), which
+// is before select_bins needs the registers for its bins: the value depends on the range's contents and the thread layout only, never
+// on the row, the slot or the grid.
 template <int EPT, bool LP>
 __global__ __launch_bounds__(kSmpThreads) void xy_slot_draw_kernel(const float *__restrict__ logits, long ld, const int *__restrict__ row_slot,
                                                                    const int *__restrict__ seg_off, const int *__restrict__ seg_len,
@@ -93,49 +91,9 @@ __global__ __launch_bounds__(kSmpThreads) void xy_slot_draw_kernel(const float *
         if constexpr (LP) raw.v[e] = j < m ? t : -INFINITY;
     }
     float lp_max = 0.f, lp_logz = 0.f;   // LP: max and log sum exp(. - max) over the allowed range
-    if constexpr (LP) {
-        float mx = raw.v[0];
-#pragma unroll
-        for (int e = 1; e < EPT; e++) mx = fmaxf(mx, raw.v[e]);
-        lp_max = block_fmax(mx, sm);
-        float z = 0.f;
-#pragma unroll
-        for (int e = 0; e < EPT; e++) z += __expf(raw.v[e] - lp_max);   // beyond the range: exp(-inf) = 0
-        lp_logz = __logf(block_sum(z, sm));
-        __syncthreads();   // sm.red is free again: select_bins writes it without a barrier of its own
-    }
-    int choice;
-    if (!do_sample) {
-        choice = key_idx(block_max(x.local_max(), sm, 0));
-    } else {
-        const uint2 key = make_uint2((uint32_t)st.seed[s], (uint32_t)(st.seed[s] >> 32));
-        const uint4 r = philox(make_uint4((uint32_t)step, (uint32_t)((uint64_t)step >> 32), (uint32_t)seg, 0x5a17u), key);
-        if (top_k > 0) {
-            const int nc = select_bins(x, sm, min(top_k, m), true);
-            const float ej = tid < nc ? __expf(sm.cand_v[tid] - sm.cand_v[0]) : 0.f;
-            float z;
-            const float cj = block_scan(ej, z, sm);
-            const bool keep = tid < nc && (tid == 0 || cj - ej < top_p * z);
-            float kept;
-            (void)block_scan(keep ? ej : 0.f, kept, sm);
-            const float target = u01(r.x) * kept;
-            if (tid == 0) sm.pick[1] = 0;
-            __syncthreads();
-            if (keep && cj <= target) atomicAdd(&sm.pick[1], 1);
-            __syncthreads();
-            float f;
-            (void)block_scan(keep ? 1.f : 0.f, f, sm);
-            const int nk = (int)f;
-            if (tid == 0) sm.pick[0] = nk > 0 ? sm.cand_i[min(sm.pick[1], nk - 1)] : 0;
-            __syncthreads();
-            choice = sm.pick[0];
-        } else {
-            const unsigned long long k = block_max(x.local_max(), sm, 0);
-            int i0, i1;
-            draw_full(x, sm, key_val(k), -1, u01(r.x), 0.f, i0, i1);
-            choice = i0 >= 0 ? i0 : key_idx(k);
-        }
-    }
+    if constexpr (LP) raw_logprob_stats(raw, sm, lp_max, lp_logz);
+    const uint2 key = make_uint2((uint32_t)st.seed[s], (uint32_t)(st.seed[s] >> 32));
+    int choice = warper_draw(x, sm, m, do_sample, top_k, top_p, key, step, (uint32_t)seg);
     choice = min(max(choice, 0), m - 1);
     if (tid == 0) {
         st.nt[(long)s * C + seg] = lo + choice;
@@ -153,7 +111,7 @@ __global__ __launch_bounds__(kSmpThreads) void xy_slot_draw_kernel(const float *
 // channel order in fp64 (one workgroup owns the slot: a plain read, add, store) and their number to n_lp.
 template <bool LP>
 __global__ __launch_bounds__(256) void xy_slot_frame_kernel(const int *__restrict__ row_slot, XYState<LP> st) {
-    __shared__ long frame[kXYSlotMaxC];
+    __shared__ long frame[kXYMaxC];
     __shared__ long next[3];   // needs, step, live after this frame
     const int C = st.C, D = st.D, tid = threadIdx.x;
     const int s = row_slot ? row_slot[blockIdx.x] : (int)blockIdx.x;
@@ -212,36 +170,7 @@ __global__ __launch_bounds__(256) void xy_slot_frame_kernel(const int *__restric
         st.step[s] = next[1];
         st.live[s] = (unsigned char)next[2];
     }
-    for (int d = tid * 8; d < D; d += 256 * 8) {
-        float acc[8];
-#pragma unroll
-        for (int c = 0; c < kXYSlotMaxC; c++) {
-            if (c < C) {
-                const uint4 r = *reinterpret_cast<const uint4 *>(st.tables[c] + frame[c] * D + d);
-                const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const float lo = __uint_as_float(w[j] << 16), hi = __uint_as_float(w[j] & 0xffff0000u);
-                    if (c == 0) {
-                        acc[2 * j] = lo;
-                        acc[2 * j + 1] = hi;
-                    } else {   // bf16 + bf16 -> bf16 (round to nearest even), as torch adds two bf16 tensors
-                        float s0 = acc[2 * j] + lo, s1 = acc[2 * j + 1] + hi;
-                        uint32_t u0 = __float_as_uint(s0), u1 = __float_as_uint(s1);
-                        u0 += 0x7fffu + ((u0 >> 16) & 1u);
-                        u1 += 0x7fffu + ((u1 >> 16) & 1u);
-                        acc[2 * j] = __uint_as_float(u0 & 0xffff0000u);
-                        acc[2 * j + 1] = __uint_as_float(u1 & 0xffff0000u);
-                    }
-                }
-            }
-        }
-        uint4 o;
-        uint32_t *ow = reinterpret_cast<uint32_t *>(&o);
-#pragma unroll
-        for (int j = 0; j < 4; j++) ow[j] = (__float_as_uint(acc[2 * j]) >> 16) | (__float_as_uint(acc[2 * j + 1]) & 0xffff0000u);
-        *reinterpret_cast<uint4 *>(st.x + (long)s * D + d) = o;
-    }
+    xy_embed_sum(C, D, st.tables, frame, st.x + (long)s * D);
 }
 
 }  // namespace
@@ -249,21 +178,18 @@ __global__ __launch_bounds__(256) void xy_slot_frame_kernel(const int *__restric
 template <bool LP>
 static int launch_xy_draw(int rows, const float *logits, long ld, const int *row_slot, const int *seg_off, const int *seg_len,
                           const int *allow_lo, const int *allow_hi, int max_domain, const XYState<LP> &st, hipStream_t stream) {
-    if (max_domain > kSmpMaxN || st.top_k_max < 0 || st.top_k_max > 64 || st.C > kXYSlotMaxC || st.D % 8 != 0) return -4;   // RWKV7_ESHAPE
+    if (max_domain > kSmpMaxN || st.top_k_max < 0 || st.top_k_max > 64 || st.C > kXYMaxC || st.D % 8 != 0) return -4;   // RWKV7_ESHAPE
     (void)hipGetLastError();
     const dim3 grid(rows * st.C), block(kSmpThreads);
-    if (max_domain <= kEptS * kSmpThreads)
-        xy_slot_draw_kernel<kEptS, LP><<<grid, block, 0, stream>>>(logits, ld, row_slot, seg_off, seg_len, allow_lo, allow_hi, st);
-    else if (max_domain <= kEptM * kSmpThreads)
-        xy_slot_draw_kernel<kEptM, LP><<<grid, block, 0, stream>>>(logits, ld, row_slot, seg_off, seg_len, allow_lo, allow_hi, st);
-    else
-        xy_slot_draw_kernel<kEptL, LP><<<grid, block, 0, stream>>>(logits, ld, row_slot, seg_off, seg_len, allow_lo, allow_hi, st);
+    for_ept(max_domain, [&](auto ept) {
+        xy_slot_draw_kernel<decltype(ept)::value, LP><<<grid, block, 0, stream>>>(logits, ld, row_slot, seg_off, seg_len, allow_lo, allow_hi, st);
+    });
     return (int)hipGetLastError();
 }
 
 template <bool LP>
 static int launch_xy_frame(int rows, const int *row_slot, const XYState<LP> &st, hipStream_t stream) {
-    if (st.C > kXYSlotMaxC || st.D % 8 != 0) return -4;
+    if (st.C > kXYMaxC || st.D % 8 != 0) return -4;
     (void)hipGetLastError();
     xy_slot_frame_kernel<LP><<<dim3(rows), dim3(256), 0, stream>>>(row_slot, st);
     return (int)hipGetLastError();
