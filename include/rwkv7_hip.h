@@ -550,6 +550,26 @@ int rwkv7_ce_fwd_bwd_ld_bf16(long rows, int V, long ld, void *logits, const long
  *      rows <= 0, V <= 0, ld < V, row0 < 0, n_seq <= 0. */
 int rwkv7_ce_seq_bwd_bf16(long rows, int V, long ld, void *logits, const long *labels, long ignore_index, long row0, long n_seq,
                           const long *seq_start, const float *seq_scale, float *loss_rows, rwkv7_stream_t stream);
+/*      The token-level clipped policy objective (PPO-clip / GRPO; losses.fused_linear_policy) of a chunk of logits [rows, ld], loss
+ *      terms and d loss / d logits in one pass: the same kernel with the scale computed per ROW.  Rows, sequences, row0 and seq_start
+ *      as in rwkv7_ce_seq_bwd_bf16.  adv, seq_w: fp32 [n_seq] on the DEVICE (a sequence's advantage A and the weight w of each of its
+ *      rows); old_lp, ref_lp: fp32 on the DEVICE, indexed by the BATCH row row0 + r (at least seq_start[n_seq] entries; read only for
+ *      rows that count); ref_lp may be NULL (no KL term, whatever beta says).  For a row that counts -- label != ignore_index, inside
+ *      [seq_start[0], seq_start[n_seq]) -- with lp = logit[label] - logsumexp in fp32 and the rest in double from it:
+ *        rho = exp(lp - old_lp);  s1 = rho A;  s2 = clamp(rho, 1 - eps_lo, 1 + eps_hi) A;  active = s1 <= s2 (ties are active; a NaN
+ *        takes the s1 branch and stays a NaN);  l = -min(s1, s2);  coef = active ? s1 : 0
+ *        with ref_lp:  d = ref_lp - lp;  kl = exp(d) - d - 1 (the k3 estimator);  l += beta kl;  coef -= beta (1 - exp(d))
+ *      The row is REPLACED by (softmax - onehot) * (float)(w coef): the product formed in fp32 and rounded to bf16 once.  Without
+ *      ref_lp and at rho = 1 that is bit for bit what rwkv7_ce_seq_bwd_bf16 writes with seq_scale = the fp32 product w A.  Per-row
+ *      outputs, fp32 [rows] indexed by the CHUNK row r, each may be NULL: lp_rows = lp, loss_rows = l (unweighted), kl_rows = kl (0
+ *      without ref_lp), clip_rows = 1.0 where not active, else 0.0.  Every other row is replaced by zeros and gets zeros in the four
+ *      outputs.  Columns V .. ld - 1 are neither read nor written.  Labels and seq_start are NOT range-checked on the device.  No LDS,
+ *      no atomics, nothing shared between rows, no host read.  RWKV7_EINVAL, before any launch: a NULL logits / labels / seq_start /
+ *      adv / seq_w / old_lp, rows <= 0, V <= 0, ld < V, row0 < 0, n_seq <= 0, eps_lo outside [0, 1), eps_hi < 0 (or either a NaN). */
+int rwkv7_ce_policy_fwd_bwd_bf16(long rows, int V, long ld, void *logits, const long *labels, long ignore_index, long row0, long n_seq,
+                                 const long *seq_start, const float *adv, const float *seq_w, const float *old_lp, const float *ref_lp,
+                                 float eps_lo, float eps_hi, float beta, float *lp_rows, float *loss_rows, float *kl_rows,
+                                 float *clip_rows, rwkv7_stream_t stream);
 /* ---- Cosy head loss: label-smoothing KL loss (cosyvoice/transformer/label_smoothing_loss.py:68-96), its gradient and the accuracy
  *      flag (cosyvoice/utils/common.py:76-95) of a chunk of bf16 logits [rows, ld] in one pass.  Columns V .. ld - 1 are neither read
  *      nor written.  dlogits (bf16 [rows, ld]) MAY be the same pointer as logits (in place); otherwise the logits are left intact.

@@ -19,9 +19,8 @@ from torch.nn.utils.rnn import pad_sequence
 from .backbone import Cache, ModelOutput, RWKV7Config, RWKV7Model
 from .hf_api import HFModelMixin
 from .losses import (EVAL_KL, SCORE_KEYS, eval_mode, fused_linear_eval, fused_linear_kl_accuracy, fused_linear_score,
-                     fused_linear_seq_logprob, label_smoothing_kl, label_smoothing_kl_fused, padded_seq_start, scored_forward,
-                     seq_token_counts,
-                     th_accuracy)
+                     fused_linear_seq_logprob, label_smoothing_kl, label_smoothing_kl_fused, padded_seq_start, policy_objective,
+                     scored_forward, seq_token_counts, th_accuracy, token_logprob_rows)
 
 IGNORE_ID = -1  # cosyvoice/utils/common.py:24
 
@@ -136,6 +135,14 @@ def _cosy_logprobs(hidden, labels, lm_head):
     return dict(logp=logp, tokens=seq_token_counts(labels, IGNORE_ID, seq_start))
 
 
+def _cosy_policy(hidden, labels, lm_head, advantages, old_logps, ref_logps, clip, kl_beta, normalize):
+    """policy_loss of the Cosy layout from the backbone's hidden states [B, L, D] (with autograd) and the targets [B, L]: _cosy_scores'
+    rows and utterances, the plain log-softmax at the target (no smoothing)."""
+    B, L = labels.shape
+    return policy_objective(hidden, labels, lm_head, IGNORE_ID, padded_seq_start(B, L, hidden.device), advantages, old_logps, ref_logps,
+                            clip, kl_beta, normalize)
+
+
 class RWKV7CosyLM(HFModelMixin, nn.Module):
     config_class = RWKV7CosyConfig
 
@@ -228,9 +235,10 @@ class RWKV7CosyLM(HFModelMixin, nn.Module):
             hidden, labels = self._scored_rows(input_ids, attention_mask, inputs_embeds, labels, max_tokens_k, kwargs)
             return _cosy_metrics(hidden, labels, self.lm_head, self.config.lsm_weight, self.config.length_normalized_loss)
 
-    def _scored_rows(self, input_ids, attention_mask, inputs_embeds, labels, max_tokens_k, kwargs):
-        """What eval_metrics, score (inside eval_mode) and sequence_logprobs (the current mode: forward's dropout while training)
-        evaluate: the backbone's hidden states [B, L, D] and the targets [B, L]."""
+    def _scored_rows(self, input_ids, attention_mask, inputs_embeds, labels, max_tokens_k, kwargs, on_tape=False):
+        """What eval_metrics, score (inside eval_mode), sequence_logprobs and policy_loss (the current mode: forward's dropout while
+        training) evaluate: the backbone's hidden states [B, L, D] and the targets [B, L].  on_tape (policy_loss): the backbone is
+        called directly, once, with autograd as forward calls it."""
         if "batch" in kwargs:
             inputs_embeds, attention_mask, labels = self.build_inputs(kwargs["batch"])
             if self.dropout is not None:
@@ -240,8 +248,8 @@ class RWKV7CosyLM(HFModelMixin, nn.Module):
                 if max_bsz < inputs_embeds.shape[0]:
                     inputs_embeds, labels, attention_mask = inputs_embeds[:max_bsz], labels[:max_bsz], attention_mask[:max_bsz]
         # scored_forward: under no_grad the plain call; with autograd (sequence_logprobs) the same no_grad pass, recomputed in backward
-        return scored_forward(lambda ids, emb: self.model(input_ids=ids, attention_mask=attention_mask, inputs_embeds=emb)[0],
-                              input_ids, inputs_embeds), labels
+        run = lambda ids, emb: self.model(input_ids=ids, attention_mask=attention_mask, inputs_embeds=emb)[0]   # noqa: E731
+        return (run(input_ids, inputs_embeds) if on_tape else scored_forward(run, input_ids, inputs_embeds)), labels
 
     def score(self, input_ids=None, attention_mask=None, inputs_embeds=None, labels=None, max_tokens_k: Optional[int] = None, **kwargs):
         """Per-utterance scores of one batch (eval_metrics' batch kwargs, rows and targets; the backbone once, eval mode, no autograd,
@@ -262,6 +270,22 @@ class RWKV7CosyLM(HFModelMixin, nn.Module):
         logp is bit for bit -score(...)["loss_sum"]."""
         hidden, labels = self._scored_rows(input_ids, attention_mask, inputs_embeds, labels, max_tokens_k, kwargs)
         return _cosy_logprobs(hidden, labels, self.lm_head)
+
+    def policy_loss(self, *, advantages, old_logps, ref_logps=None, clip=(0.2, 0.2), kl_beta=0.0, normalize="sequence", input_ids=None,
+                    attention_mask=None, inputs_embeds=None, labels=None, max_tokens_k: Optional[int] = None, **kwargs):
+        """The token-level clipped policy objective (GRPO / PPO-clip; DataParallelTrainer.policy_step) over
+        exactly score's rows, targets and utterances, in the module's current mode; the backbone runs ONCE, directly under autograd.
+        See RWKV7ForSpeech.policy_loss for the arguments and the returned dict (rows: the flattened [B * L] targets)."""
+        hidden, labels = self._scored_rows(input_ids, attention_mask, inputs_embeds, labels, max_tokens_k, kwargs, on_tape=True)
+        return _cosy_policy(hidden, labels, self.lm_head, advantages, old_logps, ref_logps, clip, kl_beta, normalize)
+
+    def token_logprobs(self, input_ids=None, attention_mask=None, inputs_embeds=None, labels=None, max_tokens_k: Optional[int] = None,
+                       **kwargs):
+        """log p(target) of every row of score's flattened [B * L] rows (fp32, 0 on ignored rows; no label smoothing): eval mode, no
+        autograd, the previous mode restored.  The exact source of policy_loss's old_logps and ref_logps."""
+        with eval_mode(self):
+            hidden, labels = self._scored_rows(input_ids, attention_mask, inputs_embeds, labels, max_tokens_k, kwargs)
+            return token_logprob_rows(hidden, labels, self.lm_head, IGNORE_ID)
 
     def forward_one_step(self, xs, masks, cache=None):
         """cosy_llm.py:274-286 / llm.py:146-158."""
@@ -480,3 +504,23 @@ class RWKV7LM(nn.Module):
             lm_input = self.dropout(lm_input)
         hidden = scored_forward(lambda emb: self.llm.model(inputs_embeds=emb, attention_mask=attention_mask)[0], lm_input)
         return _cosy_logprobs(hidden, lm_target, self.llm.lm_head)
+
+    def policy_loss(self, batch: dict, *, advantages, old_logps, ref_logps=None, clip=(0.2, 0.2), kl_beta=0.0, normalize="sequence"):
+        """The token-level clipped policy objective (forward's argument; score's rows and targets, the current mode with forward's
+        dropout, the backbone once under autograd): see RWKV7CosyLM.policy_loss."""
+        if not (hasattr(self.llm, "model") and hasattr(self.llm, "lm_head")):
+            raise TypeError("RWKV7LM.policy_loss needs an llm with .model and .lm_head (the hidden states go to the fused head)")
+        lm_input, attention_mask, lm_target = self.build_inputs(batch)
+        if self.dropout is not None:
+            lm_input = self.dropout(lm_input)
+        hidden = self.llm.model(inputs_embeds=lm_input, attention_mask=attention_mask)[0]
+        return _cosy_policy(hidden, lm_target, self.llm.lm_head, advantages, old_logps, ref_logps, clip, kl_beta, normalize)
+
+    def token_logprobs(self, batch: dict):
+        """log p(target) of every row of score's flattened rows (forward's argument): see RWKV7CosyLM.token_logprobs."""
+        if not (hasattr(self.llm, "model") and hasattr(self.llm, "lm_head")):
+            raise TypeError("RWKV7LM.token_logprobs needs an llm with .model and .lm_head (the hidden states go to the fused head)")
+        with eval_mode(self):
+            lm_input, attention_mask, lm_target = self.build_inputs(batch)
+            hidden = self.llm.model(inputs_embeds=lm_input, attention_mask=attention_mask)[0]
+            return token_logprob_rows(hidden, lm_target, self.llm.lm_head, IGNORE_ID)

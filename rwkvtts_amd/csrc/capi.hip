@@ -546,6 +546,18 @@ int rwkv7_ce_seq_bwd_bf16(long rows, int V, long ld, void *logits, const long *l
         return RWKV7_EINVAL;
     return rwkv7::ce_seq_bwd(rows, V, ld, logits, labels, ignore_index, row0, n_seq, seq_start, seq_scale, loss_rows, (hipStream_t)stream);
 }
+int rwkv7_ce_policy_fwd_bwd_bf16(long rows, int V, long ld, void *logits, const long *labels, long ignore_index, long row0, long n_seq,
+                                 const long *seq_start, const float *adv, const float *seq_w, const float *old_lp, const float *ref_lp,
+                                 float eps_lo, float eps_hi, float beta, float *lp_rows, float *loss_rows, float *kl_rows,
+                                 float *clip_rows, rwkv7_stream_t stream) {
+    if (rows <= 0 || V <= 0 || ld < V || row0 < 0 || n_seq <= 0 ||
+        any_null({(const void *)logits, (const void *)labels, (const void *)seq_start, (const void *)adv, (const void *)seq_w,
+                  (const void *)old_lp}))
+        return RWKV7_EINVAL;
+    if (!(eps_lo >= 0.f && eps_lo < 1.f && eps_hi >= 0.f)) return RWKV7_EINVAL;
+    return rwkv7::ce_policy_fwd_bwd(rows, V, ld, logits, labels, ignore_index, row0, n_seq, seq_start, adv, seq_w, old_lp, ref_lp, eps_lo,
+                                    eps_hi, beta, lp_rows, loss_rows, kl_rows, clip_rows, (hipStream_t)stream);
+}
 // the entropy constant of the label-smoothing KL's target distribution (1 - s on the label, s / (V - 1) elsewhere), sum_j t_j ln t_j
 // with 0 ln 0 = 0 (what F.kl_div gives for a zero target)
 static float kl_entropy_const(float smoothing, int V) {

@@ -1,5 +1,6 @@
 // rwkvtts_amd/csrc/head_loss.hip -- the three kernels that walk a row of bf16 head logits [rows, ld]: the two training heads (loss and
-// d loss / d logits in one pass; the cross-entropy one also with a scale per SEQUENCE, rwkv7_ce_seq_bwd_bf16) and the forward-only
+// d loss / d logits in one pass; the cross-entropy one also with a scale per SEQUENCE, rwkv7_ce_seq_bwd_bf16, and with the clipped
+// policy-gradient coefficient per ROW, rwkv7_ce_policy_fwd_bwd_bf16) and the forward-only
 // metrics of held-out evaluation.  They share ONE row body (the anonymous namespace
 // below): how a row is split, how a thread folds elements into (m, ssum, xsum[, best]), how two such partials merge, the two closing
 // loss formulas and the gradient of an element.  A kernel adds only its structure: which thread owns which element and in which order
@@ -160,33 +161,96 @@ __device__ __forceinline__ uint4 grad_piece(const uint4 r, int base, float lse, 
 // label smoothing ls: d loss / d x_j = softmax_j - ls / V - (1 - ls) [j == label].
 // ld: elements between rows (>= V; round 6: the Spark head's logits live in a buffer padded to a multiple of 256 columns, so rows are 16-byte
 // aligned and the head GEMMs see aligned leading dimensions)
-// Where a row's scale comes from is the kernel's one parameter (Scale, the two structs below): one value for the whole chunk
-// (rwkv7_ce_fwd_bwd*_bf16: loss_rows is never NULL there), or the value of the row's SEQUENCE (rwkv7_ce_seq_bwd_bf16, the backward of
+// Where a row's scale comes from is the kernel's one parameter (Scale, the three structs below): one value for the whole chunk
+// (rwkv7_ce_fwd_bwd*_bf16: loss_rows is never NULL there), the value of the row's SEQUENCE (rwkv7_ce_seq_bwd_bf16, the backward of
 // losses.fused_linear_seq_logprob: the upstream gradient of a per-sequence sum of log-probabilities differs from sequence to sequence,
-// so it cannot be applied to the finished gradient afterwards as one scalar; loss_rows may be NULL).  Everything else is one text.
+// so it cannot be applied to the finished gradient afterwards as one scalar; loss_rows may be NULL), or the clipped policy-gradient
+// coefficient of the row (rwkv7_ce_policy_fwd_bwd_bf16: PolicyScale, which also writes the row's statistics; loss_rows is NULL).
+// Everything else is one text.
+// Every source is called as scale_of(row, valid, lp, lane) by all 64 lanes of the row's wave with the same arguments but `lane`: valid --
+// the label is not ignore_index; lp = x[label] - lse, the row's fp32 log-probability of its label (meaningless when !valid).  The first
+// two ignore lp and lane.
 struct UniformScale {
     float scale;
-    __device__ __forceinline__ float operator()(long) const { return scale; }
+    __device__ __forceinline__ float operator()(long, bool valid, float, int) const { return valid ? scale : 0.f; }
 };
 
 // Row r of the chunk is row row0 + r of the batch; its sequence is the largest s < n_seq with seq_start[s] <= row0 + r, provided
 // row0 + r < seq_start[n_seq] (seq_start: n_seq + 1 non-decreasing offsets; equal neighbours are empty sequences, which own no row).
-// A row in front of seq_start[0] or at / behind seq_start[n_seq] gets scale 0, like an ignored row.  The search is the same for the
+// A row in front of seq_start[0] or at / behind seq_start[n_seq] has no sequence (-1).  The search is the same for the
 // 64 lanes of a row's wave: the row index goes through readfirstlane, so the offsets arrive by scalar loads and no lane diverges.
-struct SeqScale {
+struct SeqOfRow {
     long row0, n_seq;
     const long *seq_start;
-    const float *seq_scale;
-    __device__ __forceinline__ float operator()(long row) const {
+    __device__ __forceinline__ long operator()(long row) const {
         const long g = row0 + row;
         const long gu = ((long)__builtin_amdgcn_readfirstlane((int)(g >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)g);
-        if (gu >= seq_start[n_seq]) return 0.f;
+        if (gu >= seq_start[n_seq]) return -1;
         long lo = 0, hi = n_seq;   // lo ends as the number of s < n_seq with seq_start[s] <= gu
         while (lo < hi) {
             const long mid = (lo + hi) >> 1;
             if (seq_start[mid] <= gu) lo = mid + 1; else hi = mid;
         }
-        return lo > 0 ? seq_scale[lo - 1] : 0.f;
+        return lo - 1;
+    }
+};
+
+// A row without a sequence gets scale 0, like an ignored row.
+struct SeqScale {
+    SeqOfRow seq_of;
+    const float *seq_scale;
+    __device__ __forceinline__ float operator()(long row, bool valid, float, int) const {
+        if (!valid) return 0.f;
+        const long s = seq_of(row);
+        return s >= 0 ? seq_scale[s] : 0.f;
+    }
+};
+
+// The token-level clipped policy objective (PPO-clip / GRPO; rwkv7_ce_policy_fwd_bwd_bf16, losses.fused_linear_policy): the row's loss
+// term and its coefficient on (softmax - onehot) follow from the row's own lp and from data known before the launch -- old_lp / ref_lp of
+// batch row row0 + r, adv / seq_w of its sequence.  The closing arithmetic of a row runs in double (kl_row_loss's precedent), from the
+// fp32 lp, and it runs REPLICATED on all 64 lanes of the row's wave on purpose -- two exponentials, a clamp and the loads of old_lp /
+// ref_lp from one shared address per row, next to V / 64 exponentials per lane in each pass over the row: one lane computing and a
+// broadcast of sc would save nothing measurable and add a cross-lane step in front of the gradient pass.
+//   rho = exp(lp - old_lp);  s1 = rho A;  s2 = clamp(rho, lo, hi) A;  the unclipped branch s1 is taken unless s1 > s2 (ties are active, as
+//   the gradient of torch.minimum / clamp has it; a NaN stays a NaN);  l = -min(s1, s2);  coef = s1 where taken, else 0
+//   with ref_lp:  d = ref_lp - lp;  kl = exp(d) - d - 1 (the k3 estimator);  l += beta kl;  coef -= beta (1 - exp(d))
+//   sc = (float)(w coef)
+// Without ref_lp the KL lines are not executed at all: coef is s1 or 0 and sc the correctly rounded product w (rho A) -- at rho = 1 the
+// fp32 product w A, which is how the row then equals rwkv7_ce_seq_bwd_bf16's with seq_scale = w A bit for bit.
+// Lane 0 writes the row's statistics (each array may be NULL); ignored rows and rows without a sequence give sc = 0 and zero statistics.
+struct PolicyScale {
+    SeqOfRow seq_of;
+    const float *adv, *seq_w, *old_lp, *ref_lp;
+    double lo, hi, beta;   // 1 - eps_lo, 1 + eps_hi
+    float *lp_rows, *loss_rows, *kl_rows, *clip_rows;
+    __device__ __forceinline__ float operator()(long row, bool valid, float lp, int lane) const {
+        const long s = valid ? seq_of(row) : -1;
+        float sc = 0.f, lp_o = 0.f, l_o = 0.f, kl_o = 0.f, clip_o = 0.f;
+        if (s >= 0) {
+            const long g = seq_of.row0 + row;
+            const double A = (double)adv[s], rho = exp((double)lp - (double)old_lp[g]);
+            const double s1 = rho * A, s2 = fmin(fmax(rho, lo), hi) * A;
+            const bool take1 = !(s1 > s2);
+            double l = -(take1 ? s1 : s2), coef = take1 ? s1 : 0.0;
+            if (ref_lp != nullptr) {
+                const double d = (double)ref_lp[g] - (double)lp, e = exp(d), kl = e - d - 1.0;
+                l += beta * kl;
+                coef -= beta * (1.0 - e);
+                kl_o = (float)kl;
+            }
+            sc = (float)((double)seq_w[s] * coef);
+            lp_o = lp;
+            l_o = (float)l;
+            clip_o = take1 ? 0.f : 1.f;
+        }
+        if (lane == 0) {
+            if (lp_rows) lp_rows[row] = lp_o;
+            if (loss_rows) loss_rows[row] = l_o;
+            if (kl_rows) kl_rows[row] = kl_o;
+            if (clip_rows) clip_rows[row] = clip_o;
+        }
+        return sc;
     }
 };
 
@@ -208,8 +272,10 @@ __global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(long rows, int V, long 
     for (int i = lane; i < sp.nv; i += 64) acc_piece(acc, xv[i], sp.head + 8 * i);
     acc_butterfly(acc);
     const float lse = acc_lse(acc);
-    if (lane == 0 && loss_rows) loss_rows[row] = valid ? ce_row_loss(lse, acc.xsum, bf2f(x[lab < 0 ? 0 : lab]), V, ls) : 0.f;
-    const float sc = valid ? scale_of(row) : 0.f, hit = 1.f - ls, off_all = ls / (float)V;
+    // before any store of this row.  An ignored row reads its own first element, never x[ignore_index]; a valid row reads what it always read
+    const float xlab = bf2f(x[(valid && lab > 0) ? lab : 0]);
+    if (lane == 0 && loss_rows) loss_rows[row] = valid ? ce_row_loss(lse, acc.xsum, xlab, V, ls) : 0.f;
+    const float sc = scale_of(row, valid, xlab - lse, lane), hit = 1.f - ls, off_all = ls / (float)V;
     const int labi = (int)lab;   // an ignored row's gradient is 0 whatever this matches
     auto minus_target = [&](float p, int j) { return p - off_all - (j == labi ? hit : 0.f); };
     if (lane < sp.head) x[lane] = grad_one(bf2f(x[lane]), lane, lse, sc, minus_target);
@@ -230,7 +296,18 @@ int ce_seq_bwd(long rows, int V, long ld, void *logits, const long *labels, long
                const long *seq_start, const float *seq_scale, float *loss_rows, hipStream_t st) {
     (void)hipGetLastError();
     hipLaunchKernelGGL(ce_fwd_bwd_kernel<SeqScale>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, rows, V, ld, (bf16_t *)logits,
-                       labels, ignore_index, SeqScale{row0, n_seq, seq_start, seq_scale}, loss_rows, 0.f);
+                       labels, ignore_index, SeqScale{{row0, n_seq, seq_start}, seq_scale}, loss_rows, 0.f);
+    return (int)hipGetLastError();
+}
+
+int ce_policy_fwd_bwd(long rows, int V, long ld, void *logits, const long *labels, long ignore_index, long row0, long n_seq,
+                      const long *seq_start, const float *adv, const float *seq_w, const float *old_lp, const float *ref_lp, float eps_lo,
+                      float eps_hi, float beta, float *lp_rows, float *loss_rows, float *kl_rows, float *clip_rows, hipStream_t st) {
+    (void)hipGetLastError();
+    const PolicyScale ps{{row0, n_seq, seq_start}, adv, seq_w, old_lp, ref_lp, 1.0 - (double)eps_lo, 1.0 + (double)eps_hi, (double)beta,
+                         lp_rows, loss_rows, kl_rows, clip_rows};
+    hipLaunchKernelGGL(ce_fwd_bwd_kernel<PolicyScale>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, rows, V, ld, (bf16_t *)logits,
+                       labels, ignore_index, ps, nullptr, 0.f);
     return (int)hipGetLastError();
 }
 

@@ -138,6 +138,10 @@ int ce_fwd_bwd(long rows, int V, long ld, void *logits, const long *labels, long
                float label_smoothing, hipStream_t stream);
 int ce_seq_bwd(long rows, int V, long ld, void *logits, const long *labels, long ignore_index, long row0, long n_seq,
                const long *seq_start, const float *seq_scale, float *loss_rows, hipStream_t stream);
+//      ref_lp and each of the four per-row outputs may be NULL
+int ce_policy_fwd_bwd(long rows, int V, long ld, void *logits, const long *labels, long ignore_index, long row0, long n_seq,
+                      const long *seq_start, const float *adv, const float *seq_w, const float *old_lp, const float *ref_lp, float eps_lo,
+                      float eps_hi, float beta, float *lp_rows, float *loss_rows, float *kl_rows, float *clip_rows, hipStream_t stream);
 int kl_acc_fwd_bwd(long rows, int V, long ld, const void *logits, void *dlogits, const long *labels, long ignore_index, float smoothing,
                    float C, float scale, float *loss_rows, int *correct_rows, hipStream_t stream);
 int head_eval(long rows, int V, long ld, const void *logits, const long *labels, long ignore_index, int kind, float smoothing, float C,

@@ -15,6 +15,8 @@ fused_linear_score         : the same rows reduced per SEQUENCE instead of per b
     DataParallelTrainer.score).
 fused_linear_seq_logprob   : that loss sum, negated, UNDER AUTOGRAD with an upstream gradient per sequence (the heads' sequence_logprobs,
     DataParallelTrainer.preference_step): backward runs the head GEMM again chunk by chunk and rwkv7_ce_seq_bwd_bf16 on each chunk.
+fused_linear_policy        : the token-level clipped policy objective (PPO-clip / GRPO, optional k3 KL to a reference) UNDER AUTOGRAD (the
+    heads' policy_loss, DataParallelTrainer.policy_step): rwkv7_ce_policy_fwd_bwd_bf16 writes d loss / d logits in the forward chunk walk.
 """
 import contextlib
 import math
@@ -660,3 +662,184 @@ def fused_linear_seq_logprob(hidden, labels, weight, bias, ignore_index, *, seq_
         raise ValueError("fused_linear_seq_logprob: seq_start must be a 1-D tensor of n_seq + 1 >= 2 row offsets")
     D = hidden.shape[-1]
     return _FusedLinearSeqLogprob.apply(hidden.reshape(-1, D), weight, bias, labels.reshape(-1), seq_start, ignore_index, kind, chunk)
+
+
+# ---- token-level clipped policy gradient (GRPO / PPO-clip) ----------------------------------------------------
+POLICY_HITS = [0]   # launches of rwkv7_ce_policy_fwd_bwd_bf16 (one per chunk of a forward pass): how a test sees which route a call took
+
+
+def group_advantages(rewards, group_size, eps=1e-6):
+    """GRPO's group-relative advantages: rewards [G * group_size] (the candidates of one prompt are neighbours) ->
+    (r - mean_group) / (std_group + eps) in the rewards' floating dtype (fp32 for anything else), std the population standard
+    deviation of the group.  A group of equal rewards gives zeros."""
+    r = torch.as_tensor(rewards)
+    if not r.is_floating_point():
+        r = r.float()
+    if group_size < 1 or r.dim() != 1 or r.numel() % group_size != 0:
+        raise ValueError(f"group_advantages: {tuple(r.shape)} rewards do not form groups of {group_size}")
+    g = r.reshape(-1, group_size)
+    c = g - g.mean(dim=1, keepdim=True)
+    return (c / (c.square().mean(dim=1, keepdim=True).sqrt() + eps)).reshape(-1)
+
+
+def _row_sequences(seq_start, row0, rows):
+    """(s, inside) of rows row0 .. row0 + rows - 1: the sequence index as the head kernels look it up (the largest s with
+    seq_start[s] <= row, clamped into [0, n_seq - 1]) and whether the row lies in [seq_start[0], seq_start[-1])."""
+    r = torch.arange(row0, row0 + rows, dtype=torch.int64, device=seq_start.device)
+    s = torch.searchsorted(seq_start, r, right=True) - 1
+    return s.clamp(0, seq_start.numel() - 2), (s >= 0) & (r < seq_start[-1])
+
+
+def _policy_rows_torch(x, labels, ignore_index, s, inside, adv, seq_w, old, ref, lo, hi, beta):
+    """rwkv7_ce_policy_fwd_bwd_bf16's row formulas in torch from fp64 logits x [rows, V]: (lp, l_t, kl, clipped) fp32 [rows] and the
+    row's coefficient sc fp64 [rows], zero on ignored rows and on rows outside every sequence.  Like the kernel's closing arithmetic
+    this runs in fp64: a rounding of lp (a number of size log V) is a relative error of the whole row's gradient, and coefficients of
+    both signs cancel in dW and db.  old / ref: the rows' entries; s, inside: _row_sequences."""
+    on = inside & (labels != ignore_index)
+    lp = x.gather(1, labels.clamp(min=0).unsqueeze(1)).squeeze(1) - torch.logsumexp(x, dim=1)
+    A, rho = adv.double()[s], torch.exp(lp - old.double())
+    s1, s2 = rho * A, rho.clamp(lo, hi) * A
+    take1 = ~(s1 > s2)   # ties are active; a NaN stays a NaN, as torch.minimum keeps it
+    loss, coef = -torch.where(take1, s1, s2), torch.where(take1, s1, torch.zeros_like(s1))
+    kl = torch.zeros_like(lp)
+    if ref is not None:
+        d = ref.double() - lp
+        e = torch.exp(d)
+        kl = e - d - 1   # the k3 estimator of KL(policy || reference)
+        loss, coef = loss + beta * kl, coef - beta * (1 - e)
+    zero = torch.zeros_like(lp)
+    return tuple(torch.where(on, v, zero).float() for v in (lp, loss, kl, (~take1).double())) + (torch.where(on, seq_w.double()[s] * coef, zero),)
+
+
+class _FusedLinearPolicy(torch.autograd.Function):
+    """_FusedLinearCE's shape for the clipped policy objective: d loss / d logits is written in the FORWARD chunk walk (a row's
+    coefficient depends on its own log p(label) and on data known before the launch), the three gradient GEMMs run there too, and
+    backward applies the one upstream scalar.  The walk is _FusedLinearSeqLogprob's: one reused [chunk, ld] logits buffer, an
+    overlapping last chunk that contributes only the rows its predecessor did not cover."""
+
+    @staticmethod
+    def forward(ctx, hidden, weight, bias, labels, seq_start, adv, seq_w, old_logp, ref_logp, ignore_index, eps_lo, eps_hi, beta, chunk):
+        N, V = hidden.shape[0], weight.shape[0]
+        lo, hi = 1.0 - eps_lo, 1.0 + eps_hi
+        dev = hidden.device
+        lab = labels.contiguous()
+        st = seq_start.to(device=dev, dtype=torch.int64).clamp(0, N).contiguous()   # the kernel checks no range: keep every read inside
+        n_seq = st.numel() - 1
+        adv, seq_w, old = (t.to(device=dev, dtype=torch.float32).contiguous() for t in (adv, seq_w, old_logp))
+        ref = None if ref_logp is None else ref_logp.to(device=dev, dtype=torch.float32).contiguous()
+        hip = _hip_gate(hidden, lab, weight, bias)
+        need = ctx.needs_input_grad
+        grads = _HeadGrads(need, hidden, weight, bias)
+        stats = torch.empty(4, N, dtype=torch.float32, device=dev)   # lp, l_t, kl, clipped of every row
+        if chunk is None and not hip:
+            # this node's torch route holds fp64 logits, an fp64 softmax and the copy in the hidden dtype: 24 bytes per logit, where
+            # _chunk_plan budgets the neighbours' fp32 pair
+            chunk = EVAL_CHUNK_ROWS or auto_chunk(N, V, 24)
+        chunk, walk = _chunk_plan(N, V, hidden.element_size(), hip, chunk, SCORE_CHUNK_ALIGN, True)
+        if hip:
+            _check_labels(lab, V, ignore_index)
+            buf, wt = _logits_buffer(chunk, weight)
+        else:
+            w64, b64 = weight.double(), None if bias is None else bias.double()
+        for s, rows, skip in walk:   # an overlapping last chunk contributes the rows behind its first `skip` only
+            h, r0 = hidden[s:s + rows], s + skip
+            if hip:
+                logits = _fill_logits(buf, h, wt, bias)
+                _lib.call("rwkv7_ce_policy_fwd_bwd_bf16", buf, rows - skip, V, buf.stride(0), buf[skip:], lab[r0:], ignore_index, r0,
+                          n_seq, st, adv, seq_w, old, ref, eps_lo, eps_hi, beta, stats[0, r0:], stats[1, r0:], stats[2, r0:],
+                          stats[3, r0:])
+                POLICY_HITS[0] += 1
+                grads.add(logits[skip:], h[skip:], r0, s + rows)
+            else:
+                # fp64 logits: rho = exp(lp - old) turns an ABSOLUTE error of the logits into a relative error of the row's gradient
+                logits = F.linear(h.double(), w64, b64)
+                lb = lab[s:s + rows]
+                sq, inside = _row_sequences(st, s, rows)
+                *rows4, sc = _policy_rows_torch(logits, lb, ignore_index, sq, inside, adv, seq_w, old[s:s + rows],
+                                                None if ref is None else ref[s:s + rows], lo, hi, beta)
+                stats[:, s:s + rows] = torch.stack(rows4)
+                if need[0] or need[1]:
+                    p = _grad_rows_torch(logits, lb, 0.0, sc)
+                    grads.add(p.to(hidden.dtype), h, s, s + rows, p)
+        sq, inside = _row_sequences(st, 0, N)
+        row_w = torch.where(inside & (lab != ignore_index), seq_w[sq], torch.zeros_like(seq_w[:1]))
+        loss = (stats[1].double() * row_w.double()).sum()
+        ctx.save_for_backward(grads.dh, grads.dw, grads.db)
+        ctx.hdtype, ctx.wdtype = hidden.dtype, weight.dtype
+        lp, kl, clipped = stats[0], stats[2], stats[3]
+        ctx.mark_non_differentiable(lp, kl, clipped)
+        return loss, lp, kl, clipped
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        dh, dw, db = ctx.saved_tensors
+        return _HeadGrads.scaled(dh, dw, db, g.float(), ctx.hdtype, ctx.wdtype) + (None,) * 11
+
+
+def fused_linear_policy(hidden, labels, weight, bias, ignore_index, *, seq_start, adv, seq_w, old_logp, ref_logp=None, clip=(0.2, 0.2),
+                        kl_beta=0.0, chunk=None):
+    """The token-level clipped policy objective of a head (PPO-clip / GRPO) under autograd: hidden [..., D], labels [...] (N rows once
+    flattened), seq_start as in fused_linear_score (n_seq sequences), adv and seq_w [n_seq] (a sequence's advantage and the weight of
+    each of its rows), old_logp and ref_logp [N] (the sampling policy's and a frozen reference's log p(label) of every row; entries of
+    ignored rows and of rows outside every sequence are never used) -> (loss, {"logp", "kl", "clipped"}).
+    With lp = log softmax(F.linear(hidden, weight, bias))[label] of a row t of sequence s that counts (label != ignore_index):
+        rho = exp(lp - old_logp[t]);  s1 = rho adv[s];  s2 = clamp(rho, 1 - clip[0], 1 + clip[1]) adv[s]
+        l_t = -min(s1, s2) [+ kl_beta (exp(d) - d - 1),  d = ref_logp[t] - lp,  with ref_logp: the k3 estimator of the KL]
+        loss = sum_t seq_w[s] l_t   (fp64 on the device), differentiable with respect to hidden, weight and bias.
+    The dict holds detached fp32 [N] vectors, 0 on rows that do not count: logp = lp, kl, clipped = 1.0 where the clipped branch is the
+    minimum (no policy gradient flows through that row; at a tie the unclipped branch is taken, as torch.minimum's gradient does).
+    Without ref_logp no KL term exists whatever kl_beta says.
+    bf16 CUDA hidden / weight / bias with int64 labels: per chunk of rows the head GEMM into ONE reused [chunk, ld] bf16 buffer, then
+    rwkv7_ce_policy_fwd_bwd_bf16 turns it in place into d loss / d logits (the row's coefficient in fp64 from its fp32 lp, applied in
+    fp32 before the one bf16 rounding) and writes the row's statistics, then dh = pd W, dW += (pd^T h).float(), db += column sums;
+    backward multiplies by the upstream scalar.  Nothing of size [N, V] is kept and nothing is read on the host.  The chunk is
+    rounded up to a multiple of 64 rows and a shorter last chunk overlaps its predecessor, contributing only the rows that one did not
+    cover.  Gradients are NOT bit-identical across chunk sizes (dW's fp32 sum over chunks).  Anything else: the same definitions in
+    torch per chunk, from fp64 logits (a row's rows and coefficient in fp64, rounded once to the hidden dtype)."""
+    if seq_start is None or seq_start.dim() != 1 or seq_start.numel() < 2:
+        raise ValueError("fused_linear_policy: seq_start must be a 1-D tensor of n_seq + 1 >= 2 row offsets")
+    D = hidden.shape[-1]
+    h2, lab = hidden.reshape(-1, D), labels.reshape(-1)
+    n_seq, N = seq_start.numel() - 1, lab.numel()
+    eps_lo, eps_hi = float(clip[0]), float(clip[1])
+    if not (0.0 <= eps_lo < 1.0 and eps_hi >= 0.0):
+        raise ValueError(f"fused_linear_policy: clip must be (eps_lo in [0, 1), eps_hi >= 0), got {clip}")
+    if adv.numel() != n_seq or seq_w.numel() != n_seq or old_logp.numel() != N or (ref_logp is not None and ref_logp.numel() != N):
+        raise ValueError(f"fused_linear_policy: {n_seq} sequences and {N} rows need adv / seq_w of {n_seq} and old_logp / ref_logp of "
+                         f"{N} entries")
+    loss, lp, kl, clipped = _FusedLinearPolicy.apply(h2, weight, bias, lab, seq_start, adv.reshape(-1), seq_w.reshape(-1),
+                                                     old_logp.reshape(-1), None if ref_logp is None else ref_logp.reshape(-1),
+                                                     ignore_index, eps_lo, eps_hi, float(kl_beta), chunk)
+    return loss, dict(logp=lp, kl=kl, clipped=clipped)
+
+
+def policy_objective(hidden, labels, lm_head, ignore_index, seq_start, advantages, old_logps, ref_logps, clip, kl_beta, normalize):
+    """policy_loss of the heads from the backbone's hidden states [B, T, D] (with autograd), the labels [B, T] and the utterances'
+    seq_start: fused_linear_policy with the row weights of `normalize` ("sequence": 1 / (n_seq * tokens_s); "token": 1 / sum of
+    tokens), formed on the device."""
+    if normalize not in ("sequence", "token"):
+        raise ValueError(f'policy_loss: normalize must be "sequence" or "token", got {normalize!r}')
+    dev = hidden.device
+    labels = labels.to(dev)
+    n_seq = seq_start.numel() - 1
+    adv = torch.as_tensor(advantages).to(device=dev, dtype=torch.float32).reshape(-1)
+    old = torch.as_tensor(old_logps).to(device=dev, dtype=torch.float32).reshape(-1)
+    ref = None if ref_logps is None else torch.as_tensor(ref_logps).to(device=dev, dtype=torch.float32).reshape(-1)
+    if adv.numel() != n_seq or old.numel() != labels.numel() or (ref is not None and ref.numel() != labels.numel()):
+        raise ValueError(f"policy_loss: {n_seq} utterances over {labels.numel()} rows need {n_seq} advantages and old_logps / ref_logps "
+                         f"of {labels.numel()} entries, got {adv.numel()}, {old.numel()}" + ("" if ref is None else f", {ref.numel()}"))
+    tokens = seq_token_counts(labels, ignore_index, seq_start).double()
+    denom = tokens.clamp(min=1) * n_seq if normalize == "sequence" else tokens.sum().clamp(min=1).expand(n_seq)
+    loss, rows = fused_linear_policy(hidden, labels, lm_head.weight, lm_head.bias, ignore_index, seq_start=seq_start, adv=adv,
+                                     seq_w=(1.0 / denom).float(), old_logp=old, ref_logp=ref, clip=clip, kl_beta=kl_beta)
+    lab = labels.reshape(-1)
+    _, inside = _row_sequences(seq_start.to(device=dev, dtype=torch.int64).clamp(0, lab.numel()), 0, lab.numel())
+    return dict(loss=loss, valid=inside & (lab != ignore_index), **rows)
+
+
+@torch.no_grad()
+def token_logprob_rows(hidden, labels, lm_head, ignore_index):
+    """token_logprobs of the heads: fp32 [rows] log softmax(lm_head(hidden))[label], 0 on ignored rows -- _score_rows' cross-entropy
+    row losses (the held-out evaluation walk; smoothing 0), negated."""
+    loss_rows, _, lab, _ = _score_rows(hidden, labels.to(hidden.device), lm_head.weight, lm_head.bias, ignore_index, EVAL_CE, 0.0, None)
+    return torch.where(lab != ignore_index, -loss_rows, torch.zeros_like(loss_rows))

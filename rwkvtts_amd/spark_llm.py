@@ -21,8 +21,8 @@ import torch.nn.functional as F
 from .backbone import Cache, Linear, ModelOutput, RWKV7Config, RWKV7Model
 from .hf_api import HFModelMixin
 from .losses import (EVAL_CE, SCORE_KEYS, eval_mode, fused_linear_cross_entropy, fused_linear_eval, fused_linear_score,
-                     fused_linear_seq_logprob, padded_seq_start, scored_forward,
-                     seq_token_counts)
+                     fused_linear_seq_logprob, padded_seq_start, policy_objective, scored_forward,
+                     seq_token_counts, token_logprob_rows)
 
 
 class RWKV7SpeechConfig(RWKV7Config):
@@ -122,17 +122,17 @@ class RWKV7ForSpeech(HFModelMixin, nn.Module):
             loss_sum, tokens, correct = fused_linear_eval(hidden, labels, self.lm_head.weight, self.lm_head.bias, ignore_index, EVAL_CE)
         return dict(loss=(loss_sum / tokens).float().reshape(()), loss_sum=loss_sum, tokens=tokens, correct=correct, denom=tokens)
 
-    def _scored_rows(self, input_ids, attention_mask, inputs_embeds, labels, kwargs):
-        """What eval_metrics, score (inside eval_mode) and sequence_logprobs (the current mode: forward's dropout on inputs_embeds
-        while training) evaluate: the backbone's hidden states, forward's shifted labels, the ignore index and cu_seqlens (None for a
-        padded batch)."""
+    def _scored_rows(self, input_ids, attention_mask, inputs_embeds, labels, kwargs, on_tape=False):
+        """What eval_metrics, score (inside eval_mode), sequence_logprobs and policy_loss (the current mode: forward's dropout on
+        inputs_embeds while training) evaluate: the backbone's hidden states, forward's shifted labels, the ignore index and cu_seqlens
+        (None for a padded batch).  on_tape (policy_loss): the backbone is called directly, once, with autograd as forward calls it."""
         for k in ("past_key_values", "use_cache", "output_attentions", "output_hidden_states", "return_dict", "logits_to_keep"):
             kwargs.pop(k, None)
         if self.training and inputs_embeds is not None:
             inputs_embeds = self.dropout(inputs_embeds)
         # scored_forward: under no_grad the plain call; with autograd (sequence_logprobs) the same no_grad pass, recomputed in backward
-        hidden = scored_forward(lambda ids, emb: self.model(input_ids=ids, attention_mask=attention_mask, inputs_embeds=emb, **kwargs)[0],
-                                input_ids, inputs_embeds)
+        run = lambda ids, emb: self.model(input_ids=ids, attention_mask=attention_mask, inputs_embeds=emb, **kwargs)[0]   # noqa: E731
+        hidden = run(input_ids, inputs_embeds) if on_tape else scored_forward(run, input_ids, inputs_embeds)
         ignore_index = getattr(self.criterion, "ignore_index", -100)
         labels = labels.to(hidden.device)
         labels = torch.cat((labels[..., 1:], torch.full_like(labels[:, :1], ignore_index)), 1)
@@ -179,6 +179,29 @@ class RWKV7ForSpeech(HFModelMixin, nn.Module):
         seq_start = self._utterance_rows(labels, cu, hidden.device)
         logp = fused_linear_seq_logprob(hidden, labels, self.lm_head.weight, self.lm_head.bias, ignore_index, seq_start=seq_start)
         return dict(logp=logp, tokens=seq_token_counts(labels, ignore_index, seq_start))
+
+    def policy_loss(self, *, advantages, old_logps, ref_logps=None, clip=(0.2, 0.2), kl_beta=0.0, normalize="sequence", input_ids=None,
+                    attention_mask=None, inputs_embeds=None, labels=None, **kwargs):
+        """The token-level clipped policy objective (GRPO / PPO-clip; DataParallelTrainer.policy_step) over
+        exactly score's rows, shifted labels and utterances, in the module's current mode.  The backbone runs ONCE, directly under
+        autograd (not through losses.scored_forward); the head is losses.fused_linear_policy, so the [B, T, V] logits never exist.
+        advantages [utterances]; old_logps / ref_logps [B * T] in score's flattened row order (token_logprobs gives them).
+        normalize: "sequence" -- every row of utterance s weighs 1 / (utterances * tokens_s) (GRPO; an utterance without a valid
+        position still counts among the utterances) -- or "token" -- every row weighs 1 / (all valid positions).
+        Returns a dict: loss (fp64 scalar, differentiable), logp / kl / clipped (detached fp32 [B * T], 0 on rows that do not count)
+        and valid (bool [B * T]: the rows that count)."""
+        hidden, labels, ignore_index, cu = self._scored_rows(input_ids, attention_mask, inputs_embeds, labels, kwargs, on_tape=True)
+        seq_start = self._utterance_rows(labels, cu, hidden.device)
+        return policy_objective(hidden, labels, self.lm_head, ignore_index, seq_start, advantages, old_logps, ref_logps, clip, kl_beta,
+                                normalize)
+
+    def token_logprobs(self, input_ids=None, attention_mask=None, inputs_embeds=None, labels=None, **kwargs):
+        """log p(label) of every row of score's flattened rows (fp32 [B * T], 0 on ignored rows): eval mode, no autograd, the previous
+        mode restored; the row losses of the held-out evaluation walk (rwkv7_head_eval_bf16 on the HIP route), negated.  The exact
+        source of policy_loss's old_logps and ref_logps."""
+        with eval_mode(self):
+            hidden, labels, ignore_index, _ = self._scored_rows(input_ids, attention_mask, inputs_embeds, labels, kwargs)
+            return token_logprob_rows(hidden, labels, self.lm_head, ignore_index)
 
     def prepare_inputs_for_generation(self, input_ids=None, past_key_values=None, attention_mask=None,
                                       inputs_embeds=None, use_cache=True, logits_to_keep=None, **kwargs):

@@ -879,6 +879,54 @@ class DataParallelTrainer:
         out["loss"] = self._step_on(loss_fn)
         return {k: out[k] for k in ("loss", "margin", "accuracy", "logp_chosen", "logp_rejected")}
 
+    def policy_step(self, *, advantages, old_logps, ref_logps=None, clip=(0.2, 0.2), kl_beta=0.0, normalize="sequence", **batch):
+        """One optimisation step of the token-level clipped policy gradient (GRPO / PPO-clip) on this rank's
+        utterances: model.policy_loss(**batch) with one advantage per utterance (losses.group_advantages forms GRPO's from rewards),
+        old_logps [rows] the sampling policy's log p(label) of every row of score's flattened rows (token_logprobs gives them) and,
+        optionally, ref_logps [rows] a frozen reference's, which adds kl_beta times the k3 KL estimator per token.  The backbone
+        forward runs ONCE, on the tape (the module's current mode).  The loss then takes exactly step()'s path (_step_on): armed
+        hooks, the on-device NaN flag (raised by a non-finite loss, a non-finite advantage, or a non-finite old_logps / ref_logps
+        entry on a row that counts: a zero-gradient step on every rank), the bucketed exchange, clipping, the AdamW launches,
+        reattach, step_idx.  No host read.  Not allowed inside an accumulation window.  Returns device tensors (detached): loss,
+        clip_frac (share of the rows that count whose clipped branch was the minimum), kl (token mean of the k3 estimator; 0 without
+        ref_logps) and ratio_mean (token mean of exp(lp - old_logps))."""
+        if self._acc_count != 0:
+            raise RuntimeError(f"policy_step inside an accumulation window ({self._acc_count} micro-batches pending): "
+                               "call step() first")
+        out = {}
+
+        def loss_fn():
+            try:
+                res = self.model.policy_loss(advantages=advantages, old_logps=old_logps, ref_logps=ref_logps, clip=clip,
+                                             kl_beta=kl_beta, normalize=normalize, **batch)
+            except BaseException:
+                self.flat.reattach()   # whatever it was, nothing ran backward: the hooks are disarmed again
+                raise
+            valid, lp = res["valid"], res["logp"]
+            dev = lp.device
+            n = valid.sum().clamp(min=1).double()
+            old = torch.as_tensor(old_logps).to(device=dev, dtype=torch.float32).reshape(-1)
+            bad = ~torch.isfinite(torch.as_tensor(advantages).to(dev).double()).all() | (~torch.isfinite(old) & valid).any()
+            if ref_logps is not None:
+                bad = bad | (~torch.isfinite(torch.as_tensor(ref_logps).to(device=dev, dtype=torch.float32).reshape(-1)) & valid).any()
+            zero = torch.zeros_like(lp)
+            out.update(clip_frac=res["clipped"].double().sum() / n, kl=res["kl"].double().sum() / n,
+                       ratio_mean=torch.where(valid, torch.exp(lp - old), zero).double().sum() / n)
+            return res["loss"], bad
+
+        out["loss"] = self._step_on(loss_fn)
+        return {k: out[k] for k in ("loss", "clip_frac", "kl", "ratio_mean")}
+
+    def token_logprobs(self, batches):
+        """log p(label) of every row of this rank's batches: model.token_logprobs per batch (eval mode under no_grad, so nothing of the
+        run moves -- see score), a list with one device fp32 tensor [rows] per batch in score's flattened row order, 0 on ignored
+        rows.  No collective, no host read.  What policy_step takes as old_logps (from the policy before the update) and ref_logps
+        (from a frozen reference).  Not allowed inside an accumulation window."""
+        if self._acc_count != 0:
+            raise RuntimeError(f"token_logprobs inside an accumulation window ({self._acc_count} micro-batches pending): "
+                               "call step() first")
+        return [self.model.token_logprobs(**batch) for batch in batches]
+
     def evaluate(self, batches):
         """Held-out evaluation.  batches: an iterable of batch dicts, this rank's shard (at least one batch on
         every rank).  model.eval_metrics per batch; the sums stay on the device, ONE all_reduce(SUM) at the end when world > 1 (a
