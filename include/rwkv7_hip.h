@@ -537,6 +537,19 @@ int rwkv7_ce_fwd_bwd_ls_bf16(long rows, int V, void *logits, const long *labels,
  *      neither read nor written). */
 int rwkv7_ce_fwd_bwd_ld_bf16(long rows, int V, long ld, void *logits, const long *labels, long ignore_index, float scale, float *loss_rows,
                              float label_smoothing, rwkv7_stream_t stream);
+/*      The same with two regularisers of the logits' scale added to the GRADIENT (losses.fused_linear_cross_entropy(z_loss, max_logit);
+ *      DESIGN.md section 6.8).  For a valid row with p = softmax, lse = logsumexp, m = max_j x_j (all fp32 from the bf16 logits), a the
+ *      LOWEST index with x_a = m and t the (smoothed) target, element j is REPLACED by
+ *        (p_j (1 + 2 z_coef lse) - t_j + [j == a] max_coef m) * scale      (formed in fp32, rounded to bf16 once)
+ *      -- the gradient of CE + z_coef lse^2 + 0.5 max_coef m^2.  loss_rows stays the PLAIN cross-entropy of the row, bit for bit what
+ *      rwkv7_ce_fwd_bwd_ld_bf16 writes; lse_rows[row] = lse and max_rows[row] = m (fp32 [rows], each may be NULL; m is exact).  Rows
+ *      with label == ignore_index are replaced by zeros and give 0 in all three outputs.  With z_coef = max_coef = 0 the logits are
+ *      replaced by the bits rwkv7_ce_fwd_bwd_ld_bf16 writes.  Columns V .. ld - 1 are neither read nor written.  No LDS, no atomics,
+ *      nothing shared between rows.  RWKV7_EINVAL, before any launch: a NULL logits / labels / loss_rows, rows <= 0, V <= 0, ld < V,
+ *      label_smoothing outside [0, 1), z_coef or max_coef negative, infinite or a NaN. */
+int rwkv7_ce_reg_fwd_bwd_bf16(long rows, int V, long ld, void *logits, const long *labels, long ignore_index, float scale, float *loss_rows,
+                              float label_smoothing, float z_coef, float max_coef, float *lse_rows, float *max_rows,
+                              rwkv7_stream_t stream);
 /*      The backward of a per-SEQUENCE sum of log-probabilities (losses.fused_linear_seq_logprob): the plain cross-entropy gradient
  *      (label smoothing 0) of a chunk of logits [rows, ld] whose scale is looked up per row.  Row r of the chunk is row row0 + r of the
  *      batch; its sequence is the largest s < n_seq with seq_start[s] <= row0 + r, provided row0 + r < seq_start[n_seq] (seq_start:

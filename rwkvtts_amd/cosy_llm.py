@@ -39,6 +39,9 @@ class RWKV7CosyConfig(RWKV7Config):
         self.llm_input_size = self.llm_input_size or self.hidden_size
         self.llm_output_size = self.llm_output_size or self.hidden_size
         self.mix_ratio = list(self.mix_ratio)
+        if kw.get("z_loss") or kw.get("max_logit"):
+            raise ValueError("RWKV7CosyConfig: z_loss / max_logit exist for the cross-entropy heads (Spark, XY) only; the "
+                             "label-smoothing KL head has no such regulariser")
         self.extra = {k: v for k, v in kw.items() if k not in base and k not in self._EXTRA}
 
     def to_dict(self):

@@ -539,6 +539,15 @@ int rwkv7_ce_fwd_bwd_ld_bf16(long rows, int V, long ld, void *logits, const long
     if (!(label_smoothing >= 0.f && label_smoothing < 1.f)) return RWKV7_EINVAL;
     return rwkv7::ce_fwd_bwd(rows, V, ld, logits, labels, ignore_index, scale, loss_rows, label_smoothing, (hipStream_t)stream);
 }
+int rwkv7_ce_reg_fwd_bwd_bf16(long rows, int V, long ld, void *logits, const long *labels, long ignore_index, float scale, float *loss_rows,
+                              float label_smoothing, float z_coef, float max_coef, float *lse_rows, float *max_rows,
+                              rwkv7_stream_t stream) {
+    if (rows <= 0 || V <= 0 || ld < V || any_null({(const void *)logits, (const void *)labels, (const void *)loss_rows})) return RWKV7_EINVAL;
+    if (!(label_smoothing >= 0.f && label_smoothing < 1.f)) return RWKV7_EINVAL;
+    if (!(z_coef >= 0.f && z_coef < INFINITY && max_coef >= 0.f && max_coef < INFINITY)) return RWKV7_EINVAL;
+    return rwkv7::ce_reg_fwd_bwd(rows, V, ld, logits, labels, ignore_index, scale, loss_rows, label_smoothing, z_coef, max_coef, lse_rows,
+                                 max_rows, (hipStream_t)stream);
+}
 int rwkv7_ce_seq_bwd_bf16(long rows, int V, long ld, void *logits, const long *labels, long ignore_index, long row0, long n_seq,
                           const long *seq_start, const float *seq_scale, float *loss_rows, rwkv7_stream_t stream) {
     if (rows <= 0 || V <= 0 || ld < V || row0 < 0 || n_seq <= 0 ||

@@ -1,6 +1,7 @@
 // rwkvtts_amd/csrc/head_loss.hip -- the three kernels that walk a row of bf16 head logits [rows, ld]: the two training heads (loss and
 // d loss / d logits in one pass; the cross-entropy one also with a scale per SEQUENCE, rwkv7_ce_seq_bwd_bf16, and with the clipped
-// policy-gradient coefficient per ROW, rwkv7_ce_policy_fwd_bwd_bf16) and the forward-only
+// policy-gradient coefficient per ROW, rwkv7_ce_policy_fwd_bwd_bf16, and with the z-loss / max-logit regularisers,
+// rwkv7_ce_reg_fwd_bwd_bf16) and the forward-only
 // metrics of held-out evaluation.  They share ONE row body (the anonymous namespace
 // below): how a row is split, how a thread folds elements into (m, ssum, xsum[, best]), how two such partials merge, the two closing
 // loss formulas and the gradient of an element.  A kernel adds only its structure: which thread owns which element and in which order
@@ -161,7 +162,7 @@ __device__ __forceinline__ uint4 grad_piece(const uint4 r, int base, float lse, 
 // label smoothing ls: d loss / d x_j = softmax_j - ls / V - (1 - ls) [j == label].
 // ld: elements between rows (>= V; round 6: the Spark head's logits live in a buffer padded to a multiple of 256 columns, so rows are 16-byte
 // aligned and the head GEMMs see aligned leading dimensions)
-// Where a row's scale comes from is the kernel's one parameter (Scale, the three structs below): one value for the whole chunk
+// Where a row's scale comes from is the kernel's first parameter (Scale, the three structs below): one value for the whole chunk
 // (rwkv7_ce_fwd_bwd*_bf16: loss_rows is never NULL there), the value of the row's SEQUENCE (rwkv7_ce_seq_bwd_bf16, the backward of
 // losses.fused_linear_seq_logprob: the upstream gradient of a per-sequence sum of log-probabilities differs from sequence to sequence,
 // so it cannot be applied to the finished gradient afterwards as one scalar; loss_rows may be NULL), or the clipped policy-gradient
@@ -254,9 +255,46 @@ struct PolicyScale {
     }
 };
 
-template <typename Scale>
+// What is added to a row's gradient beside the cross-entropy is the kernel's second parameter (Reg).  reg.row(...) is called by all 64
+// lanes of the row's wave once the row's partials have met (acc is the whole row's on every lane) and returns the row's map of a softmax
+// value p_j to what takes its place in front of "- target_j":
+//   NoReg    : p_j itself, from RowAcc<false> -- the code of the three cross-entropy entries as it always was.
+//   LogitReg : p_j k + [j == a] c m  (rwkv7_ce_reg_fwd_bwd_bf16), k = 1 + 2 z lse the derivative of lse + z lse^2
+//              by lse, c m the derivative of 0.5 c m^2 by the row's maximum m, which lands on a, the LOWEST index among the row's maxima
+//              (RowAcc<true>: head_eval_kernel's arg-max fold, which changes no bit of m, ssum or xsum).  Lane 0 writes the row's lse and
+//              m (0 for an ignored row; each array may be NULL).  At z = c = 0: k = 1 and the bump 0 exactly, the row is NoReg's.
+struct NoReg {
+    static constexpr bool ARGMAX = false;
+    struct Row {
+        __device__ __forceinline__ float operator()(float p, int) const { return p; }
+    };
+    __device__ __forceinline__ Row row(long, bool, float, const RowAcc<false> &, int) const { return Row{}; }
+};
+
+struct LogitReg {
+    static constexpr bool ARGMAX = true;
+    float z, c;
+    float *lse_rows, *max_rows;
+    struct Row {
+        float k, cm;
+        int a;
+        __device__ __forceinline__ float operator()(float p, int j) const {
+            const float q = p * k;
+            return j == a ? q + cm : q;
+        }
+    };
+    __device__ __forceinline__ Row row(long row, bool valid, float lse, const RowAcc<true> &acc, int lane) const {
+        if (lane == 0) {
+            if (lse_rows) lse_rows[row] = valid ? lse : 0.f;
+            if (max_rows) max_rows[row] = valid ? acc.m : 0.f;
+        }
+        return Row{1.f + 2.f * z * lse, c * acc.m, acc.best};
+    }
+};
+
+template <typename Scale, typename Reg>
 __global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(long rows, int V, long ld, bf16_t *__restrict__ logits, const long *__restrict__ labels,
-                                                         long ignore_index, Scale scale_of, float *__restrict__ loss_rows, float ls) {
+                                                         long ignore_index, Scale scale_of, Reg reg, float *__restrict__ loss_rows, float ls) {
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -265,7 +303,7 @@ __global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(long rows, int V, long 
     const bool valid = lab != ignore_index;
     const RowSplit sp = row_split(x, V);
     const uint4 *xv = reinterpret_cast<const uint4 *>(x + sp.head);
-    RowAcc<false> acc;
+    RowAcc<Reg::ARGMAX> acc;
     acc_init(acc);
     if (lane < sp.head) acc_one(acc, bf2f(x[lane]), lane);
     if (sp.tail0 + lane < V) acc_one(acc, bf2f(x[sp.tail0 + lane]), sp.tail0 + lane);
@@ -277,7 +315,8 @@ __global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(long rows, int V, long 
     if (lane == 0 && loss_rows) loss_rows[row] = valid ? ce_row_loss(lse, acc.xsum, xlab, V, ls) : 0.f;
     const float sc = scale_of(row, valid, xlab - lse, lane), hit = 1.f - ls, off_all = ls / (float)V;
     const int labi = (int)lab;   // an ignored row's gradient is 0 whatever this matches
-    auto minus_target = [&](float p, int j) { return p - off_all - (j == labi ? hit : 0.f); };
+    const auto reg_row = reg.row(row, valid, lse, acc, lane);
+    auto minus_target = [&](float p, int j) { return reg_row(p, j) - off_all - (j == labi ? hit : 0.f); };
     if (lane < sp.head) x[lane] = grad_one(bf2f(x[lane]), lane, lse, sc, minus_target);
     if (sp.tail0 + lane < V) x[sp.tail0 + lane] = grad_one(bf2f(x[sp.tail0 + lane]), sp.tail0 + lane, lse, sc, minus_target);
     uint4 *xw = reinterpret_cast<uint4 *>(x + sp.head);
@@ -287,16 +326,25 @@ __global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(long rows, int V, long 
 int ce_fwd_bwd(long rows, int V, long ld, void *logits, const long *labels, long ignore_index, float scale, float *loss_rows,
                float label_smoothing, hipStream_t st) {
     (void)hipGetLastError();
-    hipLaunchKernelGGL(ce_fwd_bwd_kernel<UniformScale>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, rows, V, ld, (bf16_t *)logits,
-                       labels, ignore_index, UniformScale{scale}, loss_rows, label_smoothing);
+    hipLaunchKernelGGL((ce_fwd_bwd_kernel<UniformScale, NoReg>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, rows, V, ld,
+                       (bf16_t *)logits, labels, ignore_index, UniformScale{scale}, NoReg{}, loss_rows, label_smoothing);
+    return (int)hipGetLastError();
+}
+
+int ce_reg_fwd_bwd(long rows, int V, long ld, void *logits, const long *labels, long ignore_index, float scale, float *loss_rows,
+                   float label_smoothing, float z_coef, float max_coef, float *lse_rows, float *max_rows, hipStream_t st) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL((ce_fwd_bwd_kernel<UniformScale, LogitReg>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, rows, V, ld,
+                       (bf16_t *)logits, labels, ignore_index, UniformScale{scale}, LogitReg{z_coef, max_coef, lse_rows, max_rows}, loss_rows,
+                       label_smoothing);
     return (int)hipGetLastError();
 }
 
 int ce_seq_bwd(long rows, int V, long ld, void *logits, const long *labels, long ignore_index, long row0, long n_seq,
                const long *seq_start, const float *seq_scale, float *loss_rows, hipStream_t st) {
     (void)hipGetLastError();
-    hipLaunchKernelGGL(ce_fwd_bwd_kernel<SeqScale>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, rows, V, ld, (bf16_t *)logits,
-                       labels, ignore_index, SeqScale{{row0, n_seq, seq_start}, seq_scale}, loss_rows, 0.f);
+    hipLaunchKernelGGL((ce_fwd_bwd_kernel<SeqScale, NoReg>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, rows, V, ld, (bf16_t *)logits,
+                       labels, ignore_index, SeqScale{{row0, n_seq, seq_start}, seq_scale}, NoReg{}, loss_rows, 0.f);
     return (int)hipGetLastError();
 }
 
@@ -306,8 +354,8 @@ int ce_policy_fwd_bwd(long rows, int V, long ld, void *logits, const long *label
     (void)hipGetLastError();
     const PolicyScale ps{{row0, n_seq, seq_start}, adv, seq_w, old_lp, ref_lp, 1.0 - (double)eps_lo, 1.0 + (double)eps_hi, (double)beta,
                          lp_rows, loss_rows, kl_rows, clip_rows};
-    hipLaunchKernelGGL(ce_fwd_bwd_kernel<PolicyScale>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, rows, V, ld, (bf16_t *)logits,
-                       labels, ignore_index, ps, nullptr, 0.f);
+    hipLaunchKernelGGL((ce_fwd_bwd_kernel<PolicyScale, NoReg>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, rows, V, ld, (bf16_t *)logits,
+                       labels, ignore_index, ps, NoReg{}, nullptr, 0.f);
     return (int)hipGetLastError();
 }
 

@@ -136,6 +136,9 @@ int state_rows_adamw_f32(int layers, int A, const void *const *grad_tbl, void *c
 //      distribution; argmax_rows, and ce_seq_bwd's loss_rows, may be NULL
 int ce_fwd_bwd(long rows, int V, long ld, void *logits, const long *labels, long ignore_index, float scale, float *loss_rows,
                float label_smoothing, hipStream_t stream);
+//      lse_rows and max_rows may be NULL
+int ce_reg_fwd_bwd(long rows, int V, long ld, void *logits, const long *labels, long ignore_index, float scale, float *loss_rows,
+                   float label_smoothing, float z_coef, float max_coef, float *lse_rows, float *max_rows, hipStream_t stream);
 int ce_seq_bwd(long rows, int V, long ld, void *logits, const long *labels, long ignore_index, long row0, long n_seq,
                const long *seq_start, const float *seq_scale, float *loss_rows, hipStream_t stream);
 //      ref_lp and each of the four per-row outputs may be NULL

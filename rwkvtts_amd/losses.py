@@ -122,8 +122,13 @@ class _HeadGrads:
 
 class _FusedLinearCE(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, hidden, weight, bias, labels, ignore_index, chunk, label_smoothing):
+    def forward(ctx, hidden, weight, bias, labels, ignore_index, chunk, label_smoothing, z_loss=0.0, max_logit=0.0, stats=None):
         N, D = hidden.shape
+        # the logit regularisers (fused_linear_cross_entropy's z_loss / max_logit / stats).  Off -- both
+        # coefficients 0 and no stats tensor -- every line below runs as it did before they existed.
+        reg = z_loss != 0 or max_logit != 0 or stats is not None
+        if reg:
+            reg_sums = torch.zeros(3, dtype=torch.float32, device=hidden.device)   # sum lse, sum lse^2, sum m over the valid rows
         valid = labels != ignore_index
         n_valid = valid.sum().clamp(min=1)
         inv = 1.0 / n_valid.float()
@@ -162,8 +167,17 @@ class _FusedLinearCE(torch.autograd.Function):
                 else:
                     pd = F.linear(h, weight, bias)   # bf16 logits as nn.Linear gives them (the bias inside the GEMM's fp32 epilogue)
                 loss_rows = torch.empty(rows, dtype=torch.float32, device=pd.device)
-                _lib.call("rwkv7_ce_fwd_bwd_ld_bf16", pd, rows, V, pd.shape[1], pd, lab.contiguous(), ignore_index, 1.0, loss_rows,
-                          float(label_smoothing))
+                if reg:
+                    # the same kernel text with the regularisers in the gradient; loss_rows stays the plain CE, the row's lse and
+                    # maximum come out beside it (0 on ignored rows, so plain sums are sums over the valid rows)
+                    side = torch.empty(2, rows, dtype=torch.float32, device=pd.device)
+                    _lib.call("rwkv7_ce_reg_fwd_bwd_bf16", pd, rows, V, pd.shape[1], pd, lab.contiguous(), ignore_index, 1.0, loss_rows,
+                              float(label_smoothing), float(z_loss), float(max_logit), side[0], side[1])
+                    LOGIT_REG_HITS[0] += 1
+                    reg_sums += torch.stack((side[0].sum(), (side[0] * side[0]).sum(), side[1].sum()))
+                else:
+                    _lib.call("rwkv7_ce_fwd_bwd_ld_bf16", pd, rows, V, pd.shape[1], pd, lab.contiguous(), ignore_index, 1.0, loss_rows,
+                              float(label_smoothing))
                 loss += loss_rows.sum()
                 grads.add(pd, h, s, s + rows)
                 continue
@@ -181,13 +195,25 @@ class _FusedLinearCE(torch.autograd.Function):
             else:
                 per = nll
             loss += (per * vmask).sum()
+            row_reg = None
+            if reg:
+                a = logits.argmax(dim=-1)   # the lowest index among the maxima
+                m = logits.gather(1, a.unsqueeze(1)).squeeze(1)
+                reg_sums += torch.stack(((lse * vmask).sum(), (lse * lse * vmask).sum(), (m * vmask).sum()))
+                if z_loss != 0 or max_logit != 0:
+                    row_reg = (1 + 2 * z_loss * lse, a, max_logit * m)
             if need[0] or need[1]:
-                p = _grad_rows_torch(logits, lab, label_smoothing, vmask * inv)
+                p = _grad_rows_torch(logits, lab, label_smoothing, vmask * inv, row_reg)
                 grads.add(p.to(hidden.dtype), h, s, s + rows, p)
         # the HIP path leaves dh / dw unscaled (scale = 1 in the kernel: 1/n_valid lives on the device); backward folds
         # 1/n_valid into the incoming gradient
         ctx.save_for_backward(grads.dh, grads.dw[:V] if need[1] else None, grads.db, inv if hip_ce else None)
         ctx.hdtype, ctx.wdtype = hidden.dtype, weight.dtype
+        if reg:
+            if stats is not None:
+                stats += torch.cat((valid.sum().float().reshape(1), reg_sums))
+            if z_loss != 0:
+                loss = loss + z_loss * reg_sums[1]
         return loss * inv
 
     @staticmethod
@@ -195,9 +221,18 @@ class _FusedLinearCE(torch.autograd.Function):
         dh, dw, db, post = ctx.saved_tensors
         if post is not None:
             g = g * post
-        return _HeadGrads.scaled(dh, dw, db, g, ctx.hdtype, ctx.wdtype) + (None, None, None, None)
+        return _HeadGrads.scaled(dh, dw, db, g, ctx.hdtype, ctx.wdtype) + (None,) * 7
 
 
+def check_logit_reg(z_loss, max_logit, who):
+    """The configs' validation of the two coefficients: finite floats >= 0."""
+    z, c = float(z_loss), float(max_logit)
+    if not (z >= 0 and c >= 0 and math.isfinite(z) and math.isfinite(c)):
+        raise ValueError(f"{who}: z_loss and max_logit must be finite and >= 0, got {z_loss}, {max_logit}")
+    return z, c
+
+
+LOGIT_REG_HITS = [0]   # launches of rwkv7_ce_reg_fwd_bwd_bf16 (one per chunk): how a test sees which route a call took
 LOGITS_CHUNK_BYTES = int(os.environ.get("RWKV7_CE_CHUNK_BYTES", str(1 << 30)))
 
 
@@ -211,17 +246,33 @@ def auto_chunk(rows, V, esize=2):
 
 
 def fused_linear_cross_entropy(hidden, labels, weight, bias=None, ignore_index=-100, chunk=None,
-                               label_smoothing=0.0):
+                               label_smoothing=0.0, z_loss=0.0, max_logit=0.0, stats=None):
     """hidden [..., D], labels [...] (already shifted by the caller) -> mean CE over labels != ignore_index.
-    chunk: rows per round of head GEMMs (None: auto_chunk)."""
+    chunk: rows per round of head GEMMs (None: auto_chunk).
+    z_loss, max_logit (>= 0): two regularisers of the logits' scale.  With lse the row's logsumexp and m its
+    largest logit, the gradients are those of the mean over the valid rows of  CE + z_loss lse^2 + 0.5 max_logit m^2  (m's gradient
+    lands on the lowest index among the row's maxima; the reference's L2Wrap, rwkv_s2s_single_ffn.py:261-273, is max_logit =
+    factor x rows).  The RETURNED loss is (sum CE + z_loss sum lse^2) / n_valid: the 0.5 max_logit m^2 term is gradient-only, as
+    in the reference, whose L2Wrap returns the loss unchanged.
+    stats: a caller-owned fp32 [4] tensor on hidden's device; the call ADDS (n_valid, sum lse, sum lse^2, sum m) over its valid rows
+    into it, with no host read (DataParallelTrainer.last_logit_stats).
+    With both coefficients 0 and stats None the call is what it was before these arguments existed, bit for bit.  Otherwise the HIP
+    route (padded head included) runs rwkv7_ce_reg_fwd_bwd_bf16 -- the cross-entropy kernel's text with the two terms in the gradient
+    -- on the same bf16 logits, and the torch route (fp32 models, RWKV7_HIP_CE=0, the CPU) the same arithmetic from fp32 logits."""
+    z_loss, max_logit = check_logit_reg(z_loss, max_logit, "fused_linear_cross_entropy")
+    if stats is not None and not (stats.dtype == torch.float32 and stats.shape == (4,) and stats.device == hidden.device):
+        raise ValueError("fused_linear_cross_entropy: stats must be an fp32 [4] tensor on the hidden states' device")
     D = hidden.shape[-1]
     if chunk is None:
         # the HIP kernel path keeps ONE bf16 logits tensor per chunk; the torch chain (RWKV7_HIP_CE=0, fp32 models, int32 labels, a
         # non-bf16 bias) keeps fp32 logits, an fp32 softmax and a copy in the hidden dtype: budget 3 x 4 bytes per logit there
         hip = _hip_gate(hidden, labels, weight, bias)
         chunk = auto_chunk(hidden.numel() // D, weight.shape[0], hidden.element_size() if hip else 12)
+    if z_loss == 0 and max_logit == 0 and stats is None:
+        return _FusedLinearCE.apply(hidden.reshape(-1, D), weight, bias, labels.reshape(-1), ignore_index, chunk,
+                                    label_smoothing)
     return _FusedLinearCE.apply(hidden.reshape(-1, D), weight, bias, labels.reshape(-1), ignore_index, chunk,
-                                label_smoothing)
+                                label_smoothing, z_loss, max_logit, stats)
 
 
 def label_smoothing_kl(logits, target, size, padding_idx, smoothing, normalize_length=False):
@@ -418,10 +469,15 @@ def _eval_rows_torch(logits, labels, ignore_index, kind, smoothing):
     return per.masked_fill(~valid, 0.0), correct
 
 
-def _grad_rows_torch(logits, labels, smoothing, row_scale):
+def _grad_rows_torch(logits, labels, smoothing, row_scale, row_reg=None):
     """d (row loss) / d logits of the cross-entropy with label smoothing in torch, fp32 [rows, V] from fp32 logits: (softmax - smoothed
-    one-hot) * row_scale[row]; row_scale fp32 [rows] carries the upstream scale and the 0 of an ignored row."""
+    one-hot) * row_scale[row]; row_scale fp32 [rows] carries the upstream scale and the 0 of an ignored row.
+    row_reg: None, or (k, a, cm) per row -- rwkv7_ce_reg_fwd_bwd_bf16's regularisers: softmax_j becomes softmax_j k + [j == a] cm."""
     p = torch.softmax(logits, dim=-1)
+    if row_reg is not None:
+        k, a, cm = row_reg
+        p = p * k.unsqueeze(1)
+        p.scatter_add_(1, a.unsqueeze(1), cm.unsqueeze(1))
     if smoothing > 0:
         p = p - smoothing / logits.shape[-1]
     p.scatter_add_(1, labels.clamp(min=0).unsqueeze(1), torch.full_like(p[:, :1], -(1 - smoothing)))

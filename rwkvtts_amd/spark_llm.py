@@ -20,24 +20,26 @@ import torch.nn.functional as F
 
 from .backbone import Cache, Linear, ModelOutput, RWKV7Config, RWKV7Model
 from .hf_api import HFModelMixin
-from .losses import (EVAL_CE, SCORE_KEYS, eval_mode, fused_linear_cross_entropy, fused_linear_eval, fused_linear_score,
+from .losses import (EVAL_CE, SCORE_KEYS, check_logit_reg, eval_mode, fused_linear_cross_entropy, fused_linear_eval, fused_linear_score,
                      fused_linear_seq_logprob, padded_seq_start, policy_objective, scored_forward,
                      seq_token_counts, token_logprob_rows)
 
 
 class RWKV7SpeechConfig(RWKV7Config):
-    """spark_llm.py:13-17: RWKV7Config + text_vocab_size + audio_global_vocab_size."""
+    """spark_llm.py:13-17: RWKV7Config + text_vocab_size + audio_global_vocab_size.  z_loss, max_logit (not in the reference's config,
+    default off): the logit regularisers of the fused training loss (losses.fused_linear_cross_entropy)."""
 
-    def __init__(self, text_vocab_size=65536, audio_global_vocab_size=4096, **kw):
+    def __init__(self, text_vocab_size=65536, audio_global_vocab_size=4096, z_loss=0.0, max_logit=0.0, **kw):
         super().__init__(**{k: v for k, v in kw.items() if k in RWKV7Config.__dataclass_fields__ and k != "extra"})
         self.extra = {k: v for k, v in kw.items() if k not in RWKV7Config.__dataclass_fields__}
         self.text_vocab_size = text_vocab_size
         self.audio_global_vocab_size = audio_global_vocab_size
+        self.z_loss, self.max_logit = check_logit_reg(z_loss, max_logit, "RWKV7SpeechConfig")
 
     def to_dict(self):
         d = super().to_dict()
         d.update(text_vocab_size=self.text_vocab_size, audio_global_vocab_size=self.audio_global_vocab_size,
-                 architectures=["RWKV7ForSpeech"])
+                 z_loss=self.z_loss, max_logit=self.max_logit, architectures=["RWKV7ForSpeech"])
         return d
 
     @classmethod
@@ -64,6 +66,7 @@ class RWKV7ForSpeech(HFModelMixin, nn.Module):
         self.global_embedder = nn.Embedding(config.audio_global_vocab_size, config.hidden_size)
         self.tts_tag_embedder = nn.Embedding(3, config.hidden_size)  # GLOBAL=0, SEMANTIC=1, START_TTS=2
         self.dropout = nn.Dropout(0.02)
+        self.logit_stats = None   # fp32 [4] device tensor the fused training loss adds its logit statistics into (the trainer's)
 
     # ---- forward -------------------------------------------------------------------------------------
     def forward(self, input_ids=None, attention_mask=None, inputs_embeds=None, past_key_values: Optional[Cache] = None,
@@ -99,7 +102,8 @@ class RWKV7ForSpeech(HFModelMixin, nn.Module):
                     labels = torch.where(pos.unsqueeze(0) >= cu[-1].to(labels.device), torch.full_like(labels, ignore_index), labels)
             if fuse:
                 loss = fused_linear_cross_entropy(hidden_states, labels, self.lm_head.weight, self.lm_head.bias,
-                                                  ignore_index)
+                                                  ignore_index, z_loss=self.config.z_loss, max_logit=self.config.max_logit,
+                                                  stats=self.logit_stats)
             elif self.criterion is not None:
                 loss = self.criterion(logits.view(labels.numel(), -1), labels.view(-1))
             else:

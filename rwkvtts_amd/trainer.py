@@ -536,7 +536,7 @@ class DataParallelTrainer:
     def __init__(self, model: torch.nn.Module, lr=1e-4, lr_final=1e-5, warmup_steps=100, total_steps=100000,
                  weight_decay=0.0, betas=(0.9, 0.95), eps=1e-18, bucket_bytes=32 << 20, nan_guard=True,
                  master_fp32=True, param_groups=None, schedule="linear", force_allreduce=False, shard_optimizer=False,
-                 bucket_optimizer=True, max_grad_norm=None):
+                 bucket_optimizer=True, max_grad_norm=None, logit_stats=False):
         """shard_optimizer: every rank reduces the gradient pieces of ITS 1/N slab only, steps AdamW on that slab and broadcasts
         the slab's new bf16 parameters (reduce-scatter + sharded optimizer + all-gather, ZeRO-1 style: the reference's DeepSpeed
         ZeRO-2 engine does the same exchange, train_spark_rwkv7speech.py:483-516).  Same parameters after every step as the
@@ -557,7 +557,14 @@ class DataParallelTrainer:
         pass sits behind the last all-reduce.  Every rank computes the factor from identical data: replicas stay bit-identical.
         A non-finite norm makes the step a zero-gradient step, like a NaN loss.  float('inf') = measure only.
         `last_grad_norm` (None without max_grad_norm): device fp32 scalar, the pre-clip norm of the last step; step() never
-        reads it on the host."""
+        reads it on the host.
+        logit_stats: keep the scale of the head's logits.  Always on when the model's config has a non-zero
+        z_loss or max_logit.  The trainer owns an fp32 [4] device tensor that the model's fused training loss adds (tokens, sum lse,
+        sum lse^2, sum max logit) into -- every micro-batch and, for the XY model, every channel -- zeroes it at the start of every
+        optimizer step, and after step() exposes `last_logit_stats`: {"mean_lse", "mean_lse_sq", "mean_max", "tokens"}, device
+        tensors of THIS rank's rows only (no collective, no synchronisation).  evaluate, score, preference_step and policy_step
+        neither see the coefficients nor touch the statistics.  Needs a model whose training loss is the fused cross-entropy (Spark,
+        XY)."""
         self.model = model
         self.bucket_optimizer = bool(bucket_optimizer)
         self.flat = FlatBuffers(model)
@@ -632,6 +639,14 @@ class DataParallelTrainer:
         self._acc32 = None
         self._acc_count = 0
         self._acc_flag = torch.zeros(1, dtype=torch.float32, device=dev)
+        cfg = getattr(model, "config", None)
+        self.last_logit_stats = None
+        self._logit_stats = None
+        if logit_stats or getattr(cfg, "z_loss", 0.0) or getattr(cfg, "max_logit", 0.0):
+            if not hasattr(model, "logit_stats"):
+                raise ValueError("DataParallelTrainer(logit_stats=True): the model's training loss does not keep logit statistics "
+                                 "(the Spark and XY models do)")
+            self._logit_stats = model.logit_stats = torch.zeros(4, dtype=torch.float32, device=dev)
         self.step_idx = 0
         self.last_lr = None
         self._pending = None          # the one non-blocking save in flight (PendingCheckpoint)
@@ -739,6 +754,8 @@ class DataParallelTrainer:
         if self._acc32 is None:
             self._acc32 = torch.empty(self.flat.numel, dtype=torch.float32, device=self.flat.flat_grad.device)
         first = self._acc_count == 0
+        if first and self._logit_stats is not None:
+            self._logit_stats.zero_()
         self.flat.arm()
         on_ready, self.flat.on_ready = self.flat.on_ready, None   # the reducer does not see this pass
         try:
@@ -777,7 +794,15 @@ class DataParallelTrainer:
         gradients (rwkv7_grad_fold_bf16, mean over k, one rounding to bf16) right before it goes on the wire, so the exchange still
         overlaps this backward pass; the NaN flag that is all-reduced is the max over the k micro-batches.  Without a preceding
         accumulate() nothing of that runs."""
-        return self._step_on(lambda: (self.model(**batch).loss, None))
+        if self._logit_stats is None:
+            return self._step_on(lambda: (self.model(**batch).loss, None))
+        if self._acc_count == 0:
+            self._logit_stats.zero_()
+        loss = self._step_on(lambda: (self.model(**batch).loss, None))
+        n, s_lse, s_sq, s_max = self._logit_stats.clone().unbind(0)
+        d = n.clamp(min=1)
+        self.last_logit_stats = dict(mean_lse=s_lse / d, mean_lse_sq=s_sq / d, mean_max=s_max / d, tokens=n)
+        return loss
 
     def _step_on(self, loss_fn):
         """The body of step() for any scalar loss: loss_fn() runs the forward pass (after the gradient hooks are armed) and returns

@@ -20,14 +20,15 @@ import torch.nn.functional as F
 
 from .backbone import Cache, ModelOutput, RWKV7Config, RWKV7Model
 from .hf_api import HFModelMixin
-from .losses import (EVAL_CE, SCORE_KEYS, eval_mode, fused_linear_cross_entropy, fused_linear_eval, fused_linear_score,
+from .losses import (EVAL_CE, SCORE_KEYS, check_logit_reg, eval_mode, fused_linear_cross_entropy, fused_linear_eval, fused_linear_score,
                      padded_seq_start)
 
 
 class RWKV7XYConfig(RWKV7Config):
-    """xy_llm.py:17-28."""
+    """xy_llm.py:17-28.  z_loss, max_logit (not in the reference's config, default off): the logit regularisers of the fused training
+    loss, applied to every channel's head (losses.fused_linear_cross_entropy)."""
     _EXTRA = dict(llm_input_size=None, speech_vocab_size=1024, length_normalized_loss=True, lsm_weight=0.0,
-                  num_channels=8, drop_ratio=0.0, speech_pad_token=None, text_shift_size=65536)
+                  num_channels=8, drop_ratio=0.0, speech_pad_token=None, text_shift_size=65536, z_loss=0.0, max_logit=0.0)
 
     def __init__(self, **kw):
         base = {k: v for k, v in kw.items() if k in RWKV7Config.__dataclass_fields__ and k != "extra"}
@@ -37,6 +38,7 @@ class RWKV7XYConfig(RWKV7Config):
         self.llm_input_size = self.llm_input_size or self.hidden_size
         if self.speech_pad_token is None:
             self.speech_pad_token = self.speech_vocab_size - 1
+        self.z_loss, self.max_logit = check_logit_reg(self.z_loss, self.max_logit, "RWKV7XYConfig")
         self.extra = {k: v for k, v in kw.items() if k not in base and k not in self._EXTRA}
 
     def to_dict(self):
@@ -66,6 +68,7 @@ class RWKV7XYLM(HFModelMixin, nn.Module):
                                           padding_idx=config.speech_vocab_size - 1))
             self.heads.append(nn.Linear(config.hidden_size, config.speech_vocab_size))
         self.dropout = nn.Dropout(config.drop_ratio) if config.drop_ratio > 0 else None
+        self.logit_stats = None   # fp32 [4] device tensor the fused training loss adds its logit statistics into (the trainer's)
 
     def get_input_embeddings(self):
         return self.embs[0]
@@ -102,7 +105,8 @@ class RWKV7XYLM(HFModelMixin, nn.Module):
             for i in range(self.config.num_channels):
                 total_loss = total_loss + fused_linear_cross_entropy(
                     hidden, labels[:, :, i], self.heads[i].weight, self.heads[i].bias, -100,
-                    label_smoothing=self.config.lsm_weight)
+                    label_smoothing=self.config.lsm_weight, z_loss=self.config.z_loss, max_logit=self.config.max_logit,
+                    stats=self.logit_stats)
         else:
             all_logits = [self.heads[i](hidden) for i in range(self.config.num_channels)]
             if labels is not None:
