@@ -722,6 +722,10 @@ int rwkv7_wgrad_skinny_bf16(long M, int N, int K, int S, const void *dy, const v
 /*   wgrad_mid: the same partials for the [W_a ; W_b] gradient of the through-the-lerp projections (dy = dG [M][N], N = 2 R in {512, 576};
  *   K a multiple of 256; rows per slab a multiple of 64): neither side is skinny, a workgroup holds a [N / 2][256] fp32 tile. */
 int rwkv7_wgrad_mid_bf16(long M, int N, int K, int S, const void *dy, const void *x, float *parts, rwkv7_stream_t stream);
+/*   wgrad_tn: the same partials for the dense projections (r / k / v / o and the channel-mix key / value, autograd of
+ *   rwkv_s2s_single_ffn.py:171-174, 195, 228-229): N and K multiples of 256, rows per slab a multiple of 128 (RWKV7_ESHAPE otherwise,
+ *   nothing is launched); a workgroup holds a 256 x 256 fp32 tile and reads both operands token-major (csrc/wgrad_tn.hip). */
+int rwkv7_wgrad_tn_bf16(long M, int N, int K, int S, const void *dy, const void *x, float *parts, rwkv7_stream_t stream);
 
 /* ---- C[M][N] = epi(A[M][K] . W[N][K]^T), bf16, fp32 accumulation: the channel-mix key projection with its activation as
  *      the epilogue (epilogue 1: relu(.)^2, rwkv_s2s_single_ffn.py:228; 0: none).  Hand-written persistent MFMA kernel fed by

@@ -614,6 +614,12 @@ int rwkv7_wgrad_mid_bf16(long M, int N, int K, int S, const void *dy, const void
     if (M <= 0 || S <= 0 || M % S != 0 || (M / S) % 64 != 0 || K <= 0 || K % 256 != 0 || (N != 512 && N != 576)) return RWKV7_ESHAPE;
     return rwkv7::wgrad_mid_bf16(M, N, K, S, dy, x, parts, (hipStream_t)stream);
 }
+int rwkv7_wgrad_tn_bf16(long M, int N, int K, int S, const void *dy, const void *x, float *parts, rwkv7_stream_t stream) {
+    if (any_null({dy, x, parts})) return RWKV7_EINVAL;
+    if (M <= 0 || S <= 0 || N <= 0 || K <= 0) return RWKV7_EINVAL;
+    if (M % S != 0 || M / S > 0x7fffffffL || (M / S) % 128 != 0 || N % 256 != 0 || K % 256 != 0) return RWKV7_ESHAPE;
+    return rwkv7::wgrad_tn_bf16(M, N, K, S, dy, x, parts, (hipStream_t)stream);
+}
 int rwkv7_sum_slabs_bf16(long n, int S, const float *parts, void *out, int accumulate, rwkv7_stream_t stream) {
     if (n <= 0 || S <= 0 || any_null({(const void *)parts, (const void *)out})) return RWKV7_EINVAL;
     if (n % 4 != 0) return RWKV7_ESHAPE;

@@ -77,6 +77,7 @@ int lora32_bf16(int M, int N, int K, int R, int act, const void *x, const void *
                 hipStream_t stream);
 int wgrad_skinny_bf16(long M, int N, int K, int S, const void *dy, const void *x, float *parts, hipStream_t stream);
 int wgrad_mid_bf16(long M, int N, int K, int S, const void *dy, const void *x, float *parts, hipStream_t stream);
+int wgrad_tn_bf16(long M, int N, int K, int S, const void *dy, const void *x, float *parts, hipStream_t stream);   // wgrad_tn.hip
 
 // ---- low-rank branches through the token-shift lerp (mix_lora.hip).  Passed by value into the kernels
 struct MixLoraDesc {

@@ -810,6 +810,31 @@ MID_WGRAD_SLABS = 32
 MID_WGRAD_HITS = [0]
 
 
+# The dense projections' weight gradients (r / k / v / o 1024 x 1024, channel-mix key / value 4096 x 1024 / 1024 x 4096) on the own
+# token-major kernel rwkv7_wgrad_tn_bf16 (csrc/wgrad_tn.hip) instead of the library's slabs.  Only the (N, K) classes listed here, each
+# measured to win WITH its reduction (tools/wgrad_tn_ab.py, profiles/wgrad_tn_ab.txt), take it; the value is the slab count.
+# RWKV7_TN_WGRAD=0: the library slabs.
+TN_WGRAD = os.environ.get("RWKV7_TN_WGRAD", "1") == "1"
+TN_WGRAD_CLASSES = {(4096, 1024): 4, (1024, 4096): 4}
+TN_WGRAD_HITS = [0]
+
+
+def _wgrad_tn(dy2, x2, out, S):
+    """The TN_WGRAD route of wgrad_splitk; None when the entry does not take the shape (nothing was launched)."""
+    M, N = dy2.shape
+    K = x2.shape[1]
+    part = torch.empty(S, N, K, dtype=torch.float32, device=dy2.device)
+    try:
+        _lib.call("rwkv7_wgrad_tn_bf16", part, M, N, K, S, dy2, x2, part)
+    except ValueError:   # RWKV7_ESHAPE: rows per slab or a tile edge
+        return None
+    if out is None:
+        out = torch.empty(N, K, dtype=torch.bfloat16, device=dy2.device)
+    _lib.call("rwkv7_sum_slabs_bf16", part, N * K, S, part, out, 0)
+    TN_WGRAD_HITS[0] += 1
+    return out
+
+
 def wgrad_splitk(dy2, x2, out=None, slabs=None):
     """dy2[M,N]^T @ x2[M,K] -> [N,K].  The reduction runs over M = B*T rows (32768 at BASELINE configs[1]) while the
     result is at most a few 256x256 tiles, so one BLAS call leaves most CUs idle (measured on MI355X, tools/
@@ -829,6 +854,12 @@ def wgrad_splitk(dy2, x2, out=None, slabs=None):
         _lib.call("rwkv7_wgrad_skinny_bf16", part, M, N, K, S, dy2, x2, part)
         _lib.call("rwkv7_sum_slabs_bf16", part, N * K, S, part, out, 0)
         return out
+    # a listed class goes first: the list is explicit, the routes below trigger on shape alone
+    if (TN_WGRAD and (N, K) in TN_WGRAD_CLASSES and dy2.dtype == torch.bfloat16 and x2.dtype == torch.bfloat16 and M >= WGRAD_MIN_ROWS
+            and dy2.is_contiguous() and x2.is_contiguous()):
+        res = _wgrad_tn(dy2, x2, out, slabs if slabs else TN_WGRAD_CLASSES[(N, K)])
+        if res is not None:
+            return res
     if (MID_WGRAD and dy2.dtype == torch.bfloat16 and x2.dtype == torch.bfloat16 and N in (512, 576) and K % 256 == 0 and M >= WGRAD_MIN_ROWS
             and M % (MID_WGRAD_SLABS * 64) == 0 and dy2.is_contiguous() and x2.is_contiguous()):
         # the [W_a ; W_b] gradient of fused.mix_lora: rwkv7_wgrad_mid_bf16 (csrc/wgrad_skinny.hip) + one reduction

@@ -27,6 +27,7 @@ def steps(n):
 
 switches = [("head: logits in a buffer padded to 256 columns, logits GEMM on the own kernel (losses.PADDED_HEAD)", losses, "PADDED_HEAD", False, True),
             ("weight gradient of [W_a ; W_b] (N = 576) on the own kernel rwkv7_wgrad_mid_bf16", fused, "MID_WGRAD", False, True),
+            ("weight gradients of the dense projections on the own token-major kernel rwkv7_wgrad_tn_bf16", fused, "TN_WGRAD", False, True),
             ("low-rank down projections: lerp as the A prologue of the own MFMA kernel (csrc/lora_down.hip)", fused, "LORA_DOWN_DIRECT", False, True),
             ("channel-mix backward: W_value^T through the own transpose kernel", fused, "TRANSPOSE_KERNEL", False, True),
             ("time-mix side: add + LayerNorm + three lerps one-pass forward (with mix_lora)", fused, "FUSED_ADD_LN_MIX_LORA_FWD", False, True),
